@@ -24,13 +24,24 @@ N ways (--scaling strong); rank g scans shard g (+ an (L-1)-byte halo), the DFA 
 and the compact match planes of all steps of a block go to rank 0 in ONE RCCL gather inside
 the timed block.
 
-Prints ONE JSON line on rank 0.  The headline is BASELINE.json configs[1] (clamav2000); at N = 1
-the line also carries sub-records for configs[2] (clamav15000) and configs[4] (sentiment), an
-end-to-end figure that includes the host-to-device copy, and the CPU baseline.
+Prints ONE JSON line on rank 0.  The headline is BASELINE.json configs[1] (clamav2000).  A plain run
+does only what that figure needs: set-up, --warmup steps (and, for a block of at most PERIOD_STEPS
+steps, three untimed runs of the block), ONE timed block of exactly --steps steps (--repeats blocks
+when given), the outputs of the last step if --dump-outputs DIR is given, the line.
+--full adds what else the line used to carry: the median of --repeats (5) blocks with HIP events
+around the kernels (roofline), parity against the oracle, and at N = 1 sub-records for configs[2]
+(clamav15000) and configs[4] (sentiment), side measurements (one batch / one launch group in
+flight, no launch groups), an end-to-end figure that includes the host-to-device copy, and the CPU
+baseline.
+
+--dump-outputs DIR: what the timed path returned for its last step (rank 0: all ranks' records
+merged) as float64 arrays, DIR/offsets.npy, DIR/patterns.npy, DIR/final_state.npy and
+DIR/match_count.npy; the texts are seeded, so the same arguments give the same arrays.
 """
 import argparse
 import ctypes as C
 import json
+import math
 import os
 import statistics
 import sys
@@ -46,6 +57,21 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 SHARD = 32 << 20
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 L3_BYTES = 256 << 20        # Infinity Cache
+PERIOD_STEPS = 4096         # beyond this many steps a block reuses its batches (see run_workload)
+DUMP_RECORDS = 3 << 20      # --dump-outputs: at most this many records (2 x 8 B each), a seeded sample beyond
+
+
+def dump_outputs(path, offs, pids, last_state):
+    """The records of one step as float64 .npy files (offsets < 2^32 and pattern ids are exact in float64)."""
+    os.makedirs(path, exist_ok=True)
+    n = offs.size
+    if n > DUMP_RECORDS:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_RECORDS, replace=False))
+        offs, pids = offs[keep], pids[keep]
+    np.save(os.path.join(path, "offsets.npy"), offs.astype(np.float64))
+    np.save(os.path.join(path, "patterns.npy"), pids.astype(np.float64))
+    np.save(os.path.join(path, "final_state.npy"), np.array([last_state], dtype=np.float64))
+    np.save(os.path.join(path, "match_count.npy"), np.array([n], dtype=np.float64))
 
 
 def log(rank, *a):
@@ -182,6 +208,7 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
     from gpu_pattern_matching_amd._lib import check
     rank, world, dev, args = ctx["rank"], ctx["world"], ctx["dev"], ctx["args"]
     strong = args.scaling == "strong" and world > 1
+    full = args.full
 
     t0 = time.perf_counter()
     aut = wl.automaton()
@@ -250,7 +277,7 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
     ws_bytes = matcher.lib.acm_scan_workspace_bytes(matcher.dfa, n_local)
     cap = wl.cap
     W = max(1, workers)
-    K = max(W, steps)
+    K = max(1, steps)
     streams = [torch.cuda.Stream(device=dev) for _ in range(W)]
     # a worker's consecutive steps alternate between G workspaces: acm_scan_batches_async then puts
     # up to G of them into one set of launches (--group 1: every step has its own three launches)
@@ -274,13 +301,23 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
     def worker_of(k):
         return (k // Geff) % W
 
-    # planes of every step of a block: [K, 2, cap] when they all have to survive until the gather /
+    # Step k of a block is scanned by batch k % P, and a block is issued as whole periods of P batches (one
+    # library call each) plus the first batches of one more.  P = K up to PERIOD_STEPS steps (one call, as
+    # ever); beyond, a multiple of a round of launch groups and of the text rotation, so that every step reads
+    # the text and runs on the stream and in the launch group it would anyway, and the host's per-step set-up
+    # stays bounded whatever --steps.  Steps k and k + P share planes and workspace on one stream: in order.
+    P = K
+    if not dist.is_initialized() and K > PERIOD_STEPS:
+        unit = math.lcm(Geff * W * pe, ntexts)
+        P = min(K, unit * max(1, PERIOD_STEPS // unit))
+
+    # planes of every batch of a block: [P, 2, cap] when they all have to survive until the gather /
     # the check, else a ring of R slots PER WORKER (two streams never write one slot; the slots of a
     # launch group are distinct; the last ncheck steps of a block -- the ones that get checked -- survive)
     ncheck = max(1, min(ntexts, args.check_texts))      # the last steps of a block whose planes are checked
     R = max(Geff, ncheck, 2)
-    ring = not (world > 1 or K * cap * 8 <= (512 << 20)) and W * R < K
-    slots = W * R if ring else K
+    ring = not (world > 1 or P * cap * 8 <= (512 << 20)) and W * R < P
+    slots = W * R if ring else P
 
     def slot_of(k):
         if not ring:
@@ -302,11 +339,11 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
         """is step k one of worker 0's whose kernels are timed?  Whole launch groups, every pe-th of them."""
         return worker_of(k) == 0 and (k // (Geff * W)) % pe == 0
 
-    timed_steps = sum(1 for k in range(K) if timed(k))
+    timed_steps = sum(1 for k in range(P) if timed(k)) * (K // P) + sum(1 for k in range(K % P) if timed(k))
 
     def batches(profile):
         out = []
-        for k in range(K):
+        for k in range(P):
             w, p = worker_of(k), planes[slot_of(k)]
             out.append(matcher.make_batch(d_texts[k % ntexts], n_local, streams[w].cuda_stream, p[0], p[1], cap,
                                           (wss[w][k % G], ws_bytes), halo=plan["halo"],
@@ -314,7 +351,9 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
                                           profile=profile and timed(k)))
         return out
 
-    plain, profiled = batches(False), batches(True)
+    # a plain run times the scans alone; --full times them with HIP events around the kernels (roofline)
+    plain = batches(False)
+    profiled = batches(True) if full else plain
     native = args.issue == "native" or (args.issue == "threads" and W == 1)   # one worker: the caller is the thread
     pool = Pool(W) if (W > 1 and args.issue == "threads") else None
     enq, enq_many = matcher.lib.acm_scan_batch_async, matcher.lib.acm_scan_batches_async
@@ -337,11 +376,11 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
                 lo = hi
         return out
 
-    whole = {(id(bs), c): (Batch * c)(*bs[:c]) for bs in (plain, profiled) for c in {K, min(K, max(warmup, W))}}
+    whole = {(id(bs), c): (Batch * c)(*bs[:c]) for bs in (plain, profiled) for c in {P, K % P, max(0, warmup) % P} if c}
     chunked = native and dist.is_initialized() and not ring
     piecewise = {id(bs): [(lo, hi, (Batch * (hi - lo))(*bs[lo:hi])) for lo, hi in pieces(K)]
                  for bs in (plain, profiled)} if chunked else {}
-    mine_of = [[k for k in range(K) if worker_of(k) == w] for w in range(W)]
+    mine_of = [[k for k in range(P) if worker_of(k) == w] for w in range(W)]
     share = {id(bs): [(Batch * max(1, len(mine_of[w])))(*[bs[k] for k in mine_of[w]]) for w in range(W)]
              for bs in (plain, profiled)}
 
@@ -367,6 +406,15 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
                 if rc:
                     check(rc, "acm_scan_batch_async")
         return time.perf_counter() - t
+
+    def issue_steps(bs, n):
+        """n consecutive steps: whole periods of P batches, then the first n % P of one more"""
+        t = 0.0
+        for _ in range(n // P):
+            t += issue(bs, P)
+        if n % P:
+            t += issue(bs, n % P)
+        return t
 
     def fence():
         torch.cuda.synchronize()
@@ -416,7 +464,7 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
     def block(bs):
         """the K steps of a block and the gather of their planes; returns the host's enqueue seconds"""
         if not chunked:
-            t = issue(bs, K)
+            t = issue_steps(bs, K)
             gather()
             return t
         t = 0.0
@@ -429,24 +477,38 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
             gather(lo, hi)
         return t
 
-    issue(plain, min(K, max(warmup, W)))
+    issue_steps(plain, max(0, warmup))
     gather()
     fence()
+    if not full and K <= PERIOD_STEPS:
+        # three untimed runs of the block itself: the first short blocks behind the warm-up run slower than
+        # those behind them (20 steps: 0.21-0.28 ms, then 0.19-0.20, however long the warm-up), which --full's
+        # median of five blocks leaves out.  At most PERIOD_STEPS steps; a longer block does not notice.
+        for _ in range(3):
+            block(plain)
+            fence()
     blocks, host_issue = [], []
     matcher.profile_read()
     for rep in range(max(1, repeats)):
         fence()
         t0 = time.perf_counter()
-        host_issue.append(block(profiled))      # (worker 0's launch groups carry HIP events in every block)
+        host_issue.append(block(profiled))      # (--full: worker 0's launch groups carry HIP events in every block)
         fence()
         blocks.append(time.perf_counter() - t0)
     k1_ms, k2_ms, pipe_ms, launches = matcher.profile_read()
     elapsed = statistics.median(blocks)
-    host_planes = planes.cpu().numpy()      # the planes of the last timed block
-    gathered_host = [g.cpu().numpy() for g in gathered] if gathered is not None else None
+    # the planes of the last timed block: all of them for the parity check, else those of its last step
+    last_slot = slot_of((K - 1) % P)
+    host_planes = planes.cpu().numpy() if verify else None
+    gathered_host = [g.cpu().numpy() for g in gathered] if (verify and gathered is not None) else None
+    last_planes = planes[last_slot].cpu().numpy()
+    if rank == 0 and headline and args.dump_outputs:
+        dump_outputs(args.dump_outputs, *sharding.merge_gathered(
+            [g[last_slot] for g in gathered] if gathered is not None else [last_planes]))
+    extra = full and not args.no_extra
     # the same block with a set of launches per step (no launch groups), for comparison: three blocks
     ungrouped = None
-    if headline and world == 1 and Geff > 1 and matcher.sparse_eligible() and args.mode != "chain" and not args.no_extra:
+    if headline and world == 1 and Geff > 1 and matcher.sparse_eligible() and args.mode != "chain" and extra:
         matcher.lib.acm_scan_set_max_group(matcher.dfa, 1)
         ub = []
         for rep in range(3):
@@ -460,7 +522,7 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
     # one batch in flight (outside the timed region): what the kernels take when they have the GPU
     # to themselves
     scratch = torch.zeros((2, cap), dtype=torch.int32, device=dev)
-    for i in range(0 if args.no_extra else 12):
+    for i in range(12 if extra else 0):
         matcher.enqueue(matcher.make_batch(d_texts[i % ntexts], n_local, streams[0].cuda_stream, scratch[0], scratch[1],
                                            cap, (wss[0][0], ws_bytes), halo=plan["halo"],
                                            offset_shift=plan["offset_shift"], profile=True))
@@ -469,7 +531,7 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
     # ... and one launch group of Geff batches in flight, alone
     g_k1 = g_k2 = g_pipe = 0.0
     g_n = 0
-    if Geff > 1 and not args.no_extra:
+    if Geff > 1 and extra:
         gsc = torch.zeros((Geff, 2, cap), dtype=torch.int32, device=dev)
         for i in range(6):
             matcher.enqueue_many([matcher.make_batch(d_texts[(i * Geff + j) % ntexts], n_local, streams[0].cuda_stream,
@@ -491,7 +553,7 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
     # ---- end to end with the host-to-device copy: the reference's Mbps definition counts bytes
     #      from the files to the results (ocl_aho_grep.c:580,598,614,628-630) ------------------------
     e2e = None
-    if headline and world == 1 and not args.no_e2e:
+    if full and headline and world == 1 and not args.no_e2e:
         pinned = [torch.from_numpy(np.ascontiguousarray(h)).pin_memory() for h in h_texts]
         stage = [torch.zeros_like(d_texts[0]) for _ in range(W)]
         ne = 72            # 2.25 GiB behind a warm-up of 6 steps (24 cold steps measured the link's ramp: 37 of its 57 GB/s)
@@ -522,9 +584,7 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
                        "h2d_only: the same copies without the scans" % We}
 
     # ---- parity: the planes of the last steps of the last block, every distinct text once -----------
-    owner = {slot_of(k): k for k in range(K)}            # the last step that wrote each slot
-    last_k = [k for k in range(max(0, K - ncheck), K) if owner[slot_of(k)] == k]
-    m_local = int(host_planes[slot_of(K - 1), 0, 0])
+    m_local = int(last_planes[0, 0])
     m_total = m_local
     if world > 1:
         t = torch.tensor([m_local], dtype=torch.int64, device=red)
@@ -532,15 +592,18 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
         m_total = int(t.item())
     parity, cpu, out = "not checked", None, None
     if rank == 0:
-        if verify or (headline and not args.no_cpu_baseline):
+        if verify or (full and headline and not args.no_cpu_baseline):
             o = wl.oracle()
             if verify:
+                # every batch index occurs among the last P steps: the last step that wrote each slot is there
+                owner = {slot_of(k % P): k for k in range(max(0, K - P), K)}
+                last_k = [k for k in range(max(0, K - ncheck), K) if owner[slot_of(k % P)] == k]
                 ok, nrec = True, 0
                 for k in last_k:
                     if gathered_host is not None:
-                        offs, pids, last_state = sharding.merge_gathered([g[slot_of(k)] for g in gathered_host])
+                        offs, pids, last_state = sharding.merge_gathered([g[slot_of(k % P)] for g in gathered_host])
                     else:
-                        offs, pids, last_state = sharding.merge_gathered([host_planes[slot_of(k)]])
+                        offs, pids, last_state = sharding.merge_gathered([host_planes[slot_of(k % P)]])
                     epos, epat, elast = o.scan(logical(k % ntexts), cap=max(cap * world, 1 << 16))
                     good = np.array_equal(epos, offs) and np.array_equal(epat, pids) and elast == last_state
                     if not good:
@@ -550,7 +613,7 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
                     nrec += epos.size
                 parity = ("bit-exact vs oracle serial scan on %d distinct texts (%d records)" % (len(last_k), nrec)
                           if ok else "MISMATCH")
-            if headline and world == 1 and not args.no_cpu_baseline:
+            if full and headline and world == 1 and not args.no_cpu_baseline:
                 mine = h_texts[0]
                 best, reps, t_start = 1e30, 0, time.perf_counter()
                 while time.perf_counter() - t_start < args.cpu_seconds or reps < 2:
@@ -569,35 +632,7 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
                        "all_cores": {"value": round(SHARD / t_all / 1e9, 4), "cores": ncpu}}
             o.close()
 
-        # The roofline is quoted for the kernel that reads the text (the bulk pass: k_sieve, or
-        # k_spec_walk of the chain pipeline): algorithmic bytes = N x 1 B of text + 8 B per record
-        #  over that kernel's average duration, HIP events on the worker's own stream
-        # inside the timed region.
-        alg_batch = n_local + 8 * m_local
-        # batches one launch of the bulk kernel processes (the timed groups' average: the last group
-        # of a block may be short)
-        grouped = (timed_steps * max(1, repeats) / max(launches, 1)) if (groups_apply and launches) else 1
-        alg_bytes = int(alg_batch * grouped)
-        kname = "k_sieve" if path == "sparse" else ("k_lds_walk" if matcher_lds else "k_spec_walk")
-        L1 = max(launches, 1)
-        k_s = k1_ms / 1e3 / L1
-        achieved = alg_bytes / k_s / 1e9 if k_s > 0 else 0.0
         value = total_bytes * K / elapsed / 1e9
-        traffic, stage_traffic = None, {}
-        tfile = os.path.join(ROOT, "profiles", "r3_traffic_%s.json" % wl.name)
-        if not os.path.exists(tfile):
-            tfile = os.path.join(ROOT, "profiles", "r2_traffic_%s.json" % wl.name)
-        if os.path.exists(tfile):
-            for name, rec in json.load(open(tfile)).items():
-                if name.startswith("k_"):     # (the short names; the file also has the full ones and the copies)
-                    stage_traffic[name] = round(rec["hbm_bytes_per_launch"], 1)
-            if kname == "k_spec_walk" and "k_halo_walk" in stage_traffic and "k_spec_walk" not in stage_traffic:
-                kname = "k_halo_walk"     # (halo mode with the text loaded up front: its own kernel)
-            if kname == "k_lds_walk" and "k_lds_walk" not in stage_traffic:
-                stage_traffic = {}        # (counters of the kernels this workload no longer runs)
-            traffic = stage_traffic.get(kname)
-            if traffic is not None:
-                traffic = round(traffic * grouped, 1)     # (the counters were collected with one batch per launch)
         out = {
             "value": round(value, 3),
             "steps": K,
@@ -627,7 +662,37 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
             "matches_per_s": round(m_total * K / elapsed, 1),
             "frac_of_hbm_peak": round(value / world / HBM_PEAK_GBS, 5),
             "parity": parity,
-            "roofline": {
+        }
+        alg_batch = n_local + 8 * m_local
+        if full:
+            # The roofline is quoted for the kernel that reads the text (the bulk pass: k_sieve, or
+            # k_spec_walk of the chain pipeline): algorithmic bytes = N x 1 B of text + 8 B per record
+            #  over that kernel's average duration, HIP events on the worker's own stream
+            # inside the timed region.
+            # batches one launch of the bulk kernel processes (the timed groups' average: the last group
+            # of a block may be short)
+            grouped = (timed_steps * max(1, repeats) / max(launches, 1)) if (groups_apply and launches) else 1
+            alg_bytes = int(alg_batch * grouped)
+            kname = "k_sieve" if path == "sparse" else ("k_lds_walk" if matcher_lds else "k_spec_walk")
+            L1 = max(launches, 1)
+            k_s = k1_ms / 1e3 / L1
+            achieved = alg_bytes / k_s / 1e9 if k_s > 0 else 0.0
+            traffic, stage_traffic = None, {}
+            tfile = os.path.join(ROOT, "profiles", "r3_traffic_%s.json" % wl.name)
+            if not os.path.exists(tfile):
+                tfile = os.path.join(ROOT, "profiles", "r2_traffic_%s.json" % wl.name)
+            if os.path.exists(tfile):
+                for name, rec in json.load(open(tfile)).items():
+                    if name.startswith("k_"):     # (the short names; the file also has the full ones and the copies)
+                        stage_traffic[name] = round(rec["hbm_bytes_per_launch"], 1)
+                if kname == "k_spec_walk" and "k_halo_walk" in stage_traffic and "k_spec_walk" not in stage_traffic:
+                    kname = "k_halo_walk"     # (halo mode with the text loaded up front: its own kernel)
+                if kname == "k_lds_walk" and "k_lds_walk" not in stage_traffic:
+                    stage_traffic = {}        # (counters of the kernels this workload no longer runs)
+                traffic = stage_traffic.get(kname)
+                if traffic is not None:
+                    traffic = round(traffic * grouped, 1)     # (the counters were collected with one batch per launch)
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": kname,
                 "achieved": round(achieved, 2),
@@ -646,8 +711,7 @@ def run_workload(ctx, wl, steps, warmup, repeats, ntexts, workers, verify, headl
                         "in every timed block (1: all of them); with %d workers a kernel shares the GPU with the other workers' "
                         "kernels.  traffic = the bulk kernel's counted HBM bytes for ONE batch (profiles/, collected "
                         "with --group 1) x batches_per_launch; stage_traffic: per batch" % (pe, W),
-            },
-        }
+            }
         if s_n:
             sk = s_k1 / 1e3 / s_n
             out["roofline_one_batch_in_flight"] = {
@@ -690,7 +754,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps; the median is reported (default: 1, with --full 5)")
     ap.add_argument("--workload", default="clamav2000", choices=["clamav2000", "clamav10000", "clamav15000", "sentiment"])
     ap.add_argument("--sub", default="clamav15000,sentiment",
                     help="workloads reported as sub-records of the line (N = 1 only); '' for none")
@@ -726,7 +791,15 @@ def main():
                     help="only the warm-up and the timed blocks: no one-batch / one-group / ungrouped side measurements "
                          "(for a profiler run whose per-kernel averages should be those of the timed region)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything else the line can carry: HIP events in the timed blocks (roofline), parity against "
+                         "the oracle, sub-records, side measurements, end to end with the copy, CPU baseline (the --no-* "
+                         "options turn parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the headline's last timed step to DIR/*.npy (float64)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     # one hardware queue per batch in flight: with HIP's default of 4 queues per process the
     # streams of the workers (+ torch's own) share queues and serialise
@@ -763,15 +836,16 @@ def main():
     if args.gather == "abi" and dist.is_initialized() and backend == "nccl":
         ctx["rccl_comm"] = rccl_communicator(torch, dist, rank, world, ctx["dev"])
 
+    verify = args.full and not args.no_verify
     head = run_workload(ctx, Workload(args.workload, args.plant), args.steps, args.warmup, args.repeats,
-                        max(1, args.texts), args.workers, not args.no_verify, True)
+                        max(1, args.texts), args.workers, verify, True)
     subs = {}
-    if world == 1 and args.sub:
+    if args.full and world == 1 and args.sub:
         for name in args.sub.split(","):
             if not name or name == args.workload:
                 continue
             rec = run_workload(ctx, Workload(name, args.plant), args.steps, args.warmup, args.repeats,
-                               max(1, args.sub_texts or args.texts), args.workers, not args.no_verify, False)
+                               max(1, args.sub_texts or args.texts), args.workers, verify, False)
             if rec is not None:
                 subs[name] = rec
 

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for mw in ${2:-chain:2 sparse:1 sparse:2 sparse:3 sparse:4}; do
 	mode=${mw%%:*}; w=${mw##*:}; extra=""
 	case $w in *g) w=${w%g}; extra="--graphs";; esac
-	timeout -k 10 200 python3 bench.py --steps 200 --warmup 20 --mode $mode --workers $w --no-cpu-baseline $extra ${BENCH_ARGS} \
+	timeout -k 10 200 python3 bench.py --full --steps 200 --warmup 20 --mode $mode --workers $w --no-cpu-baseline $extra ${BENCH_ARGS} \
 		>> gpurun_out/sweep_$TAG.jsonl 2> gpurun_out/sweep_$TAG.err || exit 1
 done
 python3 - <<PY

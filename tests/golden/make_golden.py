@@ -14,6 +14,15 @@ first records).  The texts themselves are regenerated from seeds
 
 The reference ships no expected outputs: these vectors are what
 pins the oracle and the HIP path.
+
+    python tests/golden/make_golden.py compiled
+
+writes tests/golden/compiled_reference.json instead: what
+test_oracle_golden.py::test_oracle_equals_compiled_reference compares the oracle with
+(state count, sha256 of the whole table, the match lists of sampled states, a scan from a
+drawn state and the all-patterns walk over the reference's table and match lists), so that
+the comparison holds where oracle/_ref cannot be built.  The same test still compares
+live wherever oracle/_ref exists.
 """
 import hashlib
 import json
@@ -125,5 +134,59 @@ def main():
     print("wrote golden.json")
 
 
+COMPILED_SETS = ["tests", "tests1", "tests3", "sentiment", "clamav2000_m12"]
+HEX_SAMPLES = ["00ff10", "deadBEEF", "0a0B0c0D", "7f"]
+
+
+def match_lists_sha256(obj, nstates):
+    """sha256 over the match lists of every (nstates // 2000)-th state, as the test samples them."""
+    h = hashlib.sha256()
+    for s in range(0, nstates, max(1, nstates // 2000)):
+        h.update(json.dumps(obj.match_list(s)).encode() + b"\n")
+    return h.hexdigest()
+
+
+def compiled():
+    import fixtures
+    out = {"generator": "tests/golden/make_golden.py compiled", "source": "reference acsmx.c via oracle/_ref",
+           "hex_to_bytes": {h: orc.RefAcsmx().hex_to_bytes(h).hex() for h in HEX_SAMPLES}, "sets": {}}
+    for name in COMPILED_SETS:
+        o = fixtures.oracle_for(name)
+        r = orc.RefAcsmx()
+        for b, iid in o.patterns():
+            r.add(b, iid)
+        r.compile()
+        table = np.ascontiguousarray(r.table(), dtype=np.int32)
+        rng = np.random.default_rng(5)
+        text = fixtures.text_for({"kind": "clamav", "n": 1 << 16, "seed": 5, "n_plant": 64}, fixtures.patterns_of(name))
+        init = int(rng.integers(0, r.num_states))
+        pos, pat, fs = r.scan(text, init)
+        # all-patterns walk: every pattern of the reference's match list of the state entered at each hit
+        flat = table.reshape(-1, 512)
+        exp_pos, exp_pat, state = [], [], init
+        for k, c in enumerate(text[:1 << 14]):
+            nxt = int(flat[state, c])
+            if nxt < 0:
+                nxt = -nxt
+                for p in r.match_list(nxt):
+                    exp_pos.append(k)
+                    exp_pat.append(p)
+            state = nxt
+        out["sets"][name] = {
+            "states": r.num_states, "max_pattern_len": r.max_pattern_len,
+            "table_sha256": hashlib.sha256(table.tobytes()).hexdigest(),
+            "match_lists_sha256": match_lists_sha256(r, r.num_states),
+            "init_state": init,
+            "scan": {"count": int(pos.size), "records_digest": "%016x" % orc.records_digest(pos, pat), "final_state": int(fs)},
+            "walk": {"count": len(exp_pos), "final_state": state,
+                     "records_digest": "%016x" % orc.records_digest(np.array(exp_pos, dtype=np.uint32),
+                                                                     np.array(exp_pat, dtype=np.int32))},
+        }
+        print("==", name, out["sets"][name]["states"], "states", flush=True)
+    with open(os.path.join(HERE, "compiled_reference.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+    print("wrote compiled_reference.json")
+
+
 if __name__ == "__main__":
-    main()
+    compiled() if sys.argv[1:] == ["compiled"] else main()

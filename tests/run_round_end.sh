@@ -4,20 +4,21 @@
 #   rocprofv3 --kernel-trace --stats (all workers; ONE launch group in flight: --workers 1; sentiment;
 #   ClamAV on the chain pipeline) -> PMC passes -> real-binary table -> acm_grep end to end
 TAG=${1:-r3}
-mkdir -p gpurun_out
+OUT=${OUT:-results}     # where the logs, bench lines and profiles go
+mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 900 python3 -m pytest tests -m gpu -x -q -p no:cacheprovider > gpurun_out/pytest_$TAG.log 2>&1 || { tail -20 gpurun_out/pytest_$TAG.log; exit 1; }
-tail -2 gpurun_out/pytest_$TAG.log
-timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_driver_$TAG.json 2> gpurun_out/bench_driver_$TAG.err || { tail -5 gpurun_out/bench_driver_$TAG.err; exit 1; }
-cut -c1-400 gpurun_out/bench_driver_$TAG.json
-timeout -k 10 500 python3 bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -5 gpurun_out/bench_$TAG.err; exit 1; }
-cut -c1-400 gpurun_out/bench_$TAG.json
+timeout -k 10 900 python3 -m pytest tests -m gpu -x -q -p no:cacheprovider > $OUT/pytest_$TAG.log 2>&1 || { tail -20 $OUT/pytest_$TAG.log; exit 1; }
+tail -2 $OUT/pytest_$TAG.log
+timeout -k 10 500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_$TAG.json 2> $OUT/bench_driver_$TAG.err || { tail -5 $OUT/bench_driver_$TAG.err; exit 1; }
+cut -c1-400 $OUT/bench_driver_$TAG.json
+timeout -k 10 500 python3 bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -5 $OUT/bench_$TAG.err; exit 1; }
+cut -c1-400 $OUT/bench_$TAG.json
 prof() {   # name, bench arguments...
   local name=$1; shift
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${name}_$TAG -- python3 bench.py --no-cpu-baseline --no-e2e --no-extra --sub= "$@" > gpurun_out/bench_prof_${name}_$TAG.json 2> gpurun_out/bench_prof_${name}_$TAG.err || { tail -5 gpurun_out/bench_prof_${name}_$TAG.err; exit 1; }
-  cp $(find gpurun_out/prof_${name}_$TAG -name "*kernel_stats.csv" | head -1) gpurun_out/kernel_stats_${name}_$TAG.csv
-  rm -rf gpurun_out/prof_${name}_$TAG
-  cut -c1-150 gpurun_out/kernel_stats_${name}_$TAG.csv | head -8
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${name}_$TAG -- python3 bench.py --full --no-cpu-baseline --no-e2e --no-extra --sub= "$@" > $OUT/bench_prof_${name}_$TAG.json 2> $OUT/bench_prof_${name}_$TAG.err || { tail -5 $OUT/bench_prof_${name}_$TAG.err; exit 1; }
+  cp $(find $OUT/prof_${name}_$TAG -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_${name}_$TAG.csv
+  rm -rf $OUT/prof_${name}_$TAG
+  cut -c1-150 $OUT/kernel_stats_${name}_$TAG.csv | head -8
 }
 prof headline || exit 1
 prof driver --steps 20 --warmup 5 || exit 1
@@ -29,7 +30,7 @@ prof clamav_chain --mode chain --workers 1 --steps 40 || exit 1
 bash tests/run_pmc.sh pmc_$TAG clamav2000 || exit 1
 bash tests/run_pmc.sh pmcs_$TAG sentiment || exit 1
 bash tests/run_pmc.sh pmcc_$TAG clamav2000 chain || exit 1
-timeout -k 10 300 python3 tools/real_data_probe.py 2000 15000 > gpurun_out/real_data_probe_$TAG.txt 2>&1 || { tail -5 gpurun_out/real_data_probe_$TAG.txt; exit 1; }
-grep sigs gpurun_out/real_data_probe_$TAG.txt
-bash tests/e2e_cli.sh > gpurun_out/e2e_$TAG.txt 2>&1 || exit 1
-cat gpurun_out/e2e_$TAG.txt
+timeout -k 10 300 python3 tools/real_data_probe.py 2000 15000 > $OUT/real_data_probe_$TAG.txt 2>&1 || { tail -5 $OUT/real_data_probe_$TAG.txt; exit 1; }
+grep sigs $OUT/real_data_probe_$TAG.txt
+bash tests/e2e_cli.sh > $OUT/e2e_$TAG.txt 2>&1 || exit 1
+cat $OUT/e2e_$TAG.txt

@@ -94,7 +94,7 @@ def test_bench_collective_path_at_world_size_one(gpu, gather):
     gathered copy."""
     env = dict(os.environ, ACM_BENCH_NCCL1="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "24", "--warmup", "4", "--repeats", "2",
-                        "--texts", "3", "--sub", "", "--no-cpu-baseline", "--no-e2e", "--gather", gather], capture_output=True, text=True,
+                        "--texts", "3", "--sub", "", "--no-cpu-baseline", "--no-e2e", "--gather", gather, "--full"], capture_output=True, text=True,
                        timeout=600, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     rec = json.loads(p.stdout.strip().splitlines()[-1])
@@ -111,7 +111,7 @@ def test_bench_ranks_rehearsal(gpu, ranks, scaling):
     env = dict(os.environ, ACM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(29541 + ranks), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "16", "--warmup", "4",
-           "--repeats", "2", "--texts", "2", "--scaling", scaling]
+           "--repeats", "2", "--texts", "2", "--scaling", scaling, "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]

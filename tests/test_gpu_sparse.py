@@ -12,7 +12,7 @@ import pytest
 import fixtures
 import orc
 import synth
-from gpu_pattern_matching_amd import Automaton, DeviceArray, Matcher
+from gpu_pattern_matching_amd import Automaton, DeviceArray, Matcher, _lib
 
 pytestmark = pytest.mark.gpu
 
@@ -452,18 +452,11 @@ def test_six_byte_keys_text_ends_inside_pattern(gpu):
 
 
 def test_real_binary_content(gpu):
-    """Not synthetic: 48 MiB out of the middle of the largest ROCm library on the box (code, zero
-    pages, tables, strings) x 2000 and 15000 signatures.  Whatever path the data makes the sparse
-    pipeline take, piece by piece, the planes are the oracle's."""
-    import glob
+    """Not synthetic: 48 MiB of a real binary, the project's own libacmatch.so (host and gfx950 code,
+    zero pages, tables, strings) repeated end to end, x 2000 and 15000 signatures.  Whatever path the
+    data makes the sparse pipeline take, piece by piece, the planes are the oracle's."""
     import os
-    libs = sorted(glob.glob("/opt/rocm/lib/*.so*"), key=lambda f: os.path.getsize(f) if os.path.isfile(f) else 0)
-    if not libs or os.path.getsize(libs[-1]) < (64 << 20):
-        pytest.skip("no large library to read")
-    size = os.path.getsize(libs[-1])
-    with open(libs[-1], "rb") as fh:
-        fh.seek((size // 2) & ~4095)
-        data = np.frombuffer(fh.read(48 << 20), dtype=np.uint8)
+    data = np.resize(np.fromfile(_lib.LIB_PATH, dtype=np.uint8), 48 << 20)
     for name in ("clamav2000", "clamav15000"):
         o = fixtures.oracle_for(name)
         path, hx, ml = fixtures.set_source(name)
@@ -484,7 +477,7 @@ def test_real_binary_content(gpu):
                 paths.append(m.path_taken(piece.size))
                 state = exp[2]
         assert set(paths) <= {"sparse", "chain"}
-        print(name, os.path.basename(libs[-1]), paths)
+        print(name, os.path.basename(_lib.LIB_PATH), paths)
         m.close()
 
 

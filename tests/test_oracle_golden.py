@@ -4,7 +4,8 @@
   own table for the reference's own tests/ fixtures),
 * tests/golden/golden.json: digests produced by the reference's acsmx.c
   compiled unmodified (oracle/_ref) on every fixture pattern set,
-* the compiled reference itself, cell for cell, where oracle/_ref is present.
+* the compiled reference itself, cell for cell: as recorded from oracle/_ref in
+  tests/golden/compiled_reference.json, and live where oracle/_ref is present.
 """
 import hashlib
 import json
@@ -31,6 +32,8 @@ ROOT_ROW_TESTS = {"a": 86, "c": 104, "d": 43, "e": 152, "f": 91, "g": 15, "h": 1
 
 with open(os.path.join(os.path.dirname(__file__), "golden", "golden.json")) as _f:
     GOLDEN = json.load(_f)["sets"]
+with open(os.path.join(os.path.dirname(__file__), "golden", "compiled_reference.json")) as _f:
+    COMPILED = json.load(_f)
 
 SMALL_SETS = ["tests", "tests1", "tests2", "tests3", "sentiment", "clamav2000", "clamav2000_m12"]
 BIG_SETS = ["clamav10000", "clamav15000", "clamav15000_m12"]
@@ -104,10 +107,24 @@ def test_oracle_matches_golden(name):
 
 @pytest.mark.parametrize("name", ["tests", "tests1", "tests3", "sentiment", "clamav2000_m12"])
 def test_oracle_equals_compiled_reference(name):
-    """Cell-for-cell against the reference's acsmx.c (only where oracle/_ref exists)."""
-    if orc.rlib() is None:
-        pytest.skip("oracle/_ref not available (needs /root/reference to build)")
+    """Cell-for-cell against the reference's acsmx.c: what it produced (compiled_reference.json,
+    written by make_golden.py from oracle/_ref), and the compiled reference itself where oracle/_ref exists."""
     o = fixtures.oracle_for(name)
+    g = COMPILED["sets"][name]
+    assert o.num_states == g["states"] and o.max_pattern_len == g["max_pattern_len"]
+    assert hashlib.sha256(np.ascontiguousarray(o.table(), dtype=np.int32).tobytes()).hexdigest() == g["table_sha256"]
+    h = hashlib.sha256()
+    for s in range(0, o.num_states, max(1, o.num_states // 2000)):
+        h.update(json.dumps(o.match_list(s)).encode() + b"\n")
+    assert h.hexdigest() == g["match_lists_sha256"]
+    text = fixtures.text_for({"kind": "clamav", "n": 1 << 16, "seed": 5, "n_plant": 64}, fixtures.patterns_of(name))
+    init = int(np.random.default_rng(5).integers(0, o.num_states))
+    assert init == g["init_state"]
+    for (pos, pat, fs), want in ((o.scan(text, init), g["scan"]), (o.scan_all(text[:1 << 14], init), g["walk"])):
+        assert pos.size == want["count"] and fs == want["final_state"]
+        assert "%016x" % orc.records_digest(pos, pat) == want["records_digest"]
+    if orc.rlib() is None:
+        return      # (no oracle/_ref here: the recorded outputs above are the comparison)
     r = orc.RefAcsmx()
     for b, iid in o.patterns():
         r.add(b, iid)
@@ -142,8 +159,14 @@ def test_oracle_equals_compiled_reference(name):
 
 
 def test_reference_hex_decoder_agrees():
+    """The reference's hex decoder, as recorded in compiled_reference.json and live where oracle/_ref exists,
+    decodes as bytes.fromhex (what synth.load_hex_patterns uses)."""
+    recorded = COMPILED["hex_to_bytes"]
+    assert sorted(recorded) == sorted(["00ff10", "deadBEEF", "0a0B0c0D", "7f"])
+    for h, got in recorded.items():
+        assert bytes.fromhex(got) == bytes.fromhex(h)
     if orc.rlib() is None:
-        pytest.skip("oracle/_ref not available")
+        return
     r = orc.RefAcsmx()
     for h in ["00ff10", "deadBEEF", "0a0B0c0D", "7f"]:
         assert r.hex_to_bytes(h) == bytes.fromhex(h)
