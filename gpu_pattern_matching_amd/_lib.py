@@ -54,6 +54,8 @@ NATIVE_API = {
     "acm_automaton_free": (None, [_vp]),
     "acm_automaton_add": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int]),
     "acm_automaton_load_file": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int]),
+    "acm_automaton_set_nocase": (C.c_int, [_vp, C.c_int]),
+    "acm_automaton_nocase": (C.c_int, [_vp]),
     "acm_automaton_compile": (C.c_int, [_vp]),
     "acm_automaton_num_patterns": (C.c_int, [_vp]),
     "acm_automaton_max_pattern_len": (C.c_int, [_vp]),

@@ -72,11 +72,22 @@ class DeviceArray:
 class Automaton:
     """Host automaton: patterns -> acsmx-compatible DFA (acm_automaton_*)."""
 
-    def __init__(self):
+    def __init__(self, nocase=False):
         self.lib = _lib.load()
         self.h = self.lib.acm_automaton_new()
         if not self.h:
             raise MemoryError("acm_automaton_new")
+        if nocase:
+            self.set_nocase(True)
+
+    def set_nocase(self, enable=True):
+        """ASCII case-insensitive matching (acm_automaton_set_nocase); only before compile()."""
+        check(self.lib.acm_automaton_set_nocase(self.h, int(bool(enable))), "acm_automaton_set_nocase")
+        return self
+
+    @property
+    def nocase(self):
+        return bool(self.lib.acm_automaton_nocase(self.h))
 
     def add(self, pattern: bytes, iid: int = 0):
         check(self.lib.acm_automaton_add(self.h, pattern, len(pattern), iid), "acm_automaton_add")

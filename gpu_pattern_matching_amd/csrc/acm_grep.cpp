@@ -53,7 +53,7 @@ double now_us()
 	printf("\nUsage:\n"
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
-	       "             [-w cpu_threads] [-R max] [-tvxFM]\n"
+	       "             [-w cpu_threads] [-R max] [-tvxFMAi]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -73,6 +73,8 @@ double now_us()
 	       "  -M             accepted for compatibility (mapped buffers)\n"
 	       "  -A             report every pattern that ends at an offset, not only the one the\n"
 	       "                 reference reports (extension; off by default)\n"
+	       "  -i             ignore ASCII case in patterns and input (extension; the patterns\n"
+	       "                 are folded after -x decoding and the -m cut, -v prints them as written)\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -112,7 +114,7 @@ std::vector<std::string> regular_files_in(std::string dir)
 
 struct Config {
 	std::string pat_path, data_path;
-	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0;
+	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0;
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
 	long global_ws = -1, local_ws = -1, chunk = -1;
@@ -462,7 +464,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhA")) != -1) {   // ocl_aho_grep.c:411 + A
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAi")) != -1) {   // ocl_aho_grep.c:411 + A, i
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -489,6 +491,7 @@ int main(int argc, char **argv)
 		case 'R': c.max_results = atoi(optarg); break;
 		case 'M': break;
 		case 'A': c.all_patterns = 1; break;
+		case 'i': c.nocase = 1; break;
 		default: usage();
 		}
 	}
@@ -560,6 +563,7 @@ int main(int argc, char **argv)
 
 	// one automaton, one copy per device, shared by the workers of that device
 	acm_automaton *aut = acm_automaton_new();
+	CK(acm_automaton_set_nocase(aut, c.nocase));
 	if (acm_automaton_load_file(aut, c.pat_path.c_str(), c.hex, c.pat_limit) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;

@@ -51,9 +51,15 @@ struct acm_automaton {
 		std::vector<unsigned char> bytes;
 		int iid;
 	};
-	std::vector<Pattern> patterns;
+	std::vector<Pattern> patterns;         // bytes folded by compile when nocase: every table is built from these
 	int max_pattern_len = 0;
 	bool compiled = false;
+	// acm_automaton_set_nocase: patterns and text compared ASCII case-insensitively (case_fold.h).
+	// compile folds the pattern bytes and keeps the originals for acm_automaton_pattern; the column
+	// of every lowercase letter repeats its uppercase letter's (byte classes, dense rows), so a walk
+	// over raw text is case-folded by its table lookups alone.
+	bool nocase = false;
+	std::vector<std::vector<unsigned char>> original;   // [pattern] bytes as added (nocase only)
 
 	uint32_t num_states = 0;               // highest ref id + 1
 	std::vector<uint32_t> parent;          // [ref]

@@ -25,6 +25,7 @@
 #include <unordered_map>
 
 #include "acm_internal.h"
+#include "case_fold.h"
 
 namespace acm {
 
@@ -88,6 +89,18 @@ extern "C" int acm_automaton_add(acm_automaton *a, const unsigned char *bytes, i
 		a->max_pattern_len = n;
 	return ACM_OK;
 }
+
+extern "C" int acm_automaton_set_nocase(acm_automaton *a, int enable)
+{
+	if (!a)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_set_nocase: null automaton");
+	if (a->compiled)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_set_nocase: automaton already compiled");
+	a->nocase = enable != 0;
+	return ACM_OK;
+}
+
+extern "C" int acm_automaton_nocase(const acm_automaton *a) { return (a && a->nocase) ? 1 : 0; }
 
 // ---- pattern file ------------------------------------------------------------
 
@@ -359,6 +372,9 @@ struct Builder {
 			if (used[b])
 				a.class_byte[next++] = (uint8_t)b;
 		}
+		if (a.nocase)   // (no lowercase letter is used: each gets its uppercase letter's class)
+			for (uint32_t b = 'a'; b <= 'z'; b++)
+				a.byte_class[b] = a.byte_class[acm::fold_byte(b)];
 		a.num_classes = classes;
 		a.log_stride = 1;
 		while ((1u << a.log_stride) < classes)
@@ -460,6 +476,14 @@ extern "C" int acm_automaton_compile(acm_automaton *a)
 		return acm::fail(ACM_ERR_LIMIT, "pattern set may need %zu states (limit %u)", total,
 		    acm::kMaxStates);
 	try {
+		if (a->nocase && a->original.empty()) {   // (not again after a failed compile)
+			a->original.resize(a->patterns.size());
+			for (size_t i = 0; i < a->patterns.size(); i++) {
+				a->original[i] = a->patterns[i].bytes;
+				for (unsigned char &c : a->patterns[i].bytes)
+					c = (unsigned char)acm::fold_byte(c);
+			}
+		}
 		Builder b(*a);
 		b.insert_patterns();
 		b.index_children();
@@ -495,6 +519,9 @@ const std::vector<uint64_t> &acm_automaton::dense_rows() const
 			memcpy(row, &dense[(size_t)ref2dev[fail[s]] * 256], 256 * sizeof(uint64_t));
 		for (uint32_t e = child_begin[s]; e < child_begin[s + 1]; e++)
 			row[child_list[e].byte] = cell[child_list[e].to];
+		if (nocase)   // (the raw-byte planes: a lowercase letter's cell is its uppercase letter's)
+			for (uint32_t c = 'a'; c <= 'z'; c++)
+				row[c] = row[acm::fold_byte(c)];
 	}
 	return dense;
 }
@@ -563,8 +590,10 @@ extern "C" int acm_automaton_pattern(const acm_automaton *a, int index, int *iid
 	if (!a || index < 0 || index >= (int)a->patterns.size())
 		return acm::fail(ACM_ERR_ARG, "acm_automaton_pattern: index out of range");
 	if (iid) *iid = a->patterns[index].iid;
-	if (n) *n = (int)a->patterns[index].bytes.size();
-	if (bytes) *bytes = a->patterns[index].bytes.data();
+	const std::vector<unsigned char> &src =
+	    (size_t)index < a->original.size() ? a->original[index] : a->patterns[index].bytes;
+	if (n) *n = (int)src.size();
+	if (bytes) *bytes = src.data();
 	if (next_chained)
 		*next_chained = a->compiled ? a->next_chained[index] : -1;
 	return ACM_OK;

@@ -129,7 +129,7 @@ extern "C" acsm_t *acsm_new(void)
 extern "C" void acsm_add_pattern(acsm_t *a, unsigned char *pat, int n, int nocase, int offset,
     int depth, void *id, int iid)
 {
-	(void)nocase;  // stored but ignored by the reference too (acsmx.c:265-275)
+	(void)nocase;  // stored but ignored by the reference too (acsmx.c:265-275); acm_automaton_set_nocase is the native flag
 	(void)offset;
 	(void)depth;
 	(void)id;

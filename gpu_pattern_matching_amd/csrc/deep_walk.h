@@ -2,11 +2,17 @@
 // pipeline (sparse.hip): exact DFA walking over the deep plane with
 // fast-forward along unary trie paths.  'A' is any kernel-argument struct
 // with members deep, ls, cls, in_byte, text, text16, n_pad.
+//
+// NOCASE (acm_automaton_set_nocase): in_byte holds folded pattern bytes and the
+// plane's lowercase columns repeat the uppercase ones, so the DFA step needs
+// nothing; where text is compared with in_byte, the text side is folded.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "case_fold.h"
 
 namespace acm_dev {
 
@@ -64,18 +70,21 @@ struct __attribute__((packed)) Unaligned16 {
 	uint64_t lo, hi;
 };
 
+// (NOCASE: q is text, folded before the compare; p is pattern bytes, folded already)
+template <bool NOCASE = false>
 __device__ __forceinline__ void diff_bytes16(const uint8_t *p, const uint8_t *q, uint64_t &lo, uint64_t &hi)
 {
 	const Unaligned16 *x = (const Unaligned16 *)p, *y = (const Unaligned16 *)q;
-	lo = x->lo ^ y->lo;
-	hi = x->hi ^ y->hi;
+	lo = x->lo ^ (NOCASE ? acm::fold64(y->lo) : y->lo);
+	hi = x->hi ^ (NOCASE ? acm::fold64(y->hi) : y->hi);
 }
 
 // bytes two 16-byte windows agree on before the first difference (16: all)
+template <bool NOCASE = false>
 __device__ __forceinline__ uint32_t agree16(const uint8_t *p, const uint8_t *q)
 {
 	uint64_t x0, x1;
-	diff_bytes16(p, q, x0, x1);
+	diff_bytes16<NOCASE>(p, q, x0, x1);
 	return x0 ? (uint32_t)(__ffsll((long long)x0) - 1) >> 3
 		  : 8u + (x1 ? (uint32_t)(__ffsll((long long)x1) - 1) >> 3 : 8u);
 }
@@ -90,13 +99,13 @@ __device__ __forceinline__ uint32_t agree16(const uint8_t *p, const uint8_t *q)
 // every percentile of the walk times, not just for short runs.)  Returns the
 // bytes consumed.  Stops at the last full 16 bytes of the padded text: the
 // caller single-steps there.
-template <class A>
+template <bool NOCASE = false, class A>
 __device__ __forceinline__ uint32_t fast_forward(const A &a, Deep &d, uint32_t pos, uint32_t limit)
 {
 	uint32_t total = 0;
 	while (d.run != 0 && total < limit && pos + total + 16 <= a.n_pad) {
 		const uint32_t want = min(min(d.run, limit - total), 16u);
-		const uint32_t same = min(agree16(a.in_byte + d.s + 1, a.text + pos + total), want);
+		const uint32_t same = min(agree16<NOCASE>(a.in_byte + d.s + 1, a.text + pos + total), want);
 		d.s += same;
 		d.depth += same;
 		d.run -= same;

@@ -16,6 +16,7 @@ struct acm_dfa {
 	uint32_t hot_rows = 0;
 	uint32_t hot_depth1 = 1;             // hot ids below this have depth <= 1
 	uint32_t max_pattern_len = 0;
+	bool nocase = false;                 // acm_automaton_set_nocase: the kernels that compare text with pattern bytes, or hash it, fold it (case_fold.h)
 
 	uint32_t log_stride = 8;             // cells per row of the planes below = 1 << log_stride (byte classes; 8: bytes)
 	uint8_t *d_class = nullptr;          // [256] byte -> class (the identity when log_stride == 8)

@@ -37,6 +37,7 @@
 #include <unordered_map>
 
 #include "acm_internal.h"
+#include "case_fold.h"
 #include "device_dfa.h"
 #include "lds_walk.h"
 #include "sieve_tables.h"
@@ -122,6 +123,10 @@ int build_sieve(const acm_automaton &a, acm_dfa *d)
 		if (k == D)
 			d->sv_run_ok[b >> 5] |= 1u << (b & 31);
 	}
+	if (a.nocase)   // (the bulk kernel tests a run of raw bytes: a run of 'a' is one of 'A')
+		for (uint32_t b = 'a'; b <= 'z'; b++)
+			if ((d->sv_run_ok[acm::fold_byte(b) >> 5] >> (acm::fold_byte(b) & 31)) & 1u)
+				d->sv_run_ok[b >> 5] |= 1u << (b & 31);
 
 	// 3-grams at offsets < W of every pattern, with the offsets they occur at
 	std::unordered_map<uint32_t, uint32_t> grams;
@@ -275,6 +280,7 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 	d->hot_rows = a->hot_count;
 	d->hot_depth1 = a->hot_depth1;
 	d->max_pattern_len = (uint32_t)a->max_pattern_len;
+	d->nocase = a->nocase;
 	d->ref2dev = a->ref2dev;
 
 	int rc = ACM_OK;

@@ -26,6 +26,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 
 #include "acm_internal.h"
 #include "compact_tables.h"
@@ -825,10 +826,22 @@ int lds_walk_prepare(const acm_automaton *a, acm_dfa *d)
 	d->lds_ref2code.resize(t.n);
 	for (uint32_t r = 0; r < t.n; r++)
 		d->lds_ref2code[r] = (uint16_t)t.code_of_ref(r);
-	const void *kernels[] = { (const void *)k_lds_walk<kChains, true, 5>, (const void *)k_lds_walk<kChains, true, 6>,
-		(const void *)k_lds_walk<kChains, false, 6> };
-	for (const void *k : kernels)
-		ACM_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.image_bytes));
+	{
+		// The cap belongs to the kernel on the device, not to this automaton: set once per device to what
+		// any image may take, so a smaller automaton uploaded later cannot lower it for a larger one alive.
+		static std::mutex mu;
+		static std::vector<bool> done;
+		std::lock_guard<std::mutex> lock(mu);
+		if ((size_t)d->device >= done.size())
+			done.resize((size_t)d->device + 1, false);
+		if (!done[d->device]) {
+			const void *kernels[] = { (const void *)k_lds_walk<kChains, true, 5>, (const void *)k_lds_walk<kChains, true, 6>,
+				(const void *)k_lds_walk<kChains, false, 6> };
+			for (const void *k : kernels)
+				ACM_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCompactLdsBytes));
+			done[d->device] = true;
+		}
+	}
 	d->lds_ok = true;
 	return ACM_OK;
 }

@@ -42,7 +42,9 @@
 // itself: deep[idx] = state | depth << 32 | run << 48.  depth feeds the merge
 // test; run is the length of the unary trie path ahead, along which states
 // are consecutive ids and the walk only compares text with in_byte[] --
-// 16 bytes per load level instead of one table lookup per byte.
+// 16 bytes per load level instead of one table lookup per byte.  (A nocase
+// automaton: that compare is the one place the text is folded, k_probe /
+// k_resolve<NOCASE = true>; the tables fold everything else.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -501,6 +503,7 @@ __global__ __launch_bounds__(BLOCK) void k_halo_walk(ScanArgs a)
 // assumption (wend), and whether anything in the unmerged head needs an
 // emission walk (a true hit there, or a K1 hit that must be dropped).
 // Chains the walk kernel's epilogue already probed are skipped.
+template <bool NOCASE = false>
 __global__ __launch_bounds__(kBlock2) void k_probe(ScanArgs a)
 {
 	const uint32_t c = blockIdx.x * kBlock2 + threadIdx.x;
@@ -526,7 +529,7 @@ __global__ __launch_bounds__(kBlock2) void k_probe(ScanArgs a)
 			}
 			work |= (d.s >= a.F) | (m >= f);
 			if (d.run != 0 && d.s < a.F) {
-				m += fast_forward(a, d, base + m, len - m);
+				m += fast_forward<NOCASE>(a, d, base + m, len - m);
 				work |= (m >= f);
 			}
 		}
@@ -536,6 +539,7 @@ __global__ __launch_bounds__(kBlock2) void k_probe(ScanArgs a)
 }
 
 // K2b resolve: one lane per chain (see the file header).
+template <bool NOCASE = false>
 __global__ __launch_bounds__(kBlock2) void k_resolve(ScanArgs a)
 {
 	__shared__ uint32_t wave_fill[kBlock2 / 64];
@@ -598,7 +602,7 @@ __global__ __launch_bounds__(kBlock2) void k_resolve(ScanArgs a)
 						continue;
 					}
 					if (d.run != 0 && d.s < a.F)
-						m += fast_forward(a, d, (c << a.logS) + m, a.S - m);
+						m += fast_forward<NOCASE>(a, d, (c << a.logS) + m, a.S - m);
 					state = d.s;
 					if (m == a.S) {
 						c++;
@@ -628,7 +632,7 @@ __global__ __launch_bounds__(kBlock2) void k_resolve(ScanArgs a)
 					if (!killed && m >= f)
 						killed = true;  // a K1 hit sits in the unmerged head: take the chain over
 					if (d.run != 0 && state < a.F) {
-						m += fast_forward(a, d, base + m, len - m);
+						m += fast_forward<NOCASE>(a, d, base + m, len - m);
 						state = d.s;
 						if (!killed && m >= f)
 							killed = true;
@@ -1602,8 +1606,13 @@ int enqueue_batch(const acm_dfa *d, const acm_scan_batch *batch, bool sparse, De
 	}
 	const uint32_t nb = (a.n_chains + kBlock2 - 1) / kBlock2;   // K2 blocks == scatter blocks
 	if (!a.halo_mode) {
-		hipLaunchKernelGGL(k_probe, dim3(nb), dim3(kBlock2), 0, s, a);
-		hipLaunchKernelGGL(k_resolve, dim3(nb), dim3(kBlock2), 0, s, a);
+		if (d->nocase) {
+			hipLaunchKernelGGL(k_probe<true>, dim3(nb), dim3(kBlock2), 0, s, a);
+			hipLaunchKernelGGL(k_resolve<true>, dim3(nb), dim3(kBlock2), 0, s, a);
+		} else {
+			hipLaunchKernelGGL(k_probe<false>, dim3(nb), dim3(kBlock2), 0, s, a);
+			hipLaunchKernelGGL(k_resolve<false>, dim3(nb), dim3(kBlock2), 0, s, a);
+		}
 		ACM_HIP_TRY(hipGetLastError());
 	}
 	if (nb <= kFoldMax) {

@@ -309,13 +309,13 @@ __device__ __forceinline__ void note_hit(LaneHits &h, uint32_t x, uint32_t value
 // bytes the windows of CH * 16 bytes at p and q agree on before the first difference (CH * 16:
 // all).  All the loads are unconditional and in flight together: one latency for the whole window
 // (a load inside a branch gets its own wait: a round trip each instead of one).
-template <int CH>
+template <int CH, bool NOCASE = false>
 __device__ __forceinline__ uint32_t agree(const uint8_t *p, const uint8_t *q)
 {
 	uint64_t lo[CH], hi[CH];
 #pragma unroll
 	for (int k = 0; k < CH; k++)
-		acm_dev::diff_bytes16(p + k * 16, q + k * 16, lo[k], hi[k]);
+		acm_dev::diff_bytes16<NOCASE>(p + k * 16, q + k * 16, lo[k], hi[k]);
 	uint32_t same = CH * 16;
 #pragma unroll
 	for (int k = CH - 1; k >= 0; k--) {   // the earliest difference is written last
@@ -354,6 +354,7 @@ __device__ __forceinline__ void final_node(const SieveArgs &a, LaneHits &h, uint
 	}
 }
 
+template <bool NOCASE = false>
 __device__ __forceinline__ Follow follow(const SieveArgs &a, LaneHits &h, uint32_t node, uint32_t run, uint32_t x, int mode,
     uint32_t floor, RowRef row, uint32_t at)
 {
@@ -373,16 +374,16 @@ __device__ __forceinline__ Follow follow(const SieveArgs &a, LaneHits &h, uint32
 			const uint32_t step = min(run, roomy ? kLongLevel : 64u), want = min(step, a.n - 1 - x);
 			// with the compare, what the node at the end of the stretch needs if the stretch is the
 			// whole run: its record and the byte behind it -- one level instead of two
-			c = a.text[min(x + step + 1, a.n_pad - 1)];
+			c = acm::fold_if<NOCASE>(a.text[min(x + step + 1, a.n_pad - 1)]);
 			rec = a.rec[node + step];
 			uint32_t same;
 			if (roomy) {
-				same = agree<kLongLevel / 16>(a.in_byte + node + 1, a.text + x + 1);
+				same = agree<kLongLevel / 16, NOCASE>(a.in_byte + node + 1, a.text + x + 1);
 			} else if (x + 65 <= a.n_pad) {
-				same = agree<4>(a.in_byte + node + 1, a.text + x + 1);
+				same = agree<4, NOCASE>(a.in_byte + node + 1, a.text + x + 1);
 			} else {
 				same = 0;
-				while (same < want && a.in_byte[node + 1 + same] == a.text[x + 1 + same])
+				while (same < want && a.in_byte[node + 1 + same] == (NOCASE ? (uint8_t)acm::fold_byte(a.text[x + 1 + same]) : a.text[x + 1 + same]))
 					same++;
 			}
 			const uint32_t k = min(same, want);
@@ -396,7 +397,7 @@ __device__ __forceinline__ Follow follow(const SieveArgs &a, LaneHits &h, uint32
 			if (x + 1 >= a.n)
 				break;
 		} else {
-			c = a.text[x + 1];   // both loads before anything looks at either
+			c = acm::fold_if<NOCASE>(a.text[x + 1]);   // both loads before anything looks at either
 			rec = a.rec[node];
 		}
 		__asm__ volatile("" : "+v"(c));   // (keeps the byte's load from sinking into the branch that uses it)
@@ -464,7 +465,7 @@ struct FollowerQueue {
 // together: two dependent steps whatever the number of offsets.  What is a trie path goes
 // to the follower queue, the lanes' followers one behind the other, a lane's own in
 // descending offset = ascending start order.
-template <int W>
+template <int W, bool NOCASE = false>
 __device__ __forceinline__ void stage1_round(const SieveArgs &a, FollowerQueue &fq, uint32_t p, uint32_t gram, bool act,
     uint32_t lane)
 {
@@ -482,6 +483,11 @@ __device__ __forceinline__ void stage1_round(const SieveArgs &a, FollowerQueue &
 		A = p >= 8 ? va : p ? va << (8 * (8 - p)) : 0ull;
 		B = p <= last8 ? vb : p >= a.n_pad ? 0ull : vb >> (8 * (p - last8));
 		C = p + 8 <= last8 ? vc : p + 8 >= a.n_pad ? 0ull : vc >> (8 * (p + 8 - last8));
+		if (NOCASE) {   // (the prefix keys are pattern bytes, folded; the gram came folded from the bulk kernel)
+			A = acm::fold64(A);
+			B = acm::fold64(B);
+			C = acm::fold64(C);
+		}
 		const uint32_t bmask = (1u << a.gram_log_buckets) - 1u;
 		uint32_t b = acm::sieve_gram_bucket(gram, a.gram_log_buckets);
 		for (uint32_t probe = 0; probe < a.gram_probes; probe++, b = (b + 1) & bmask) {
@@ -576,6 +582,7 @@ __device__ __forceinline__ void write_summary(const SieveArgs &a, const Row &t, 
 
 // Stage 2, one follower per lane (ascending starts): follow, shadow across the lanes, append the
 // surviving hits to the row's list.
+template <bool NOCASE = false>
 __device__ __forceinline__ void stage2_round(const SieveArgs &a, Row &t, RowRef row, uint32_t s, uint32_t node,
     uint32_t run, bool act, uint32_t lane, uint32_t &dbg_levels)
 {
@@ -592,7 +599,7 @@ __device__ __forceinline__ void stage2_round(const SieveArgs &a, Row &t, RowRef 
 			h.levels = 0;
 		}
 		if (act && (mode == kKeep || big)) {
-			const Follow f = follow(a, h, node, run, s + a.D - 1, mode, M, RowRef{ 0, 0 }, 0);
+			const Follow f = follow<NOCASE>(a, h, node, run, s + a.D - 1, mode, M, RowRef{ 0, 0 }, 0);
 			E = f.extent1;
 			if (f.at_end) {
 				akey = s + 2;
@@ -661,7 +668,7 @@ __device__ __forceinline__ void stage2_round(const SieveArgs &a, Row &t, RowRef 
 			if (__ballot(big && mine)) {   // third pass: the big lanes write what the shadow leaves them
 				h.n = 0;
 				if (big && mine)
-					(void)follow(a, h, node, run, s + a.D - 1, kWrite, M, row, at);
+					(void)follow<NOCASE>(a, h, node, run, s + a.D - 1, kWrite, M, row, at);
 			}
 			const unsigned long long keepers = __ballot(mine != 0);
 			const uint32_t fp = (uint32_t)__builtin_amdgcn_readlane((int)firstpos, (int)((uint32_t)__ffsll((long long)keepers) - 1u));
@@ -683,6 +690,7 @@ __device__ __forceinline__ void stage2_round(const SieveArgs &a, Row &t, RowRef 
 
 // The carried state (a path that started before byte 0) and the state the last D-1
 // bytes lead to from the root: two short serial walks of the real DFA, one lane.
+template <bool NOCASE = false>
 __device__ void side_walks(const SieveArgs &a)
 {
 	{
@@ -708,7 +716,7 @@ __device__ void side_walks(const SieveArgs &a)
 		}
 		if (run && x + 16 <= a.n_pad) {
 			const uint32_t want = min(min(run, 16u), a.n - x);
-			const uint32_t k = min(agree16(a.in_byte + state + 1, a.text + x), want);
+			const uint32_t k = min(agree16<NOCASE>(a.in_byte + state + 1, a.text + x), want);
 			state += k;   // depth grows with every byte: the start stays where it is
 			x += k;
 			run -= k;
@@ -792,7 +800,10 @@ struct BulkBatch {
 	}
 };
 
-template <int W, bool DBG, int LG>
+// NOCASE: the samples' grams and keys are of the folded text -- folded per sample, here where they are
+// cut from the registers, instead of every loaded word (the run test below needs nothing: run_ok has the
+// lowercase letters of the uppercase ones, device_dfa.hip).
+template <int W, bool DBG, int LG, bool NOCASE = false>
 __global__ __launch_bounds__(kBlock) void k_sieve(SieveGroup g)
 {
 	extern __shared__ __attribute__((aligned(16))) uint32_t bloom[];
@@ -853,7 +864,7 @@ __global__ __launch_bounds__(kBlock) void k_sieve(SieveGroup g)
 		const uint32_t x[5] = { w[j].x, w[j].y, w[j].z, w[j].w, nx[j] };
 		const uint32_t b = k * W, i = b / 4, sh = b % 4;
 		const uint32_t v = sh == 0 ? x[i] : __builtin_amdgcn_alignbyte(x[i + 1 > 4 ? 4 : i + 1], x[i], sh);
-		return v & 0xFFFFFFu;
+		return (NOCASE ? acm::fold32(v) : v) & 0xFFFFFFu;
 	};
 	// the 3 bytes behind the 3-gram (6-byte keys), else 0
 	auto more_of = [&](uint32_t j, uint32_t k) -> uint32_t {
@@ -862,7 +873,7 @@ __global__ __launch_bounds__(kBlock) void k_sieve(SieveGroup g)
 		const uint32_t x[5] = { w[j].x, w[j].y, w[j].z, w[j].w, nx[j] };
 		const uint32_t b = k * W + 3, i = b / 4, sh = b % 4;
 		const uint32_t v = sh == 0 ? x[i > 4 ? 4 : i] : __builtin_amdgcn_alignbyte(x[i + 1 > 4 ? 4 : i + 1], x[i > 4 ? 4 : i], sh);
-		return v & 0xFFFFFFu;
+		return (NOCASE ? acm::fold32(v) : v) & 0xFFFFFFu;
 	};
 	const uint32_t tile_first = blockIdx.x * kWaves + wv;
 	const BulkBatch b0(batch_view(g, 0));   // the first batch's scalars now, with the filter still on its way
@@ -1068,7 +1079,7 @@ __device__ __forceinline__ void load_counts(const SieveArgs &a, uint32_t blk, ui
 // Returns the number of sub-rows the block has beyond its first.  (The counts are loaded in here, not handed in:
 // carried around the caller's loop they cost the kernel thirty registers.)
 // WHOLE: no sub-rows, the block is one row (no helper waves launched: cutting it up would only be bookkeeping).
-template <int W, bool WHOLE, uint32_t TPC>
+template <int W, bool WHOLE, uint32_t TPC, bool NOCASE = false>
 __device__ __forceinline__ uint32_t check_subrow(const SieveArgs &a, uint32_t (*q2)[kQ2Cap], uint32_t lane, uint32_t blk, uint32_t j,
     uint32_t slot, unsigned long long *stamp)
 {
@@ -1100,7 +1111,7 @@ __device__ __forceinline__ uint32_t check_subrow(const SieveArgs &a, uint32_t (*
 		dbg_rounds++;
 		dbg_cands += ns;
 		r0 = ns;
-		stage1_round<W>(a, fq, bc.spec.x, bc.spec.y, lane % kSpecLanes < bc.mycount, lane);
+		stage1_round<W, NOCASE>(a, fq, bc.spec.x, bc.spec.y, lane % kSpecLanes < bc.mycount, lane);
 	}
 	for (;;) {
 		if (fq.count >= 64 || (r0 >= hi && fq.count > 0)) {   // stage 2: a round of followers
@@ -1129,7 +1140,7 @@ __device__ __forceinline__ uint32_t check_subrow(const SieveArgs &a, uint32_t (*
 				__builtin_amdgcn_wave_barrier();
 			}
 			fq.count = left;
-			stage2_round(a, t, row, s0, nd, rn, act, lane, dbg_levels);
+			stage2_round<NOCASE>(a, t, row, s0, nd, rn, act, lane, dbg_levels);
 			continue;
 		}
 		if (r0 >= hi)
@@ -1168,7 +1179,7 @@ __device__ __forceinline__ uint32_t check_subrow(const SieveArgs &a, uint32_t (*
 		dbg_rounds++;
 		dbg_cands += min(hi - r0, 64u);
 		r0 += 64;
-		stage1_round<W>(a, fq, it.x, it.y, act, lane);
+		stage1_round<W, NOCASE>(a, fq, it.x, it.y, act, lane);
 	}
 	if (lane == 0)
 		write_summary(a, t, slot, j == 0 ? extras : row.lbase);
@@ -1196,7 +1207,7 @@ __device__ __forceinline__ uint32_t check_subrow(const SieveArgs &a, uint32_t (*
 // nearly every block in one load level, 36 us for a batch; 16 in a launch group of four or more: half the waves,
 // each with twice the lanes busy in the followers' levels -- the kernel is paced by waves x levels in the shadow
 // of the other streams' bulk kernels: 4.09 -> 4.36 TB/s (40 us for a batch alone; 32 tiles: 4.24 and 53).
-template <int W, bool HELPED, uint32_t TPC>
+template <int W, bool HELPED, uint32_t TPC, bool NOCASE = false>
 __global__ __launch_bounds__(kCheckBlock) void k_sieve_check(SieveGroup g, uint32_t helpers)
 {
 	__shared__ uint32_t q2[3][kQ2Cap];
@@ -1213,14 +1224,14 @@ __global__ __launch_bounds__(kCheckBlock) void k_sieve_check(SieveGroup g, uint3
 	const SieveArgs a = batch_view(g, bi);
 	if (blk == nblocks) {
 		if (threadIdx.x == 0)
-			side_walks(a);
+			side_walks<NOCASE>(a);
 		return;
 	}
 	unsigned long long *stamp = kCheckStamps && a.stamps && blk < nblocks ? a.stamps + (size_t)(blk + 8192) * 8 : nullptr;
 	if (stamp && lane == 0)
 		stamp[0] = __builtin_amdgcn_s_memrealtime();
 	if constexpr (!HELPED) {
-		(void)check_subrow<W, true, TPC>(a, q2, lane, blk, 0, blk + 1, stamp);
+		(void)check_subrow<W, true, TPC, NOCASE>(a, q2, lane, blk, 0, blk + 1, stamp);
 	} else {
 		// The sub-rows behind the first of every block are numbered through the batch in block order and dealt to
 		// the helper waves.  A lane takes eight neighbouring blocks (sixty-four tiles: the text has at most 4096),
@@ -1279,7 +1290,7 @@ __global__ __launch_bounds__(kCheckBlock) void k_sieve_check(SieveGroup g, uint3
 				tj = (uint32_t)__builtin_amdgcn_readlane((int)fk, src);
 				tslot = a.nrows + s0;
 			}
-			(void)check_subrow<W, false, TPC>(a, q2, lane, tb, tj, tslot, own ? stamp : nullptr);
+			(void)check_subrow<W, false, TPC, NOCASE>(a, q2, lane, tb, tj, tslot, own ? stamp : nullptr);
 			if (own)
 				return;
 		}
@@ -1577,7 +1588,9 @@ int sparse_prepare(const acm_dfa *)
 	const void *kernels[] = { (const void *)k_sieve<8, false, 3>, (const void *)k_sieve<4, false, 3>, (const void *)k_sieve<2, false, 3>,
 		(const void *)k_sieve<1, false, 3>, (const void *)k_sieve<8, true, 3>, (const void *)k_sieve<4, true, 3>,
 		(const void *)k_sieve<2, true, 3>, (const void *)k_sieve<1, true, 3>, (const void *)k_sieve<8, false, 6>,
-		(const void *)k_sieve<4, false, 6>, (const void *)k_sieve<8, true, 6>, (const void *)k_sieve<4, true, 6> };
+		(const void *)k_sieve<4, false, 6>, (const void *)k_sieve<8, true, 6>, (const void *)k_sieve<4, true, 6>,
+		(const void *)k_sieve<8, false, 3, true>, (const void *)k_sieve<4, false, 3, true>, (const void *)k_sieve<2, false, 3, true>,
+		(const void *)k_sieve<1, false, 3, true>, (const void *)k_sieve<8, false, 6, true>, (const void *)k_sieve<4, false, 6, true> };
 	for (const void *k : kernels)
 		ACM_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
 	return ACM_OK;
@@ -1722,7 +1735,20 @@ int sparse_group_enqueue(const acm_dfa *d, const SieveJob *jobs, uint32_t count,
 	while (eblocks < 64 && ((size_t)eblocks << 22) < n)   // (a CU issues scattered 4-byte stores one a clock)
 		eblocks *= 2;
 	const bool long_keys = d->sv_gram_len == 6;
-	if (!want_stamps) {
+	if (d->nocase) {   // (no clock stamps: the debugging aid is for the case-sensitive kernels)
+		switch (d->sv_stride) {
+		case 8:
+			if (long_keys) hipLaunchKernelGGL((k_sieve<8, false, 6, true>), dim3(blocks), dim3(kBlock), lds, s, grp);
+			else hipLaunchKernelGGL((k_sieve<8, false, 3, true>), dim3(blocks), dim3(kBlock), lds, s, grp);
+			break;
+		case 4:
+			if (long_keys) hipLaunchKernelGGL((k_sieve<4, false, 6, true>), dim3(blocks), dim3(kBlock), lds, s, grp);
+			else hipLaunchKernelGGL((k_sieve<4, false, 3, true>), dim3(blocks), dim3(kBlock), lds, s, grp);
+			break;
+		case 2: hipLaunchKernelGGL((k_sieve<2, false, 3, true>), dim3(blocks), dim3(kBlock), lds, s, grp); break;
+		default: hipLaunchKernelGGL((k_sieve<1, false, 3, true>), dim3(blocks), dim3(kBlock), lds, s, grp); break;
+		}
+	} else if (!want_stamps) {
 		switch (d->sv_stride) {
 		case 8:
 			if (long_keys) hipLaunchKernelGGL((k_sieve<8, false, 6>), dim3(blocks), dim3(kBlock), lds, s, grp);
@@ -1753,17 +1779,24 @@ int sparse_group_enqueue(const acm_dfa *d, const SieveJob *jobs, uint32_t count,
 		ACM_HIP_TRY(hipEventRecord(after_sieve, s));
 	static const char *skip = getenv("ACM_SIEVE_SKIP");   // experiment (results are void): "c" no check kernel, "e" no emit kernel
 	const bool skip_check = skip && strchr(skip, 'c'), skip_emit = skip && strchr(skip, 'e');
-#define ACM_CHECK(W)                                                                                                                        \
-	if (helpers) hipLaunchKernelGGL((k_sieve_check<W, true, kTilesPerChecker>), dim3(cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers); \
-	else if (tpc == kTilesPerCheckerWide)                                                                                                       \
-		hipLaunchKernelGGL((k_sieve_check<W, false, kTilesPerCheckerWide>), dim3(cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers);     \
-	else hipLaunchKernelGGL((k_sieve_check<W, false, kTilesPerChecker>), dim3(cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers)
-	if (!skip_check)
+#define ACM_CHECK(W, NC)                                                                                                                        \
+	if (helpers) hipLaunchKernelGGL((k_sieve_check<W, true, kTilesPerChecker, NC>), dim3(cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers); \
+	else if (tpc == kTilesPerCheckerWide)                                                                                                           \
+		hipLaunchKernelGGL((k_sieve_check<W, false, kTilesPerCheckerWide, NC>), dim3(cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers);     \
+	else hipLaunchKernelGGL((k_sieve_check<W, false, kTilesPerChecker, NC>), dim3(cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers)
+	if (!skip_check && d->nocase)
 	switch (d->sv_stride) {
-	case 8: ACM_CHECK(8); break;
-	case 4: ACM_CHECK(4); break;
-	case 2: ACM_CHECK(2); break;
-	default: ACM_CHECK(1); break;
+	case 8: ACM_CHECK(8, true); break;
+	case 4: ACM_CHECK(4, true); break;
+	case 2: ACM_CHECK(2, true); break;
+	default: ACM_CHECK(1, true); break;
+	}
+	else if (!skip_check)
+	switch (d->sv_stride) {
+	case 8: ACM_CHECK(8, false); break;
+	case 4: ACM_CHECK(4, false); break;
+	case 2: ACM_CHECK(2, false); break;
+	default: ACM_CHECK(1, false); break;
 	}
 #undef ACM_CHECK
 	if (!skip_emit) {

@@ -75,6 +75,21 @@ int acm_automaton_add(acm_automaton *, const unsigned char *bytes, int n,
 int acm_automaton_load_file(acm_automaton *, const char *path, int hex,
     int max_len);
 
+/* ASCII case-insensitive matching for every pattern of the automaton.  With
+ * it on, fold(b) = b - 0x20 for 'a' <= b <= 'z' and b otherwise (toupper in
+ * the C locale; bytes >= 0x80 are never folded), and a scan of text T gives
+ * bit for bit what the automaton of the folded patterns gives on fold(T):
+ * same records, planes, states and overflow, pattern indices and iids those
+ * of the patterns as added.  acm_automaton_pattern still returns the bytes as
+ * added.  Off by default.  Only before acm_automaton_compile: afterwards it
+ * fails with ACM_ERR_ARG.  Not provided: case sensitivity per pattern within
+ * one automaton, and any folding beyond ASCII letters.  The reference-named
+ * layer (acsm_add_pattern's nocase argument) keeps ignoring the flag as the
+ * reference does. */
+int acm_automaton_set_nocase(acm_automaton *, int enable);
+/* 1 if the automaton matches case-insensitively, else 0 */
+int acm_automaton_nocase(const acm_automaton *);
+
 /* trie -> fail links -> full DFA, reference state numbering preserved
  * (acsmx.c:552-594) and a BFS renumbering derived for the device. */
 int acm_automaton_compile(acm_automaton *);
