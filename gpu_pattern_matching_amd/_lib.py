@@ -67,6 +67,8 @@ NATIVE_API = {
     "acm_automaton_export_reference_table": (C.c_int, [_vp, _i32p]),
     "acm_automaton_pattern": (C.c_int, [_vp, C.c_int, _i32p, _i32p, C.POINTER(_vp), _i32p]),
     "acm_automaton_state_output": (C.c_int, [_vp, C.c_int]),
+    "acm_automaton_state_fail": (C.c_int, [_vp, C.c_int]),
+    "acm_automaton_state_depth": (C.c_int, [_vp, C.c_int]),
     "acm_dfa_upload": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
     "acm_dfa_release": (None, [_vp]),
     "acm_dfa_device_bytes": (C.c_size_t, [_vp]),
@@ -85,6 +87,9 @@ NATIVE_API = {
     "acm_scan_kernel_count": (C.c_int, []),
     "acm_expand_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "acm_expand_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "acm_segment_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "acm_segment_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_long, C.c_int, _vp, _vp,
+                                            _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
     "acm_scan_set_mode": (C.c_int, [_vp, C.c_int]),
     "acm_scan_set_graphs": (C.c_int, [_vp, C.c_int]),
     "acm_scan_sparse_eligible": (C.c_int, [_vp]),

@@ -145,6 +145,20 @@ class Automaton:
     def state_output(self, ref_state):
         return self.lib.acm_automaton_state_output(self.h, ref_state)
 
+    def state_fail(self, ref_state):
+        """fail link of a reference state (acm_automaton_state_fail)"""
+        r = self.lib.acm_automaton_state_fail(self.h, ref_state)
+        if r < 0:
+            check(r, "acm_automaton_state_fail")
+        return r
+
+    def state_depth(self, ref_state):
+        """trie depth of a reference state (acm_automaton_state_depth); 0 for the root"""
+        r = self.lib.acm_automaton_state_depth(self.h, ref_state)
+        if r < 0:
+            check(r, "acm_automaton_state_depth")
+        return r
+
     def close(self):
         if self.h:
             self.lib.acm_automaton_free(self.h)
@@ -327,6 +341,101 @@ class Matcher:
             return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1])
         finally:
             for b in (d, ws, pat, off):
+                b.free()
+
+    def segment_async(self, state_plane, off_plane, max_records, seg_start, segments, text_end, pat_out, off_out,
+                      out_capacity, seg_out=None, seg_counts=None, report=0, workspace=None, stream=None):
+        """Enqueue the segment pass (acm_segment_matches_async) over caller-owned device planes: the
+        records of a REPORT_STATE scan, each clamped to its own segment.  seg_start: device int32
+        [segments] (None when segments == 0).  workspace: (ptr, nbytes), or None for a temporary one
+        that lives until the stream has passed it (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        tmp = None
+        if workspace is None:
+            nb = self.lib.acm_segment_workspace_bytes(max_records)
+            tmp = DeviceArray(max(nb, 16))
+            workspace = (tmp.ptr, nb)
+        try:
+            check(self.lib.acm_segment_matches_async(
+                self.dfa, _ptr(state_plane), _ptr(off_plane), max_records, _ptr(seg_start), segments, text_end,
+                report, _ptr(pat_out), _ptr(off_out), _ptr(seg_out), out_capacity, _ptr(seg_counts),
+                _ptr(workspace[0]), workspace[1], st), "acm_segment_matches_async")
+        finally:
+            if tmp is not None:
+                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
+                tmp.free()
+
+    @staticmethod
+    def pack_segments(texts):
+        """(uint8 text, int32 starts) of a list of bytes-like texts, or of a (text, starts) pair."""
+        if isinstance(texts, tuple):
+            t, starts = texts
+            return np.ascontiguousarray(t, dtype=np.uint8), np.ascontiguousarray(starts, dtype=np.int32)
+        parts = [np.frombuffer(bytes(x), dtype=np.uint8) for x in texts]
+        sizes = np.array([p.size for p in parts], dtype=np.int64)
+        starts = np.zeros(len(parts), dtype=np.int64)
+        if len(parts) > 1:
+            starts[1:] = np.cumsum(sizes)[:-1]
+        t = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        return t, starts.astype(np.int32)
+
+    def scan_segments(self, texts, init_state=0, all_patterns=False, counts=False, out_capacity=None):
+        """Scan many independent texts in one batch: each text is matched as if scanned alone from the
+        root (acm_segment_matches_async behind an ordinary scan).  texts: a list of bytes-like objects,
+        or a (uint8 array, int32 starts) pair.  Returns (offsets, patterns, segment_ids, last_state),
+        offsets in the coordinates of the concatenation; with counts=True also the records per text.
+        Records before the first start continue a text that init_state was in (segment -1).
+        all_patterns: every pattern of each record's clamped state (acm_expand_matches_async)."""
+        t, starts = self.pack_segments(texts)
+        self.reserve(max(t.size, 1))
+        d = DeviceArray.from_numpy(t, stream=self.stream)
+        nseg = int(starts.size)
+        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
+        max_records = self.plane_capacity - 2
+        cap = self.plane_capacity
+        seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
+        bufs = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4), DeviceArray(cap * 4),
+                DeviceArray(max(nseg, 1) * 4)]
+        ws, pat, off, seg, cnt = bufs
+        bufs += [d] + ([d_st] if d_st is not None else [])
+        try:
+            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
+            self.segment_async(self.pat_plane, self.off_plane, max_records, d_st, nseg, t.size, pat, off, cap,
+                               seg_out=seg, seg_counts=cnt if nseg else None,
+                               report=_lib.REPORT_STATE if all_patterns else _lib.REPORT_HEAD,
+                               workspace=(ws.ptr, seg_ws))
+            m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
+            if m > cap - 2:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_segments", "%d records but planes hold %d"
+                               % (m, cap - 2))
+            if not all_patterns:
+                p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
+                o = off.to_numpy(np.int32, m + 2, stream=self.stream)
+                sg = seg.to_numpy(np.int32, m + 2, stream=self.stream)
+                res = (o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), sg[1:1 + m].copy(), int(p[m + 1]))
+                if counts:
+                    res += (cnt.to_numpy(np.int32, nseg, stream=self.stream),)
+                return res
+            acap = out_capacity if out_capacity is not None else 8 * cap
+            ex_ws = self.lib.acm_expand_workspace_bytes(max(m, 1))
+            xb = [DeviceArray(ex_ws), DeviceArray(acap * 4), DeviceArray(acap * 4)]
+            bufs += xb
+            check(self.lib.acm_expand_matches_async(self.dfa, pat.ptr, off.ptr, max(m, 1), xb[1].ptr, xb[2].ptr,
+                                                    acap, xb[0].ptr, ex_ws, self.stream), "acm_expand_matches_async")
+            n = int(xb[1].to_numpy(np.int32, 1, stream=self.stream)[0])
+            if n > acap - 2:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_segments", "%d records but planes hold %d"
+                               % (n, acap - 2))
+            p = xb[1].to_numpy(np.int32, n + 2, stream=self.stream)
+            o = xb[2].to_numpy(np.int32, n + 2, stream=self.stream)
+            offs = o[1:1 + n].astype(np.uint32)
+            sg = (np.searchsorted(starts, offs.astype(np.int64), side="right") - 1).astype(np.int32)
+            res = (offs, p[1:1 + n].copy(), sg, int(p[n + 1]))
+            if counts:
+                res += (np.bincount(sg[sg >= 0], minlength=nseg).astype(np.int32)[:nseg],)
+            return res
+        finally:
+            for b in bufs:
                 b.free()
 
     def scan(self, text, init_state=0):

@@ -53,7 +53,7 @@ double now_us()
 	printf("\nUsage:\n"
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
-	       "             [-w cpu_threads] [-R max] [-tvxFMAi]\n"
+	       "             [-w cpu_threads] [-R max] [-tvxFMAiS]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -75,6 +75,9 @@ double now_us()
 	       "                 reference reports (extension; off by default)\n"
 	       "  -i             ignore ASCII case in patterns and input (extension; the patterns\n"
 	       "                 are folded after -x decoding and the -m cut, -v prints them as written)\n"
+	       "  -S             every input unit is its own text: a file, or with -t a line; no match\n"
+	       "                 spans two of them (extension; data appended under -F continues its file\n"
+	       "                 when the worker's previous chunk came from the same file)\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -114,7 +117,7 @@ std::vector<std::string> regular_files_in(std::string dir)
 
 struct Config {
 	std::string pat_path, data_path;
-	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0;
+	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0;
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
 	long global_ws = -1, local_ws = -1, chunk = -1;
@@ -144,6 +147,10 @@ struct Buffer {   // one of the two staging buffers of a worker
 	size_t all_cap = 0;          // cells of the -A planes
 	int32_t *h_all_count = nullptr;   // pinned: records the expansion produced
 	size_t expand_ws_bytes = 0;
+	void *d_seg_pat = nullptr, *d_seg_off = nullptr, *d_seg_start = nullptr, *d_seg_ws = nullptr;   // -S only
+	size_t seg_ws_bytes = 0;
+	std::vector<int32_t> seg_starts;   // -S: stream offsets where a file (-t: a line) begins
+	const int32_t *end_plane = nullptr;   // plane whose trailer holds the state the next buffer starts in
 	void *d_packed = nullptr;
 	size_t chunks = 0, bytes = 0;
 	std::vector<int32_t> starts;
@@ -161,6 +168,8 @@ struct Worker {
 	size_t ws_bytes = 0;
 	Buffer buf[2];
 	long last_state = 0;
+	int seg_file = -1;        // -S: file of the last chunk submitted
+	bool seg_open = false;    // -S -t: that chunk ended inside a line
 	size_t matches = 0, reported = 0, bytes = 0, lines = 0, rounds = 0;
 };
 
@@ -191,6 +200,13 @@ void buffer_alloc(Buffer &b, const Config &c)
 	CK(acm_rt_malloc(&b.d_results2, plane));
 	CK(acm_rt_malloc(&b.d_pat, (size + 2) * 4));
 	CK(acm_rt_malloc(&b.d_off, (size + 2) * 4));
+	if (c.segmented) {
+		b.seg_ws_bytes = acm_segment_workspace_bytes(size);
+		CK(acm_rt_malloc(&b.d_seg_pat, (size + 2) * 4));
+		CK(acm_rt_malloc(&b.d_seg_off, (size + 2) * 4));
+		CK(acm_rt_malloc(&b.d_seg_start, (G + 1) * 4));
+		CK(acm_rt_malloc(&b.d_seg_ws, b.seg_ws_bytes));
+	}
 	if (c.all_patterns) {
 		b.expand_ws_bytes = acm_expand_workspace_bytes(size);
 		// every pattern of every final state's list: more records than text bytes when patterns nest
@@ -294,7 +310,7 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 	sb.init_state = w.last_state;
 	if (prev) {
 		sb.init_state = 0;
-		sb.d_init_plane = (const int32_t *)prev->d_pat;
+		sb.d_init_plane = prev->end_plane;
 		sb.init_plane_capacity = prev->scan_cap;
 	}
 	sb.d_workspace = w.ws;
@@ -304,11 +320,36 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 	sb.plane_capacity = cap;
 	sb.stream = s;
 	b.scan_cap = cap;
-	if (!c.all_patterns) {
-		CK(acm_scan_batch_async(w.dfa, &sb));
-	} else {   // final states instead of head patterns, then every pattern of each state's match list
+	b.end_plane = pat;
+	if (c.segmented) {
+		// a text begins at every chunk of another file than the chunk before it (-t: and at every chunk
+		// that follows a finished line); a long line split over chunks, or a file over buffers, goes on
+		b.seg_starts.clear();
+		for (int i = 0; i < chunks; i++) {
+			if (b.file_ids[i] != w.seg_file || (c.text_mode && !w.seg_open))
+				b.seg_starts.push_back(b.starts[i]);
+			w.seg_file = b.file_ids[i];
+			w.seg_open = b.h_sizes[i] > 0 && b.h_data[b.h_indices[i] + b.h_sizes[i] - 1] != '\n';
+		}
+		if (!b.seg_starts.empty())
+			CK(acm_rt_memcpy_h2d(b.d_seg_start, b.seg_starts.data(), b.seg_starts.size() * 4, s));
+		// the scan reports final states, the segment pass clamps every one to its own text
 		sb.report = ACM_REPORT_STATE;
 		CK(acm_scan_batch_async(w.dfa, &sb));
+		CK(acm_segment_matches_async(w.dfa, pat, off, cap - 2, (const int32_t *)b.d_seg_start, b.seg_starts.size(),
+		    (long)stream_len, c.all_patterns ? ACM_REPORT_STATE : ACM_REPORT_HEAD, (int32_t *)b.d_seg_pat,
+		    (int32_t *)b.d_seg_off, nullptr, cap, nullptr, b.d_seg_ws, b.seg_ws_bytes, s));
+		pat = (int32_t *)b.d_seg_pat;
+		off = (int32_t *)b.d_seg_off;
+		b.end_plane = pat;   // its trailer is the clamped state: the next buffer goes on from there
+	}
+	if (!c.all_patterns) {
+		if (!c.segmented)
+			CK(acm_scan_batch_async(w.dfa, &sb));
+	} else {   // final states instead of head patterns, then every pattern of each state's match list
+		sb.report = ACM_REPORT_STATE;
+		if (!c.segmented)
+			CK(acm_scan_batch_async(w.dfa, &sb));
 		CK(acm_expand_matches_async(w.dfa, pat, off, cap - 2, (int32_t *)b.d_pat_all, (int32_t *)b.d_off_all,
 		    b.all_cap, b.d_expand_ws, b.expand_ws_bytes, s));
 		pat = (int32_t *)b.d_pat_all;
@@ -464,7 +505,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAi")) != -1) {   // ocl_aho_grep.c:411 + A, i
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiS")) != -1) {   // ocl_aho_grep.c:411 + A, i, S
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -492,6 +533,7 @@ int main(int argc, char **argv)
 		case 'M': break;
 		case 'A': c.all_patterns = 1; break;
 		case 'i': c.nocase = 1; break;
+		case 'S': c.segmented = 1; break;
 		default: usage();
 		}
 	}

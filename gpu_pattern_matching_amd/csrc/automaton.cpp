@@ -617,3 +617,17 @@ extern "C" int acm_automaton_state_output(const acm_automaton *a, int ref_state)
 		return -1;
 	return a->head_of((uint32_t)ref_state);
 }
+
+extern "C" int acm_automaton_state_fail(const acm_automaton *a, int ref_state)
+{
+	if (!a || !a->compiled || ref_state < 0 || (uint32_t)ref_state >= a->num_states)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_state_fail: automaton not compiled or state out of range");
+	return (int)a->fail[ref_state];
+}
+
+extern "C" int acm_automaton_state_depth(const acm_automaton *a, int ref_state)
+{
+	if (!a || !a->compiled || ref_state < 0 || (uint32_t)ref_state >= a->num_states)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_state_depth: automaton not compiled or state out of range");
+	return (int)a->depth[ref_state];
+}

@@ -45,6 +45,7 @@ struct acm_dfa {
 	uint32_t *d_list_begin = nullptr;    // [states, reference numbering] offset of the state's match list in d_list_pool
 	uint32_t *d_list_len = nullptr;      // [states] its length (0: not final)
 	int32_t *d_list_pool = nullptr;      // pattern indices, list order
+	uint32_t *d_fail_depth = nullptr;    // [states, reference numbering][2] {fail link, trie depth}: segmented scans (segment.hip)
 	size_t device_bytes = 0;
 	void *arena = nullptr;               // one allocation for the small tables (device_dfa.hip, upload_small)
 	size_t arena_bytes = 0, arena_used = 0;

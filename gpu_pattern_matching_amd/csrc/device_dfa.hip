@@ -285,7 +285,8 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 
 	int rc = ACM_OK;
 	{
-		const size_t want = (((size_t)a->num_states * 48 + (8u << 20)) + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1);
+		// 48 B per state for the tables below, 8 more for the segment pass's {fail, depth} records
+		const size_t want = (((size_t)a->num_states * 56 + (8u << 20)) + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1);
 		if (hipMalloc(&d->arena, want) == hipSuccess) {
 			d->arena_bytes = want;
 			d->device_bytes += want;
@@ -358,6 +359,14 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 		if (rc == ACM_OK) rc = upload(&d->d_list_begin, lbegin.data(), lbegin.size(), &d->device_bytes);
 		if (rc == ACM_OK) rc = upload(&d->d_list_len, llen.data(), llen.size(), &d->device_bytes);
 		if (rc == ACM_OK) rc = upload(&d->d_list_pool, a->list_pool.data(), a->list_pool.size(), &d->device_bytes);
+		// fail link and trie depth of every state, reference numbering: the segment pass clamps a state to
+		// the longest suffix that lies inside its segment by walking fail links (segment.hip)
+		std::vector<uint32_t> fd((size_t)n * 2);
+		for (uint32_t r = 0; r < n; r++) {
+			fd[2 * (size_t)r] = a->fail[r];
+			fd[2 * (size_t)r + 1] = a->depth[r];
+		}
+		if (rc == ACM_OK) rc = upload_small(d, &d->d_fail_depth, fd.data(), fd.size());
 	} catch (const std::bad_alloc &) {
 		rc = acm::fail(ACM_ERR_NOMEM, "acm_dfa_upload: out of host memory");
 	}
@@ -411,6 +420,7 @@ extern "C" void acm_dfa_release(acm_dfa *d)
 		hipFree(d->d_list_begin);
 		hipFree(d->d_list_len);
 		hipFree(d->d_list_pool);
+		free_small(d, d->d_fail_depth);
 		free_small(d, d->d_depth);
 		free_small(d, d->d_class);
 		free_small(d, d->d_sv_bloom);

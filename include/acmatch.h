@@ -125,6 +125,11 @@ int acm_automaton_export_reference_table(const acm_automaton *, int32_t *dst);
  * pattern chained to it by acsm_get_patterns_table (acsmx.c:707-721) or -1 */
 int acm_automaton_pattern(const acm_automaton *, int index, int *iid, int *n,
     const unsigned char **bytes, int *next_chained);
+/* fail link and trie depth of reference state s (depth(root) = 0, depth(fail(s)) < depth(s) for
+ * every other state): what the segment pass (acm_segment_matches_async) walks.  ACM_ERR_ARG for an
+ * uncompiled automaton or a state out of range.  For host tests and FFI users. */
+int acm_automaton_state_fail(const acm_automaton *, int ref_state);
+int acm_automaton_state_depth(const acm_automaton *, int ref_state);
 /* head-of-match-list pattern index of reference state s, or -1 */
 int acm_automaton_state_output(const acm_automaton *, int ref_state);
 /* every pattern that ends where the walk enters ref_state, in the order of the
@@ -256,6 +261,37 @@ size_t acm_expand_workspace_bytes(size_t max_records);
 int acm_expand_matches_async(const acm_dfa *, const int32_t *d_state_plane,
     const int32_t *d_off_plane, size_t max_records, int32_t *d_pat_out,
     int32_t *d_off_out, size_t out_capacity, void *d_workspace,
+    size_t workspace_bytes, void *stream);
+
+/* Segmented scans: many independent texts in one scan, each matched as if scanned alone from the
+ * root.  Input: the planes of a scan enqueued with report = ACM_REPORT_STATE (at most max_records
+ * records are looked at, as in acm_expand_matches_async), and the start offsets of the texts,
+ * d_seg_start[segments]: non-decreasing, in the coordinates of the reported offsets (offset_shift of a
+ * shard or halo scan included); empty segments (equal starts) and starts at or beyond text_end are
+ * allowed.  A record at offset o belongs to the last segment k with start[k] <= o; its state is
+ * clamped to the first state on its fail chain whose depth is <= o - start[k] + 1 (the state a walk
+ * restarted at start[k] would be in), and the record is kept iff that state's match list is not empty.
+ * A record before start[0] continues a text that began before this scan: it is not clamped and its
+ * segment is -1.  segments == 0: nothing is clamped (the output is the input in the report form asked).
+ * Output, the scan's cell layout and overflow contract ([0] = full count of kept records, records in
+ * position order, trailer at min(count + 1, out_capacity - 1)):
+ *   d_pat_out   report = ACM_REPORT_HEAD: the head of the clamped state's match list (what the scan
+ *               reports); ACM_REPORT_STATE: the clamped state (for acm_expand_matches_async)
+ *   d_off_out   the offset, unchanged
+ *   d_seg_out   (NULL: not wanted) the segment k, or -1
+ *   trailer     the input trailer clamped with b = text_end - start[k], k the last segment with
+ *               start[k] <= text_end (b = 0: the root): the state the next buffer starts in, so the
+ *               output planes can be handed to the next scan as acm_scan_batch.d_init_plane with
+ *               init_plane_capacity = out_capacity
+ *   d_seg_counts (NULL: not wanted) int32[segments], written whole: records kept per segment
+ * The output planes must not overlap the input planes.  Stream-ordered, no host sync, no allocation;
+ * argument errors return ACM_ERR_ARG before anything is enqueued.  The scan kernels are not involved:
+ * it is a pass over the records (cost per record, not per text byte). */
+size_t acm_segment_workspace_bytes(size_t max_records);
+int acm_segment_matches_async(const acm_dfa *, const int32_t *d_state_plane,
+    const int32_t *d_off_plane, size_t max_records, const int32_t *d_seg_start,
+    size_t segments, long text_end, int report, int32_t *d_pat_out, int32_t *d_off_out,
+    int32_t *d_seg_out, size_t out_capacity, int32_t *d_seg_counts, void *d_workspace,
     size_t workspace_bytes, void *stream);
 
 int acm_scan_batch_async(const acm_dfa *, const acm_scan_batch *);
