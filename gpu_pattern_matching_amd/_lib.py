@@ -90,6 +90,9 @@ NATIVE_API = {
     "acm_segment_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "acm_segment_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_long, C.c_int, _vp, _vp,
                                             _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "acm_word_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "acm_word_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_long, C.c_long, _vp, C.c_size_t, C.c_int,
+                                         _vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
     "acm_scan_set_mode": (C.c_int, [_vp, C.c_int]),
     "acm_scan_set_graphs": (C.c_int, [_vp, C.c_int]),
     "acm_scan_sparse_eligible": (C.c_int, [_vp]),

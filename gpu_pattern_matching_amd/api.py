@@ -438,6 +438,98 @@ class Matcher:
             for b in bufs:
                 b.free()
 
+    @staticmethod
+    def word_mask(word_set):
+        """32-byte mask (bit b of byte b // 8: byte b is a word byte) of an iterable of byte values or a
+        bytes-like object listing the word bytes; None stays None (the default set [0-9A-Za-z_])."""
+        if word_set is None:
+            return None
+        m = np.zeros(256, dtype=np.uint8)
+        vals = np.frombuffer(bytes(word_set), dtype=np.uint8) if isinstance(word_set, (bytes, bytearray, memoryview)) \
+            else np.asarray(list(word_set), dtype=np.int64)
+        if vals.size:
+            m[vals] = 1
+        return np.packbits(m, bitorder="little").tobytes()
+
+    def word_async(self, state_plane, off_plane, max_records, d_text, text_origin, text_end, pat_out, off_out,
+                   out_capacity, before=None, before_len=0, next_byte=-1, seg_start=None, segments=0,
+                   word_mask=None, all_patterns=False, tail_out=None, workspace=None, stream=None):
+        """Enqueue the word pass (acm_word_matches_async) over caller-owned device planes: the records of
+        a REPORT_STATE scan (or of the segment pass in STATE form) kept where a pattern is a whole word.
+        word_mask: 32 bytes (Matcher.word_mask) or None for [0-9A-Za-z_].  workspace: (ptr, nbytes), or
+        None for a temporary one that lives until the stream has passed it (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        tmp = None
+        if workspace is None:
+            nb = self.lib.acm_word_workspace_bytes(max_records)
+            tmp = DeviceArray(max(nb, 16))
+            workspace = (tmp.ptr, nb)
+        mask = None
+        if word_mask is not None:
+            if len(word_mask) != 32:
+                raise ValueError("word_mask must be 32 bytes")
+            mask = C.create_string_buffer(bytes(word_mask), 32)
+        try:
+            check(self.lib.acm_word_matches_async(
+                self.dfa, _ptr(state_plane), _ptr(off_plane), max_records, _ptr(d_text), text_origin, text_end,
+                _ptr(before), before_len, next_byte, _ptr(seg_start), segments, mask, 1 if all_patterns else 0,
+                _ptr(pat_out), _ptr(off_out), out_capacity, _ptr(tail_out), _ptr(workspace[0]), workspace[1], st),
+                "acm_word_matches_async")
+        finally:
+            if tmp is not None:
+                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
+                tmp.free()
+
+    def scan_words(self, text, all_patterns=False, word_set=None, segments=None, init_state=0, before=b"",
+                   next_byte=-1, out_capacity=None):
+        """Whole-word matching (grep -w): scan host bytes and keep a pattern only where the bytes around
+        it are not word bytes (acm_word_matches_async behind a REPORT_STATE scan).  word_set: the word
+        bytes (bytes-like or iterable of ints), None for [0-9A-Za-z_].  segments: int32 text starts;
+        the records then go through the segment pass first.  before: the bytes in front of text (a
+        stream's previous piece; further back is a text start); next_byte: the byte after text, or -1.
+        all_patterns: every word-bounded pattern, else the first in list order.  Returns
+        (offsets, patterns, last_state)."""
+        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
+            else np.ascontiguousarray(text, dtype=np.uint8)
+        bf = np.frombuffer(bytes(before), dtype=np.uint8)
+        self.reserve(max(t.size, 1))
+        d = DeviceArray.from_numpy(t, stream=self.stream)
+        d_bf = DeviceArray.from_numpy(bf, stream=self.stream) if bf.size else None
+        starts = np.ascontiguousarray(segments if segments is not None else [], dtype=np.int32)
+        nseg = int(starts.size)
+        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
+        max_records = self.plane_capacity - 2
+        cap = self.plane_capacity
+        ocap = out_capacity if out_capacity is not None else (8 * cap if all_patterns else cap)
+        ws_bytes = self.lib.acm_word_workspace_bytes(max_records)
+        bufs = [DeviceArray(max(ws_bytes, 16)), DeviceArray(ocap * 4), DeviceArray(ocap * 4)]
+        ws, pat, off = bufs
+        bufs += [b for b in (d, d_bf, d_st) if b is not None]
+        try:
+            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
+            sp, so = self.pat_plane, self.off_plane
+            if nseg:
+                sb = [DeviceArray(max(self.lib.acm_segment_workspace_bytes(max_records), 16)),
+                      DeviceArray(cap * 4), DeviceArray(cap * 4)]
+                bufs += sb
+                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
+                                   report=_lib.REPORT_STATE,
+                                   workspace=(sb[0].ptr, self.lib.acm_segment_workspace_bytes(max_records)))
+                sp, so = sb[1], sb[2]
+            self.word_async(sp, so, max_records, d, 0, t.size, pat, off, ocap, before=d_bf, before_len=int(bf.size),
+                            next_byte=next_byte, seg_start=d_st, segments=nseg, word_mask=self.word_mask(word_set),
+                            all_patterns=all_patterns, workspace=(ws.ptr, ws_bytes))
+            m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
+            if m > ocap - 2:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_words", "%d records but planes hold %d"
+                               % (m, ocap - 2))
+            p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
+            o = off.to_numpy(np.int32, m + 2, stream=self.stream)
+            return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1])
+        finally:
+            for b in bufs:
+                b.free()
+
     def scan(self, text, init_state=0):
         """Scan host bytes: upload, scan, download."""
         t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \

@@ -53,7 +53,7 @@ double now_us()
 	printf("\nUsage:\n"
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
-	       "             [-w cpu_threads] [-R max] [-tvxFMAiS]\n"
+	       "             [-w cpu_threads] [-R max] [-tvxFMAiSW]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -78,6 +78,9 @@ double now_us()
 	       "  -S             every input unit is its own text: a file, or with -t a line; no match\n"
 	       "                 spans two of them (extension; data appended under -F continues its file\n"
 	       "                 when the worker's previous chunk came from the same file)\n"
+	       "  -W             whole words only (grep -w): a pattern counts where the bytes around it\n"
+	       "                 are not in [0-9A-Za-z_] or are a text start or end; with -A every such\n"
+	       "                 pattern, else the first of the match list (extension; not with -F)\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -117,7 +120,8 @@ std::vector<std::string> regular_files_in(std::string dir)
 
 struct Config {
 	std::string pat_path, data_path;
-	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0;
+	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0,
+	    words = 0;
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
 	long global_ws = -1, local_ws = -1, chunk = -1;
@@ -130,6 +134,7 @@ struct Shared {
 	std::vector<int> fds;
 	std::vector<std::string> pat_bytes;   // for the -v line
 	std::vector<int> pat_iid;
+	int max_pattern_len = 0;
 	pthread_mutex_t print_lock = PTHREAD_MUTEX_INITIALIZER;
 	pthread_barrier_t ready;   // workers have their buffers; the clock starts (the reference
 	                           // also allocates in ocl_worker_ctx_init, before start_time)
@@ -151,6 +156,12 @@ struct Buffer {   // one of the two staging buffers of a worker
 	size_t seg_ws_bytes = 0;
 	std::vector<int32_t> seg_starts;   // -S: stream offsets where a file (-t: a line) begins
 	const int32_t *end_plane = nullptr;   // plane whose trailer holds the state the next buffer starts in
+	void *d_word_pat = nullptr, *d_word_off = nullptr, *d_word_ws = nullptr;   // -W only
+	size_t word_ws_bytes = 0;
+	const void *text = nullptr;  // the scanned stream on the device (d_data, or d_packed)
+	size_t stream_len = 0;
+	bool packed = true;          // the chunks lie back to back in h_data: no offset remapping
+	int32_t *rec_pat = nullptr, *rec_off = nullptr;   // the scan's (or segment pass's) planes, for finish()
 	void *d_packed = nullptr;
 	size_t chunks = 0, bytes = 0;
 	std::vector<int32_t> starts;
@@ -170,6 +181,9 @@ struct Worker {
 	long last_state = 0;
 	int seg_file = -1;        // -S: file of the last chunk submitted
 	bool seg_open = false;    // -S -t: that chunk ended inside a line
+	void *d_tail[2] = { nullptr, nullptr };   // -W: the last max_pattern_len bytes of the stream so far, ping-pong
+	int tail_cur = 0;
+	size_t tail_len = 0;
 	size_t matches = 0, reported = 0, bytes = 0, lines = 0, rounds = 0;
 };
 
@@ -206,6 +220,12 @@ void buffer_alloc(Buffer &b, const Config &c)
 		CK(acm_rt_malloc(&b.d_seg_off, (size + 2) * 4));
 		CK(acm_rt_malloc(&b.d_seg_start, (G + 1) * 4));
 		CK(acm_rt_malloc(&b.d_seg_ws, b.seg_ws_bytes));
+	}
+	if (c.words) {
+		b.word_ws_bytes = acm_word_workspace_bytes(size);
+		CK(acm_rt_malloc(&b.d_word_pat, (size + 2) * 4));
+		CK(acm_rt_malloc(&b.d_word_off, (size + 2) * 4));
+		CK(acm_rt_malloc(&b.d_word_ws, b.word_ws_bytes));
 	}
 	if (c.all_patterns) {
 		b.expand_ws_bytes = acm_expand_workspace_bytes(size);
@@ -271,42 +291,76 @@ size_t fill_text(Buffer &b, const Config &c, FILE *fp, int file_id, size_t *line
 	return total;
 }
 
-// enqueue copy-in, scan, bucket planes and copy-back of one buffer; no sync.  prev: the worker's buffer
-// in front of this one if its results have not been collected yet -- the scan then starts in the state
-// that buffer's scan ended in, read from its planes ON THE DEVICE (acm_scan_batch.d_init_plane; the
-// reference carries it through the host, databuf.c:622): the GPU goes on with this buffer while the
-// host walks the previous one's results.
+// the buffer's chunk list as one stream: chunk starts, its length, and (-S) where its texts begin.  Host
+// only; called for every buffer in order, before submit
+void prepare(Worker &w, Buffer &b)
+{
+	const Config &c = w.sh->cfg;
+	const int chunks = (int)b.chunks;
+	size_t stream_len = 0;
+	b.packed = true;
+	b.starts.resize((size_t)chunks + 1);
+	for (int i = 0; i < chunks; i++) {
+		if ((size_t)b.h_indices[i] != stream_len)
+			b.packed = false;
+		b.starts[i] = (int32_t)stream_len;
+		stream_len += (size_t)b.h_sizes[i];
+	}
+	b.starts[chunks] = (int32_t)stream_len;
+	b.stream_len = stream_len;
+	if (c.segmented) {
+		// a text begins at every chunk of another file than the chunk before it (-t: and at every chunk
+		// that follows a finished line); a long line split over chunks, or a file over buffers, goes on
+		b.seg_starts.clear();
+		for (int i = 0; i < chunks; i++) {
+			if (b.file_ids[i] != w.seg_file || (c.text_mode && !w.seg_open))
+				b.seg_starts.push_back(b.starts[i]);
+			w.seg_file = b.file_ids[i];
+			w.seg_open = b.h_sizes[i] > 0 && b.h_data[b.h_indices[i] + b.h_sizes[i] - 1] != '\n';
+		}
+	}
+}
+
+// -W: the byte that follows the stream of the buffer in front of b, the first byte of b's stream; -1
+// where b begins a new text (-S) or has no bytes
+int first_byte(const Config &c, const Buffer &b)
+{
+	if (c.segmented && !b.seg_starts.empty() && b.seg_starts[0] == 0)
+		return -1;
+	for (size_t i = 0; i < b.chunks; i++)
+		if (b.h_sizes[i] > 0)
+			return b.h_data[b.h_indices[i]];
+	return -1;
+}
+
+void finish(Worker &w, Buffer &b, int next_byte);
+
+// enqueue copy-in and scan of one buffer (prepared), then, without -W, its bucket planes and copy-back;
+// no sync.  prev: the worker's buffer in front of this one if its results have not been collected yet --
+// the scan then starts in the state that buffer's scan ended in, read from its planes ON THE DEVICE
+// (acm_scan_batch.d_init_plane; the reference carries it through the host, databuf.c:622): the GPU goes on
+// with this buffer while the host walks the previous one's results.
 void submit(Worker &w, Buffer &b, const Buffer *prev)
 {
 	const Config &c = w.sh->cfg;
 	const int chunks = (int)b.chunks;
 	void *s = w.stream;
-	size_t stream_len = 0;
-	bool packed = true;
-	b.starts.resize((size_t)chunks + 1);
-	for (int i = 0; i < chunks; i++) {
-		if ((size_t)b.h_indices[i] != stream_len)
-			packed = false;
-		b.starts[i] = (int32_t)stream_len;
-		stream_len += (size_t)b.h_sizes[i];
-	}
-	b.starts[chunks] = (int32_t)stream_len;
 	CK(acm_rt_memcpy_h2d(b.d_data, b.h_data, (b.bytes + 15) & ~(size_t)15, s));
 	CK(acm_rt_memcpy_h2d(b.d_indices, b.h_indices, (size_t)chunks * 4, s));
 	CK(acm_rt_memcpy_h2d(b.d_sizes, b.h_sizes, (size_t)chunks * 4, s));
-	size_t cap = (size_t)c.global_ws * c.chunk + 2;
-	const void *text = b.d_data;
-	if (!packed) {   // padded chunk list: scan the chunks' bytes back to back
+	const size_t cap = (size_t)c.global_ws * c.chunk + 2;
+	b.text = b.d_data;
+	if (!b.packed) {   // padded chunk list: scan the chunks' bytes back to back
 		CK(acm_rt_memcpy_h2d(b.d_starts, b.starts.data(), ((size_t)chunks + 1) * 4, s));
 		CK(acm_pack_chunks(b.d_packed, b.d_data, (const int32_t *)b.d_indices, (const int32_t *)b.d_sizes,
 		    (const int32_t *)b.d_starts, chunks, s));
-		text = b.d_packed;
+		b.text = b.d_packed;
 	}
 	int32_t *pat = (int32_t *)b.d_pat, *off = (int32_t *)b.d_off;
 	acm_scan_batch sb;
 	memset(&sb, 0, sizeof(sb));
-	sb.d_text = text;
-	sb.n = stream_len;
+	sb.d_text = b.text;
+	sb.n = b.stream_len;
 	sb.init_state = w.last_state;
 	if (prev) {
 		sb.init_state = 0;
@@ -321,35 +375,53 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 	sb.stream = s;
 	b.scan_cap = cap;
 	b.end_plane = pat;
+	// final states instead of head patterns where a pass over the records follows: the segment pass
+	// clamps every one to its own text, the word pass keeps whole words, the expansion (-A) lists them
+	const bool states = c.segmented || c.words || c.all_patterns;
+	sb.report = states ? ACM_REPORT_STATE : ACM_REPORT_HEAD;
+	if (c.segmented && !b.seg_starts.empty())
+		CK(acm_rt_memcpy_h2d(b.d_seg_start, b.seg_starts.data(), b.seg_starts.size() * 4, s));
+	CK(acm_scan_batch_async(w.dfa, &sb));
 	if (c.segmented) {
-		// a text begins at every chunk of another file than the chunk before it (-t: and at every chunk
-		// that follows a finished line); a long line split over chunks, or a file over buffers, goes on
-		b.seg_starts.clear();
-		for (int i = 0; i < chunks; i++) {
-			if (b.file_ids[i] != w.seg_file || (c.text_mode && !w.seg_open))
-				b.seg_starts.push_back(b.starts[i]);
-			w.seg_file = b.file_ids[i];
-			w.seg_open = b.h_sizes[i] > 0 && b.h_data[b.h_indices[i] + b.h_sizes[i] - 1] != '\n';
-		}
-		if (!b.seg_starts.empty())
-			CK(acm_rt_memcpy_h2d(b.d_seg_start, b.seg_starts.data(), b.seg_starts.size() * 4, s));
-		// the scan reports final states, the segment pass clamps every one to its own text
-		sb.report = ACM_REPORT_STATE;
-		CK(acm_scan_batch_async(w.dfa, &sb));
 		CK(acm_segment_matches_async(w.dfa, pat, off, cap - 2, (const int32_t *)b.d_seg_start, b.seg_starts.size(),
-		    (long)stream_len, c.all_patterns ? ACM_REPORT_STATE : ACM_REPORT_HEAD, (int32_t *)b.d_seg_pat,
-		    (int32_t *)b.d_seg_off, nullptr, cap, nullptr, b.d_seg_ws, b.seg_ws_bytes, s));
+		    (long)b.stream_len, (c.all_patterns || c.words) ? ACM_REPORT_STATE : ACM_REPORT_HEAD,
+		    (int32_t *)b.d_seg_pat, (int32_t *)b.d_seg_off, nullptr, cap, nullptr, b.d_seg_ws, b.seg_ws_bytes, s));
 		pat = (int32_t *)b.d_seg_pat;
 		off = (int32_t *)b.d_seg_off;
 		b.end_plane = pat;   // its trailer is the clamped state: the next buffer goes on from there
 	}
-	if (!c.all_patterns) {
-		if (!c.segmented)
-			CK(acm_scan_batch_async(w.dfa, &sb));
-	} else {   // final states instead of head patterns, then every pattern of each state's match list
-		sb.report = ACM_REPORT_STATE;
-		if (!c.segmented)
-			CK(acm_scan_batch_async(w.dfa, &sb));
+	b.rec_pat = pat;
+	b.rec_off = off;
+	if (!c.words)
+		finish(w, b, -1);
+}
+
+// enqueue the passes over b's records, its bucket planes and copy-back.  -W: called once the byte after
+// b's stream is known (next_byte: the first byte of the next buffer, or -1 at the end of the stream), on
+// the worker's stream in front of the next buffer's copy-in
+void finish(Worker &w, Buffer &b, int next_byte)
+{
+	const Config &c = w.sh->cfg;
+	const int chunks = (int)b.chunks;
+	void *s = w.stream;
+	int32_t *pat = b.rec_pat, *off = b.rec_off;
+	size_t cap = b.scan_cap;
+	if (c.words) {   // whole words; with -A every word-bounded pattern (the expansion's place)
+		int32_t *wp = (int32_t *)(c.all_patterns ? b.d_pat_all : b.d_word_pat);
+		int32_t *wo = (int32_t *)(c.all_patterns ? b.d_off_all : b.d_word_off);
+		const size_t wcap = c.all_patterns ? b.all_cap : b.scan_cap;
+		CK(acm_word_matches_async(w.dfa, pat, off, cap - 2, b.text, 0, (long)b.stream_len,
+		    w.tail_len ? w.d_tail[w.tail_cur] : nullptr, w.tail_len, next_byte,
+		    c.segmented ? (const int32_t *)b.d_seg_start : nullptr, c.segmented ? b.seg_starts.size() : 0, nullptr,
+		    c.all_patterns, wp, wo, wcap, w.d_tail[w.tail_cur ^ 1], b.d_word_ws, b.word_ws_bytes, s));
+		w.tail_cur ^= 1;
+		w.tail_len = std::min((size_t)w.sh->max_pattern_len, w.tail_len + b.stream_len);
+		pat = wp;
+		off = wo;
+		cap = wcap;
+		if (c.all_patterns)
+			CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
+	} else if (c.all_patterns) {   // every pattern of each final state's match list
 		CK(acm_expand_matches_async(w.dfa, pat, off, cap - 2, (int32_t *)b.d_pat_all, (int32_t *)b.d_off_all,
 		    b.all_cap, b.d_expand_ws, b.expand_ws_bytes, s));
 		pat = (int32_t *)b.d_pat_all;
@@ -357,7 +429,7 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 		cap = b.all_cap;
 		CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
 	}
-	if (!packed)
+	if (!b.packed)
 		CK(acm_remap_offsets(off, cap - 2, (const int32_t *)b.d_indices,
 		    (const int32_t *)b.d_starts, chunks, s));
 	CK(acm_bucketize(pat, off, (const int32_t *)b.d_indices,
@@ -428,6 +500,9 @@ void *worker_main(void *arg)
 	CK(acm_rt_malloc(&w.ws, w.ws_bytes));
 	buffer_alloc(w.buf[0], c);
 	buffer_alloc(w.buf[1], c);
+	if (c.words)
+		for (void *&t : w.d_tail)
+			CK(acm_rt_malloc(&t, (size_t)sh.max_pattern_len + 16));
 	pthread_barrier_wait(&sh.ready);
 
 	const int nfiles = (int)sh.files.size();
@@ -481,6 +556,9 @@ void *worker_main(void *arg)
 		if (b.chunks > 0 && (full || last || (c.follow && file_done))) {
 			// the scan starts in the state the previous buffer ended in: taken from that buffer's planes on
 			// the device, so this one is enqueued BEFORE the host waits for the previous one and walks its results
+			prepare(w, b);
+			if (in_flight && c.words)   // b's first byte ends the previous buffer's stream
+				finish(w, w.buf[filling ^ 1], first_byte(c, b));
 			submit(w, b, in_flight ? &w.buf[filling ^ 1] : nullptr);   // GPU works on b while we read into the other buffer
 			if (in_flight)
 				collect(w, w.buf[filling ^ 1]);
@@ -490,8 +568,11 @@ void *worker_main(void *arg)
 		if (g_terminate)
 			break;
 	}
-	if (in_flight)
+	if (in_flight) {
+		if (c.words)   // the end of the worker's stream
+			finish(w, w.buf[filling ^ 1], -1);
 		collect(w, w.buf[filling ^ 1]);
+	}
 	return nullptr;
 }
 
@@ -505,7 +586,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiS")) != -1) {   // ocl_aho_grep.c:411 + A, i, S
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSW")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -534,6 +615,7 @@ int main(int argc, char **argv)
 		case 'A': c.all_patterns = 1; break;
 		case 'i': c.nocase = 1; break;
 		case 'S': c.segmented = 1; break;
+		case 'W': c.words = 1; break;
 		default: usage();
 		}
 	}
@@ -551,6 +633,10 @@ int main(int argc, char **argv)
 	if (c.pat_limit != -1 && c.pat_limit <= 0) { printf("ERROR: The pattern size limit should be >= 1\n"); err++; }
 	if (c.pat_limit >= 4096) { printf("ERROR: The pattern size limit should be <= 4095\n"); err++; }
 	if (c.max_results <= 0) { printf("ERROR: The maximum result cells should be >= 1\n"); err++; }
+	if (c.words && c.follow) {   // a buffer's word test needs the byte after it, unknown while the input pauses
+		printf("ERROR: -W cannot be combined with -F: the byte after a paused input is not known\n");
+		err++;
+	}
 	if (err)
 		usage();
 	auto align16 = [](long &v, const char *what) {   // align_parameters, ocl_aho_grep.c:316-346
@@ -629,6 +715,7 @@ int main(int argc, char **argv)
 		sh.dfas.push_back(dfa);
 	}
 	const size_t automaton_bytes = acm_dfa_device_bytes(sh.dfas[0]);
+	sh.max_pattern_len = acm_automaton_max_pattern_len(aut);
 	acm_automaton_free(aut);
 
 	signal(SIGINT, on_sigint);

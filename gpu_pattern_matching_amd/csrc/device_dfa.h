@@ -46,6 +46,8 @@ struct acm_dfa {
 	uint32_t *d_list_len = nullptr;      // [states] its length (0: not final)
 	int32_t *d_list_pool = nullptr;      // pattern indices, list order
 	uint32_t *d_fail_depth = nullptr;    // [states, reference numbering][2] {fail link, trie depth}: segmented scans (segment.hip)
+	uint32_t *d_pat_len = nullptr;       // [patterns] bytes of each pattern: where a list entry starts (word.hip)
+	uint32_t num_patterns = 0;
 	size_t device_bytes = 0;
 	void *arena = nullptr;               // one allocation for the small tables (device_dfa.hip, upload_small)
 	size_t arena_bytes = 0, arena_used = 0;

@@ -285,8 +285,10 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 
 	int rc = ACM_OK;
 	{
-		// 48 B per state for the tables below, 8 more for the segment pass's {fail, depth} records
-		const size_t want = (((size_t)a->num_states * 56 + (8u << 20)) + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1);
+		// 48 B per state for the tables below, 8 more for the segment pass's {fail, depth} records, 4 per
+		// pattern for the word pass's lengths
+		const size_t want = (((size_t)a->num_states * 56 + a->patterns.size() * 4 + (8u << 20)) + (2u << 20) - 1) &
+		                    ~(size_t)((2u << 20) - 1);
 		if (hipMalloc(&d->arena, want) == hipSuccess) {
 			d->arena_bytes = want;
 			d->device_bytes += want;
@@ -367,6 +369,12 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 			fd[2 * (size_t)r + 1] = a->depth[r];
 		}
 		if (rc == ACM_OK) rc = upload_small(d, &d->d_fail_depth, fd.data(), fd.size());
+		// length of every pattern: the word pass finds where a list entry starts (word.hip)
+		std::vector<uint32_t> plen(a->patterns.size());
+		for (size_t i = 0; i < plen.size(); i++)
+			plen[i] = (uint32_t)a->patterns[i].bytes.size();
+		d->num_patterns = (uint32_t)plen.size();
+		if (rc == ACM_OK) rc = upload_small(d, &d->d_pat_len, plen.data(), plen.size());
 	} catch (const std::bad_alloc &) {
 		rc = acm::fail(ACM_ERR_NOMEM, "acm_dfa_upload: out of host memory");
 	}
@@ -421,6 +429,7 @@ extern "C" void acm_dfa_release(acm_dfa *d)
 		hipFree(d->d_list_len);
 		hipFree(d->d_list_pool);
 		free_small(d, d->d_fail_depth);
+		free_small(d, d->d_pat_len);
 		free_small(d, d->d_depth);
 		free_small(d, d->d_class);
 		free_small(d, d->d_sv_bloom);

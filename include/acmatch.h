@@ -294,6 +294,49 @@ int acm_segment_matches_async(const acm_dfa *, const int32_t *d_state_plane,
     int32_t *d_seg_out, size_t out_capacity, int32_t *d_seg_counts, void *d_workspace,
     size_t workspace_bytes, void *stream);
 
+/* Whole-word matching (grep -w).  A word byte is a byte of the set W: word_set (host, 32 bytes, bit
+ * b of byte b / 8 set = byte b is a word byte), or with word_set NULL the default [0-9A-Za-z_] (grep's
+ * C locale; bytes >= 0x80 are not word bytes).  Pattern P of length L >= 1 that ends at offset o
+ * (starts at a = o - L + 1) is word-bounded when both hold:
+ *   the byte at a - 1 is not in W, or a is the start of the text;
+ *   the byte at o + 1 is not in W, or o + 1 is the end of the text.
+ * Only the bytes outside the match are looked at (grep -w, not a regex \b); patterns of length 0 are
+ * never word-bounded.  The test reads raw text bytes: case folding (nocase automata) does not enter.
+ * Input: the planes of a scan enqueued with report = ACM_REPORT_STATE, or of the segment pass in STATE
+ * form (at most max_records records are looked at, as in acm_expand_matches_async), offsets in the
+ * coordinates the scan reported (offset_shift included: a shard or halo scan passes its halo as part
+ * of d_text with text_origin = offset_shift).  The text:
+ *   d_text      d_text[i] = the byte at offset text_origin + i, for offsets [text_origin, text_end)
+ *   d_before    the bytes at [text_origin - before_len, text_origin) (a streaming caller's previous
+ *               piece); offsets further back are the text start
+ *   next_byte   the byte at text_end, or -1: the text ends there
+ *   d_seg_start optional (segments == 0: none), as in acm_segment_matches_async: every start is a text
+ *               start and the end of the text in front of it.  Pass the segment pass's output.
+ * Output, the scan's cell layout and overflow contract ([0] = full count, records, trailer at
+ * min(count + 1, out_capacity - 1)):
+ *   all_patterns == 0  one record per offset where some pattern of the record's state is word-bounded:
+ *                      the first such pattern in match-list order (acm_automaton_state_matches).  With
+ *                      an empty W this is the scan's HEAD records bit for bit.
+ *   all_patterns != 0  one record per word-bounded pattern, list order, offsets ascending.  With an
+ *                      empty W this is acm_expand_matches_async's output bit for bit.
+ *   trailer            the input trailer unchanged: the output can be the next scan's d_init_plane
+ *   d_tail_out         (NULL: not wanted) the last min(max_pattern_len, before_len + text_end -
+ *                      text_origin) bytes of before ++ text: the next piece's d_before.  It must not
+ *                      overlap d_before or d_text.
+ * Chained calls over consecutive pieces of a stream (each piece's d_before the previous piece's tail,
+ * its next_byte the first byte of the following piece) give exactly the records of one call over the
+ * whole stream.  No text read leaves [text_origin, text_end) of d_text or d_before, whatever the
+ * records hold.  The output planes must not overlap the input planes.  Stream-ordered, no host sync,
+ * no allocation; argument errors return ACM_ERR_ARG before anything is enqueued.  A pass over the
+ * records (cost per record, not per text byte); the scan kernels are not involved. */
+size_t acm_word_workspace_bytes(size_t max_records);
+int acm_word_matches_async(const acm_dfa *, const int32_t *d_state_plane,
+    const int32_t *d_off_plane, size_t max_records, const void *d_text, long text_origin,
+    long text_end, const void *d_before, size_t before_len, int next_byte,
+    const int32_t *d_seg_start, size_t segments, const uint8_t *word_set, int all_patterns,
+    int32_t *d_pat_out, int32_t *d_off_out, size_t out_capacity, void *d_tail_out,
+    void *d_workspace, size_t workspace_bytes, void *stream);
+
 int acm_scan_batch_async(const acm_dfa *, const acm_scan_batch *);
 
 /* count batches with one call, enqueued in array order: what a worker pool
