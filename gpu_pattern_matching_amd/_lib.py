@@ -95,6 +95,7 @@ NATIVE_API = {
                                          _vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
     "acm_scan_set_mode": (C.c_int, [_vp, C.c_int]),
     "acm_scan_set_graphs": (C.c_int, [_vp, C.c_int]),
+    "acm_scan_graph_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "acm_scan_sparse_eligible": (C.c_int, [_vp]),
     "acm_scan_lds_resident": (C.c_int, [_vp]),
     "acm_scan_group_capable": (C.c_int, [_vp]),

@@ -225,6 +225,12 @@ class Matcher:
         """Replay repeating scans as HIP graphs (acm_scan_set_graphs); returns the setting in use."""
         return bool(self.lib.acm_scan_set_graphs(self.dfa, int(enable)))
 
+    def graph_stats(self):
+        """(graphs instantiated, hipGraphLaunch calls issued) since upload (acm_scan_graph_stats)."""
+        cap, run = C.c_uint64(), C.c_uint64()
+        check(self.lib.acm_scan_graph_stats(self.dfa, C.byref(cap), C.byref(run)), "acm_scan_graph_stats")
+        return cap.value, run.value
+
     def sparse_eligible(self):
         return bool(self.lib.acm_scan_sparse_eligible(self.dfa))
 

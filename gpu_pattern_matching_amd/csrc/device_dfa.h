@@ -102,6 +102,7 @@ struct acm_dfa {
 	mutable std::vector<void *> parked_graphs;   // evicted execs, destroyed by acm_dfa_release
 	mutable std::mutex graph_mutex;
 	mutable uint64_t graph_tick = 0;
+	mutable std::atomic<uint64_t> graphs_captured{0}, graphs_launched{0};   // acm_scan_graph_stats: instantiated, hipGraphLaunch calls
 
 	// optional in-line timing (acm_scan_profile_*): event triples
 	// {before walk, after walk, after last kernel} per recorded launch

@@ -1304,6 +1304,7 @@ extern "C" int acm_scan_batch_async(const acm_dfa *d, const acm_scan_batch *batc
 	if (exec) {
 		ACM_HIP_TRY(hipSetDevice(d->device));
 		ACM_HIP_TRY(hipGraphLaunch(exec, s));
+		d->graphs_launched.fetch_add(1, std::memory_order_relaxed);
 		return ACM_OK;
 	}
 	if (!capture)
@@ -1332,6 +1333,7 @@ extern "C" int acm_scan_batch_async(const acm_dfa *d, const acm_scan_batch *batc
 		d->use_graphs = false;
 		return enqueue_batch(d, batch, sparse);
 	}
+	d->graphs_captured.fetch_add(1, std::memory_order_relaxed);
 	{
 		std::lock_guard<std::mutex> lock(d->graph_mutex);
 		bool stored = false;
@@ -1341,12 +1343,25 @@ extern "C" int acm_scan_batch_async(const acm_dfa *d, const acm_scan_batch *batc
 				stored = true;
 			}
 		if (!stored) {   // evicted, or another thread was quicker
+			d->parked_graphs.push_back((void *)exec);   // cannot be destroyed while in flight (nor leaked if the launch fails)
 			ACM_HIP_TRY(hipGraphLaunch(exec, s));
-			d->parked_graphs.push_back((void *)exec);   // cannot be destroyed while in flight
+			d->graphs_launched.fetch_add(1, std::memory_order_relaxed);
 			return ACM_OK;
 		}
 	}
 	ACM_HIP_TRY(hipGraphLaunch(exec, s));
+	d->graphs_launched.fetch_add(1, std::memory_order_relaxed);
+	return ACM_OK;
+}
+
+extern "C" int acm_scan_graph_stats(const acm_dfa *d, uint64_t *captured, uint64_t *launched)
+{
+	if (!d)
+		return acm::fail(ACM_ERR_ARG, "acm_scan_graph_stats: null dfa");
+	if (captured)
+		*captured = d->graphs_captured.load(std::memory_order_relaxed);
+	if (launched)
+		*launched = d->graphs_launched.load(std::memory_order_relaxed);
 	return ACM_OK;
 }
 
@@ -1536,6 +1551,8 @@ int enqueue_batch(const acm_dfa *d, const acm_scan_batch *batch, bool sparse, De
 	if (empty) {
 		hipLaunchKernelGGL(k_finalize_empty, dim3(1), dim3(64), 0, s, a);
 		ACM_HIP_TRY(hipGetLastError());
+		if (batch->record_after_walk)   // (no walk: the batch behind this one waits for nothing older than this point)
+			ACM_HIP_TRY(hipEventRecord((hipEvent_t)batch->record_after_walk, s));
 		if (profile) {
 			for (int k = 1; k < 4; k++)
 				ACM_HIP_TRY(hipEventRecord(ev[k], s));

@@ -212,7 +212,10 @@ int acm_scan_set_chain_bytes(acm_dfa *, int chain_bytes);
  * batch k+1's first kernel waits for wait_before_walk (recorded by batch k
  * as record_after_walk) -- while everything behind it runs concurrently
  * with the next batch's first kernel.  Optional: independent streams alone
- * overlap as well, and that is what bench.py measures.
+ * overlap as well, and that is what bench.py measures.  Every batch that is
+ * enqueued records its record_after_walk, an empty text (n == 0: no walk)
+ * behind the kernel that writes its header and trailer, so a waiter never
+ * sees an older record of the event.
  */
 typedef struct acm_scan_batch {
 	const void *d_text;
@@ -374,6 +377,15 @@ int acm_scan_kernel_count(void);
  * event fields of acm_scan_batch.  enable = 0 / 1, -1 only queries.  Returns
  * the setting in use. */
 int acm_scan_set_graphs(acm_dfa *, int enable);
+/* What the graph path has done since acm_dfa_upload: captured = graphs
+ * instantiated (one per key seen twice, one more each time an evicted key comes
+ * back or two threads capture the same key at once), launched = hipGraphLaunch
+ * calls issued.  A key's first enqueue is plain, its second captures and
+ * launches, later ones only launch: R enqueues of one key give captured 1,
+ * launched R - 1.  Scans the graph path leaves out (NULL stream, profiling,
+ * event fields, n == 0, graphs off) move neither.  Either pointer may be NULL.
+ * ACM_ERR_ARG for a NULL dfa. */
+int acm_scan_graph_stats(const acm_dfa *, uint64_t *captured, uint64_t *launched);
 
 /* Which pipeline acm_scan_*_async runs.  Both produce the same planes.
  *   CHAIN   speculative chains (any pattern set)

@@ -110,15 +110,16 @@ def fill(bufs, how, stale=None):
         b.fill(how)
 
 
-def check_planes(pat, off, cap, exp, poison=PLANE_POISON, what="", pat_cells=True):
+def check_planes(pat, off, cap, exp, poison=PLANE_POISON, what="", pat_cells=True, stream=None):
     """The planes of cap cells hold exp = (offsets, pattern ids, final state) in the scan's layout: cells
     [0, min(m + 2, cap)) exact -- count, records, trailer (at cap - 1 on overflow) -- and every cell
     behind the trailer still the poison byte.  pat_cells=False: the pattern plane holds states
-    (REPORT_STATE); its records are not compared."""
+    (REPORT_STATE); its records are not compared.  stream: the stream the scan was enqueued on (the
+    download is ordered behind it)."""
     pos, ids, last = exp
     m = len(pos)
-    p = pat.to_numpy(np.int32, cap)
-    o = off.to_numpy(np.int32, cap)
+    p = pat.to_numpy(np.int32, cap, stream=stream)
+    o = off.to_numpy(np.int32, cap, stream=stream)
     stored = min(m, cap - 2)
     t = stored + 1
     assert int(p[0]) == m and int(o[0]) == m, "%s: count cells %d/%d, expected %d" % (what, p[0], o[0], m)

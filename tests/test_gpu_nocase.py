@@ -11,7 +11,9 @@ import pytest
 
 import fixtures
 import orc
+import streams
 from gpu_pattern_matching_amd import Automaton, DeviceArray, Matcher
+from gpu_pattern_matching_amd._lib import check
 from test_host_nocase import fold, folded_oracle, scramble
 
 pytestmark = pytest.mark.gpu
@@ -150,21 +152,38 @@ def test_launch_group_of_mixed_sizes(gpu, name):
 
 @pytest.mark.parametrize("mode", ["auto", "chain", "sparse"])
 def test_graph_mode(gpu, mode):
+    """graph replay of a nocase scan on a stream of its own (the NULL stream is never captured): the text
+    changes between the replays, and acm_scan_graph_stats shows one capture and R - 1 launches per key"""
     name = "clamav2000"
     o = folded_oracle(name)
     m = nocase_matcher(name, MiB)
     m.set_mode(mode)
     n = MiB
     d = DeviceArray(n)
+    rig = streams.Rig()
     try:
+        s = rig.stream()
         assert m.set_graphs(True)
+        paths, keep = [], []
         for seed in range(4):
             text = text_of(name, n, 500 + seed)
-            m.lib.acm_rt_memcpy_h2d(d.ptr, text.ctypes.data, n, m.stream)
-            m.scan_async(d, n)
-            assert_same(m.fetch(), o.scan(fold(text)))
+            keep.append(text)
+            check(m.lib.acm_rt_memcpy_h2d(d.ptr, text.ctypes.data, n, s), "h2d")
+            m.pat_plane.fill(0xEE, s)
+            m.off_plane.fill(0xEE, s)
+            m.scan_async(d, n, stream=s)
+            assert_same(m.fetch(stream=s), o.scan(fold(text)))
+            paths.append(m.path_taken(n, stream=s))
+        if mode != "auto":
+            assert paths == [mode] * 4
+        counts = [paths.count(p) for p in set(paths)]     # the pipeline is part of the key
+        got = m.graph_stats()
+        assert got == (sum(1 for c in counts if c >= 2), sum(c - 1 for c in counts)), (got, paths)
+        assert got[1] > 0                                 # for one pipeline (1, 3)
+        assert m.set_graphs(-1) is True                   # no silent fall-back
     finally:
         m.set_graphs(False)
+        rig.close()
         d.free()
         m.close()
 

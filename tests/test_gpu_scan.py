@@ -11,6 +11,7 @@ import pytest
 
 import fixtures
 import orc
+import streams
 from gpu_pattern_matching_amd import AcmError, Automaton, DeviceArray, Matcher
 from gpu_pattern_matching_amd._lib import check
 
@@ -216,11 +217,21 @@ def test_bad_arguments(gpu, lib):
     d.free()
 
 
+def expected_graph_stats(paths):
+    """(captured, launched) for enqueues of one set of buffers whose pipelines were paths: the pipeline is
+    part of a graph's key; a key's first enqueue is plain, its second captures and launches, later ones
+    only launch"""
+    counts = [paths.count(p) for p in set(paths)]
+    return sum(1 for c in counts if c >= 2), sum(c - 1 for c in counts)
+
+
 @pytest.mark.parametrize("mode", ["chain", "auto"])
 def test_graph_replay_tracks_buffer_contents(gpu, mode):
-    """With acm_scan_set_graphs on, a scan that repeats with the same buffers is replayed as a HIP
-    graph from its third enqueue on: the replay reads what is in the buffers then, not what
-    was there at capture, and gives what separate launches give."""
+    """With acm_scan_set_graphs on, a scan that repeats with the same buffers on a stream of its own is
+    captured into a HIP graph at its second enqueue and replayed from then on (never on the NULL stream):
+    the replay reads what is in the buffers then, not what was there at capture, and gives what separate
+    launches give.  acm_scan_graph_stats counts it: one capture and R - 1 launches for R enqueues of a
+    key, and no silent fall-back to plain launches."""
     name = "clamav2000"
     o = fixtures.oracle_for(name)
     pats = fixtures.patterns_of(name)
@@ -228,18 +239,36 @@ def test_graph_replay_tracks_buffer_contents(gpu, mode):
     m.set_mode(mode)
     n = 1 << 20
     d = DeviceArray(n)
+    rig = streams.Rig()
     try:
+        s = rig.stream()
         for graphs in (True, False):
             assert m.set_graphs(graphs) == graphs
+            before = m.graph_stats()
+            paths, keep = [], []
             for seed in range(5):
                 text = fixtures.text_for({"kind": "clamav", "n": n, "seed": 40 + seed, "n_plant": 100 * seed},
                                          pats)
-                check(m.lib.acm_rt_memcpy_h2d(d.ptr, text.ctypes.data, n, m.stream), "h2d")
-                m.scan_async(d, n)
-                assert_same(m.fetch(), o.scan(text))
+                keep.append(text)
+                check(m.lib.acm_rt_memcpy_h2d(d.ptr, text.ctypes.data, n, s), "h2d")
+                m.pat_plane.fill(0xEE, s)
+                m.off_plane.fill(0xEE, s)
+                m.scan_async(d, n, stream=s)
+                assert_same(m.fetch(stream=s), o.scan(text))
+                paths.append(m.path_taken(n, stream=s))
+            captured, launched = m.graph_stats()
+            got = (captured - before[0], launched - before[1])
+            if graphs:
+                assert set(paths) <= ({"chain"} if mode == "chain" else {"chain", "sparse"})
+                assert got == expected_graph_stats(paths), (got, paths)
+                assert got[1] > 0                       # really replayed: for one pipeline (1, 4)
+                assert m.set_graphs(-1) is True         # and never fell back to plain launches
+            else:
+                assert got == (0, 0)
     finally:
         m.set_graphs(False)
         m.set_mode("auto")
+        rig.close()
         d.free()
 
 
