@@ -34,6 +34,7 @@ class ShardPlan(C.Structure):
 
 
 REPORT_HEAD, REPORT_STATE = 0, 1
+TALLY_ACCUMULATE, TALLY_ALL_PATTERNS = 1, 2
 
 
 class AcmError(RuntimeError):
@@ -93,6 +94,9 @@ NATIVE_API = {
     "acm_word_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "acm_word_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_long, C.c_long, _vp, C.c_size_t, C.c_int,
                                          _vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "acm_tally_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "acm_tally_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t,
+                                          _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "acm_scan_set_mode": (C.c_int, [_vp, C.c_int]),
     "acm_scan_set_graphs": (C.c_int, [_vp, C.c_int]),
     "acm_scan_graph_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

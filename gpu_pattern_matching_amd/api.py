@@ -22,6 +22,14 @@ def _ptr(x):
     return int(x)
 
 
+def class_map(values):
+    """(labels, class_of) of one value per pattern: labels sorted and unique, class_of int32 with
+    labels[class_of[i]] == values[i] -- what Matcher.scan_tally and acm_tally_matches_async take.
+    class_map(np.sign(automaton.iids())) splits a categorical pattern file into negative / positive."""
+    labels, inverse = np.unique(np.asarray(values), return_inverse=True)
+    return labels, np.ascontiguousarray(inverse.reshape(-1), dtype=np.int32)
+
+
 class DeviceArray:
     """A hipMalloc'ed block; numpy in, numpy out."""
 
@@ -134,6 +142,10 @@ class Automaton:
         data = C.string_at(p.value, n.value) if n.value else b""
         return data, iid.value, nxt.value
 
+    def iids(self):
+        """int32[num_patterns]: the id every pattern was added with (the 'ID pattern' form of a pattern file)"""
+        return np.array([self.pattern(i)[1] for i in range(self.num_patterns)], dtype=np.int32)
+
     def state_matches(self, ref_state):
         """Every pattern index ending where the walk enters ref_state, list order."""
         buf = (C.c_int32 * 4096)()
@@ -181,6 +193,7 @@ class Matcher:
         h = C.c_void_p()
         check(self.lib.acm_dfa_upload(automaton.h, device, C.byref(h)), "acm_dfa_upload")
         self.dfa = h.value
+        self.num_patterns = automaton.num_patterns
         self.max_text = 0
         self.ws = self.pat_plane = self.off_plane = None
         self.reserve(max_text, plane_capacity)
@@ -532,6 +545,106 @@ class Matcher:
             p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
             o = off.to_numpy(np.int32, m + 2, stream=self.stream)
             return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1])
+        finally:
+            for b in bufs:
+                b.free()
+
+    def tally_async(self, pat_plane, off_plane, max_records, class_total, report=0, all_patterns=False,
+                    accumulate=False, class_of=None, num_classes=None, seg_start=None, segments=0, seg_class=None,
+                    lead=None, workspace=None, stream=None):
+        """Enqueue the tally pass (acm_tally_matches_async) over caller-owned device planes: entries per
+        class into class_total (uint64[num_classes]), per (segment, class) into seg_class
+        (int32[segments, num_classes]) and of the records in front of the first start into lead
+        (int32[num_classes]).  class_of: device int32[num_patterns] or None for the identity (num_classes
+        then defaults to the number of patterns).  workspace: (ptr, nbytes), or None for a temporary one
+        that lives until the stream has passed it (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        if num_classes is None:
+            if class_of is not None:
+                raise ValueError("num_classes is needed with a class map")
+            num_classes = self.num_patterns
+        tmp = None
+        if workspace is None:
+            nb = self.lib.acm_tally_workspace_bytes(max_records, num_classes)
+            tmp = DeviceArray(max(nb, 16))
+            workspace = (tmp.ptr, nb)
+        flags = (_lib.TALLY_ACCUMULATE if accumulate else 0) | (_lib.TALLY_ALL_PATTERNS if all_patterns else 0)
+        try:
+            check(self.lib.acm_tally_matches_async(
+                self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, report, flags, _ptr(class_of), num_classes,
+                _ptr(seg_start), segments, _ptr(class_total), _ptr(seg_class), _ptr(lead), _ptr(workspace[0]),
+                workspace[1], st), "acm_tally_matches_async")
+        finally:
+            if tmp is not None:
+                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
+                tmp.free()
+
+    def scan_tally(self, texts, class_of=None, num_classes=None, all_patterns=False, per_text=True, init_state=0):
+        """Count instead of list: scan, clamp every record to its own text when there are several
+        (acm_segment_matches_async), tally on the device (acm_tally_matches_async) and download only the
+        tallies.  texts: a list of bytes-like objects or a (uint8 array, int32 starts) pair, as
+        scan_segments takes them, or one bytes-like / uint8 array with no segments.  class_of: int32 class
+        of every pattern (class_map), None for one class per pattern; num_classes defaults to
+        max(class_of) + 1.  all_patterns: count every pattern that ends at an offset, else the one the
+        scan reports.  Returns (class_total uint64[C], seg_class int32[S, C] or None, lead int32[C],
+        last_state); seg_class is None without segments or with per_text=False."""
+        if isinstance(texts, (list, tuple)):
+            t, starts = self.pack_segments(texts)
+        else:
+            t = np.frombuffer(texts, dtype=np.uint8) if isinstance(texts, (bytes, bytearray, memoryview)) \
+                else np.ascontiguousarray(texts, dtype=np.uint8)
+            starts = np.zeros(0, dtype=np.int32)
+        nseg = int(starts.size)
+        cmap = None
+        if class_of is not None:
+            cmap = np.ascontiguousarray(class_of, dtype=np.int32)
+            if cmap.size != self.num_patterns:
+                raise ValueError("class_of has %d entries for %d patterns" % (cmap.size, self.num_patterns))
+            if num_classes is None:
+                num_classes = max(int(cmap.max()) + 1, 1) if cmap.size else 1
+        elif num_classes is None:
+            num_classes = self.num_patterns
+        ncls = int(num_classes)
+        self.reserve(max(t.size, 1))
+        max_records = self.plane_capacity - 2
+        cap = self.plane_capacity
+        want_rows = bool(per_text and nseg)
+        tally_ws = self.lib.acm_tally_workspace_bytes(max_records, ncls)
+        bufs = [DeviceArray.from_numpy(t, stream=self.stream), DeviceArray(max(tally_ws, 16)),
+                DeviceArray(max(ncls * 8, 16)), DeviceArray(max(ncls * 4, 16))]
+        d, ws, tot, lead = bufs
+        d_map = d_st = rows = None
+        if cmap is not None:
+            d_map = DeviceArray.from_numpy(cmap, pad_to=0, stream=self.stream) if cmap.size else DeviceArray(16)
+            bufs.append(d_map)
+        if nseg:
+            d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream)
+            bufs.append(d_st)
+        if want_rows:
+            rows = DeviceArray(max(nseg * ncls * 4, 16))
+            bufs.append(rows)
+        try:
+            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
+            sp, so = self.pat_plane, self.off_plane
+            if nseg:
+                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
+                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
+                bufs += sb
+                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
+                                   report=_lib.REPORT_STATE, workspace=(sb[0].ptr, seg_ws))
+                sp, so = sb[1], sb[2]
+            self.tally_async(sp, so, max_records, tot, report=_lib.REPORT_STATE, all_patterns=all_patterns,
+                             class_of=d_map, num_classes=ncls, seg_start=d_st, segments=nseg, seg_class=rows,
+                             lead=lead, workspace=(ws.ptr, tally_ws))
+            m = int(sp.to_numpy(np.int32, 1, stream=self.stream)[0])
+            if m > cap - 2:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_tally", "%d records but planes hold %d"
+                               % (m, cap - 2))
+            last = int(sp.to_numpy(np.int32, 1, offset_bytes=4 * (m + 1), stream=self.stream)[0])
+            seg_class = rows.to_numpy(np.int32, nseg * ncls, stream=self.stream).reshape(nseg, ncls) \
+                if want_rows else None
+            return (tot.to_numpy(np.uint64, ncls, stream=self.stream), seg_class,
+                    lead.to_numpy(np.int32, ncls, stream=self.stream), last)
         finally:
             for b in bufs:
                 b.free()

@@ -53,7 +53,7 @@ double now_us()
 	printf("\nUsage:\n"
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
-	       "             [-w cpu_threads] [-R max] [-tvxFMAiSW]\n"
+	       "             [-w cpu_threads] [-R max] [-tvxFMAiSWc]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -81,6 +81,11 @@ double now_us()
 	       "  -W             whole words only (grep -w): a pattern counts where the bytes around it\n"
 	       "                 are not in [0-9A-Za-z_] or are a text start or end; with -A every such\n"
 	       "                 pattern, else the first of the match list (extension; not with -F)\n"
+	       "  -c             exact counts of the records the run reports, tallied on the device and not\n"
+	       "                 limited by -R (extension): after the workers have finished, one line\n"
+	       "                 \"Count file '<path>': <n>\" per input file and one line\n"
+	       "                 \"Count pattern <id> ('<bytes>'): <n>\" per pattern with n > 0; a record\n"
+	       "                 belongs to the file that holds its last byte\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -121,7 +126,7 @@ std::vector<std::string> regular_files_in(std::string dir)
 struct Config {
 	std::string pat_path, data_path;
 	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0,
-	    words = 0;
+	    words = 0, count = 0;
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
 	long global_ws = -1, local_ws = -1, chunk = -1;
@@ -158,6 +163,14 @@ struct Buffer {   // one of the two staging buffers of a worker
 	const int32_t *end_plane = nullptr;   // plane whose trailer holds the state the next buffer starts in
 	void *d_word_pat = nullptr, *d_word_off = nullptr, *d_word_ws = nullptr;   // -W only
 	size_t word_ws_bytes = 0;
+	// -c only: the grid of file starts of this buffer's stream, the counts per start, of the records in front
+	// of the first start (they belong to cnt_prev_file) and of the whole buffer, and their pinned host twins
+	void *d_cnt_start = nullptr, *d_cnt_rows = nullptr, *d_cnt_lead = nullptr, *d_cnt_total = nullptr, *d_cnt_ws = nullptr;
+	int32_t *h_cnt_rows = nullptr, *h_cnt_lead = nullptr;
+	uint64_t *h_cnt_total = nullptr;
+	size_t cnt_ws_bytes = 0;
+	std::vector<int32_t> cnt_starts, cnt_files;   // stream offset and file of every start
+	int cnt_prev_file = -1;      // file of the worker's last chunk in front of this buffer
 	const void *text = nullptr;  // the scanned stream on the device (d_data, or d_packed)
 	size_t stream_len = 0;
 	bool packed = true;          // the chunks lie back to back in h_data: no offset remapping
@@ -184,6 +197,9 @@ struct Worker {
 	void *d_tail[2] = { nullptr, nullptr };   // -W: the last max_pattern_len bytes of the stream so far, ping-pong
 	int tail_cur = 0;
 	size_t tail_len = 0;
+	int cnt_file = -1;        // -c: file of the last chunk prepared
+	void *d_pat_total = nullptr, *d_one_class = nullptr;   // -c: uint64 per pattern, summed over the buffers on the device; a map of every pattern to class 0
+	std::vector<uint64_t> pat_total, file_total;            // -c: the worker's counts per pattern (at its end) and per file
 	size_t matches = 0, reported = 0, bytes = 0, lines = 0, rounds = 0;
 };
 
@@ -226,6 +242,17 @@ void buffer_alloc(Buffer &b, const Config &c)
 		CK(acm_rt_malloc(&b.d_word_pat, (size + 2) * 4));
 		CK(acm_rt_malloc(&b.d_word_off, (size + 2) * 4));
 		CK(acm_rt_malloc(&b.d_word_ws, b.word_ws_bytes));
+	}
+	if (c.count) {
+		b.cnt_ws_bytes = acm_tally_workspace_bytes(size * kAllFactor, 1);
+		CK(acm_rt_malloc(&b.d_cnt_start, (G + 1) * 4));
+		CK(acm_rt_malloc(&b.d_cnt_rows, (G + 1) * 4));
+		CK(acm_rt_malloc(&b.d_cnt_lead, 16));
+		CK(acm_rt_malloc(&b.d_cnt_total, 16));
+		CK(acm_rt_malloc(&b.d_cnt_ws, b.cnt_ws_bytes));
+		CK(acm_rt_host_alloc((void **)&b.h_cnt_rows, (G + 1) * 4));
+		CK(acm_rt_host_alloc((void **)&b.h_cnt_lead, 64));
+		CK(acm_rt_host_alloc((void **)&b.h_cnt_total, 64));
 	}
 	if (c.all_patterns) {
 		b.expand_ws_bytes = acm_expand_workspace_bytes(size);
@@ -308,6 +335,18 @@ void prepare(Worker &w, Buffer &b)
 	}
 	b.starts[chunks] = (int32_t)stream_len;
 	b.stream_len = stream_len;
+	if (c.count) {   // a start at every chunk of another file than the chunk before it, across buffers too
+		b.cnt_starts.clear();
+		b.cnt_files.clear();
+		b.cnt_prev_file = w.cnt_file;
+		for (int i = 0; i < chunks; i++) {
+			if (b.file_ids[i] != w.cnt_file) {
+				b.cnt_starts.push_back(b.starts[i]);
+				b.cnt_files.push_back(b.file_ids[i]);
+			}
+			w.cnt_file = b.file_ids[i];
+		}
+	}
 	if (c.segmented) {
 		// a text begins at every chunk of another file than the chunk before it (-t: and at every chunk
 		// that follows a finished line); a long line split over chunks, or a file over buffers, goes on
@@ -429,6 +468,23 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		cap = b.all_cap;
 		CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
 	}
+	if (c.count && !w.sh->pat_iid.empty()) {
+		// exact counts of the records as they are reported (pattern indices by now, whatever passes ran),
+		// in stream coordinates: per pattern into the worker's running totals, per file over the grid of
+		// file starts; the records in front of the first start belong to the file the worker was in
+		const size_t np = w.sh->pat_iid.size(), nstart = b.cnt_starts.size();
+		CK(acm_tally_matches_async(w.dfa, pat, off, cap - 2, ACM_REPORT_HEAD, ACM_TALLY_ACCUMULATE, nullptr, np, nullptr, 0,
+		    (uint64_t *)w.d_pat_total, nullptr, nullptr, b.d_cnt_ws, b.cnt_ws_bytes, s));
+		if (nstart)
+			CK(acm_rt_memcpy_h2d(b.d_cnt_start, b.cnt_starts.data(), nstart * 4, s));
+		CK(acm_tally_matches_async(w.dfa, pat, off, cap - 2, ACM_REPORT_HEAD, 0, (const int32_t *)w.d_one_class, 1,
+		    (const int32_t *)b.d_cnt_start, nstart, (uint64_t *)b.d_cnt_total, nstart ? (int32_t *)b.d_cnt_rows : nullptr,
+		    (int32_t *)b.d_cnt_lead, b.d_cnt_ws, b.cnt_ws_bytes, s));
+		if (nstart)
+			CK(acm_rt_memcpy_d2h(b.h_cnt_rows, b.d_cnt_rows, nstart * 4, s));
+		CK(acm_rt_memcpy_d2h(b.h_cnt_lead, b.d_cnt_lead, 4, s));
+		CK(acm_rt_memcpy_d2h(b.h_cnt_total, b.d_cnt_total, 8, s));
+	}
 	if (!b.packed)
 		CK(acm_remap_offsets(off, cap - 2, (const int32_t *)b.d_indices,
 		    (const int32_t *)b.d_starts, chunks, s));
@@ -451,6 +507,17 @@ void collect(Worker &w, Buffer &b)
 		fprintf(stderr, "ERROR: -A produced %d records for one buffer, the planes hold %zu; use a smaller -G/-B\n",
 		    *b.h_all_count, b.all_cap - 2);
 		exit(1);
+	}
+	if (c.count && !w.sh->pat_iid.empty()) {
+		if (b.cnt_starts.empty()) {   // the whole buffer goes on with the file in front of it
+			if (b.cnt_prev_file >= 0)
+				w.file_total[(size_t)b.cnt_prev_file] += *b.h_cnt_total;
+		} else {
+			if (b.cnt_prev_file >= 0)
+				w.file_total[(size_t)b.cnt_prev_file] += (uint64_t)*b.h_cnt_lead;
+			for (size_t k = 0; k < b.cnt_starts.size(); k++)
+				w.file_total[(size_t)b.cnt_files[k]] += (uint64_t)b.h_cnt_rows[k];
+		}
 	}
 	const size_t chunks = b.chunks;
 	const int R = c.max_results;
@@ -503,6 +570,17 @@ void *worker_main(void *arg)
 	if (c.words)
 		for (void *&t : w.d_tail)
 			CK(acm_rt_malloc(&t, (size_t)sh.max_pattern_len + 16));
+	const size_t npat = sh.pat_iid.size();
+	if (c.count) {
+		w.file_total.assign(sh.files.size(), 0);
+		w.pat_total.assign(npat, 0);
+		if (npat) {
+			CK(acm_rt_malloc(&w.d_pat_total, npat * 8));
+			CK(acm_rt_malloc(&w.d_one_class, npat * 4));
+			CK(acm_rt_memset(w.d_pat_total, 0, npat * 8, w.stream));
+			CK(acm_rt_memset(w.d_one_class, 0, npat * 4, w.stream));
+		}
+	}
 	pthread_barrier_wait(&sh.ready);
 
 	const int nfiles = (int)sh.files.size();
@@ -573,6 +651,10 @@ void *worker_main(void *arg)
 			finish(w, w.buf[filling ^ 1], -1);
 		collect(w, w.buf[filling ^ 1]);
 	}
+	if (c.count && npat) {   // the per-pattern totals come back once
+		CK(acm_rt_memcpy_d2h(w.pat_total.data(), w.d_pat_total, npat * 8, w.stream));
+		CK(acm_rt_stream_sync(w.stream));
+	}
 	return nullptr;
 }
 
@@ -586,7 +668,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSW")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWc")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -616,6 +698,7 @@ int main(int argc, char **argv)
 		case 'i': c.nocase = 1; break;
 		case 'S': c.segmented = 1; break;
 		case 'W': c.words = 1; break;
+		case 'c': c.count = 1; break;
 		default: usage();
 		}
 	}
@@ -743,6 +826,20 @@ int main(int argc, char **argv)
 		rounds += w.rounds;
 	}
 	const double secs = (now_us() - t0) / 1e6;
+	if (c.count) {
+		std::vector<uint64_t> per_file(sh.files.size(), 0), per_pat(sh.pat_iid.size(), 0);
+		for (auto &w : workers) {
+			for (size_t i = 0; i < per_file.size(); i++)
+				per_file[i] += w.file_total[i];
+			for (size_t i = 0; i < per_pat.size(); i++)
+				per_pat[i] += w.pat_total[i];
+		}
+		for (size_t i = 0; i < per_file.size(); i++)
+			printf("Count file '%s': %lu\n", sh.files[i].c_str(), (unsigned long)per_file[i]);
+		for (size_t i = 0; i < per_pat.size(); i++)
+			if (per_pat[i])
+				printf("Count pattern %d ('%s'): %lu\n", sh.pat_iid[i], sh.pat_bytes[i].c_str(), (unsigned long)per_pat[i]);
+	}
 	printf("-------------- STATS --------------\n");   // ocl_aho_grep.c:615-631
 	printf("Matches:             %lu\n", (unsigned long)matches);
 	printf("Matches reported:    %lu\n", (unsigned long)reported);

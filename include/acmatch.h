@@ -340,6 +340,46 @@ int acm_word_matches_async(const acm_dfa *, const int32_t *d_state_plane,
     int32_t *d_pat_out, int32_t *d_off_out, size_t out_capacity, void *d_tail_out,
     void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* Match tallies: counts of the records of any pass, reduced on the device, so a caller who only counts
+ * (a classifier, grep -c, "which signatures hit which file") copies back the counts, not the records.
+ * Input: planes in the scan's cell layout; at most min([0], max_records) records are looked at, as in
+ * acm_expand_matches_async.  report says what the pattern plane's cells are:
+ *   ACM_REPORT_HEAD   pattern indices (a default scan, the segment pass in HEAD form, the word pass,
+ *                     acm_expand_matches_async): each record counts once
+ *   ACM_REPORT_STATE  final states (a STATE scan, the segment pass in STATE form): each record counts
+ *                     once, for the head of the state's match list; with ACM_TALLY_ALL_PATTERNS once for
+ *                     every entry of the list (the counts of the expansion, without materialising it).
+ *                     ACM_TALLY_ALL_PATTERNS with ACM_REPORT_HEAD is ACM_ERR_ARG.
+ * Classes: d_class_of is a device int32[num_patterns], the class of each pattern; NULL is the identity
+ * (num_classes must then be the number of patterns).  An entry whose class is negative or >=
+ * num_classes is counted nowhere, and so is a cell that is no pattern index or state.  No write leaves
+ * the output arrays whatever the planes and the class map hold.
+ * Segments (segments == 0: none): d_seg_start as in acm_segment_matches_async.  A record at offset o
+ * belongs to the last k with start[k] <= o; one in front of start[0] to no segment (the "lead": it
+ * continues a text of an earlier buffer).  The starts are only a grid of attribution: nothing is
+ * clamped; for per-text matching run the segment pass first and tally its output.
+ * Output:
+ *   d_class_total  uint64[num_classes], required: entries per class, the lead included.  Written whole;
+ *                  with ACM_TALLY_ACCUMULATE added to what is there (a running total over the buffers
+ *                  of a stream, kept on the device)
+ *   d_seg_class    (NULL: not wanted; needs segments > 0) int32[segments][num_classes], row-major,
+ *                  written whole.  segments * num_classes > 2^31 - 1 is ACM_ERR_LIMIT
+ *   d_lead         (NULL: not wanted) int32[num_classes], written whole: the entries of the records in
+ *                  front of start[0] (all zero when segments == 0); a streaming caller adds it to the
+ *                  last row of its previous buffer
+ * Integer sums: exact and the same on every run.  The outputs must not overlap the inputs.  Stream-
+ * ordered, no host sync, no allocation, no host read of device data; argument errors return before
+ * anything is enqueued.  One launch over the records behind the zero-fills of the outputs (cost per
+ * record, not per text byte); the scan kernels are not involved.  The workspace query is monotone in both
+ * arguments and a multiple of 256 (the pass keeps no scratch today; the block must still be given). */
+enum { ACM_TALLY_ACCUMULATE = 1, ACM_TALLY_ALL_PATTERNS = 2 };
+size_t acm_tally_workspace_bytes(size_t max_records, size_t num_classes);
+int acm_tally_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
+    const int32_t *d_off_plane, size_t max_records, int report, int flags,
+    const int32_t *d_class_of, size_t num_classes, const int32_t *d_seg_start, size_t segments,
+    uint64_t *d_class_total, int32_t *d_seg_class, int32_t *d_lead, void *d_workspace,
+    size_t workspace_bytes, void *stream);
+
 int acm_scan_batch_async(const acm_dfa *, const acm_scan_batch *);
 
 /* count batches with one call, enqueued in array order: what a worker pool
