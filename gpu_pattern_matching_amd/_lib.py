@@ -97,6 +97,13 @@ NATIVE_API = {
     "acm_tally_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_tally_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t,
                                           _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "acm_line_index_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "acm_line_index_async": (C.c_int, [_vp, C.c_size_t, C.c_long, C.c_int, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp,
+                                       C.c_size_t, _vp]),
+    "acm_line_number_async": (C.c_int, [_vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "acm_line_select_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "acm_line_select_async": (C.c_int, [_vp, C.c_size_t, _vp, C.c_long, C.c_long, _vp, C.c_size_t, C.c_int, _vp, _vp, _vp,
+                                        C.c_size_t, _vp, C.c_size_t, _vp]),
     "acm_scan_set_mode": (C.c_int, [_vp, C.c_int]),
     "acm_scan_set_graphs": (C.c_int, [_vp, C.c_int]),
     "acm_scan_graph_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -649,6 +649,125 @@ class Matcher:
             for b in bufs:
                 b.free()
 
+    def line_index_async(self, d_text, n, line_start, capacity, info, text_origin=0, delimiter=b"\n", prev_byte=-1,
+                         prev_info=None, workspace=None, stream=None):
+        """Enqueue the line index (acm_line_index_async) over device text: the line starts into line_start
+        (int32[capacity], INT32_MAX behind them: a valid seg_start for the segment, word and tally
+        passes) and the counts into info (int32[8]).  prev_info: the info of the piece in front, on the
+        device.  workspace: (ptr, nbytes), or None for a temporary one (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        d = delimiter[0] if isinstance(delimiter, (bytes, bytearray)) else int(delimiter)
+        tmp = None
+        if workspace is None:
+            nb = self.lib.acm_line_index_workspace_bytes(n)
+            tmp = DeviceArray(max(nb, 16))
+            workspace = (tmp.ptr, nb)
+        try:
+            check(self.lib.acm_line_index_async(_ptr(d_text), n, text_origin, d, prev_byte, _ptr(prev_info),
+                                                _ptr(line_start), capacity, _ptr(info), _ptr(workspace[0]), workspace[1],
+                                                st), "acm_line_index_async")
+        finally:
+            if tmp is not None:
+                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
+                tmp.free()
+
+    def line_number_async(self, line_start, capacity, info, offsets, count, line_out, d_count=None, stream=None):
+        """Enqueue acm_line_number_async: delimiters in front of each of count device offsets (of at most
+        *d_count of them when d_count is given: a plane's header cell) into line_out."""
+        st = stream if stream is not None else self.stream
+        check(self.lib.acm_line_number_async(_ptr(line_start), capacity, _ptr(info), _ptr(offsets), _ptr(d_count), count,
+                                             _ptr(line_out), st), "acm_line_number_async")
+
+    def line_select_async(self, line_start, capacity, info, text_origin, text_end, off_plane, max_records, rel_out,
+                          begin_out, next_out, out_capacity, invert=False, workspace=None, stream=None):
+        """Enqueue acm_line_select_async: the lines that hold a record of off_plane (invert: that hold
+        none) as (delimiters in front, first byte, first byte behind) planes in the scan's cell layout.
+        workspace: (ptr, nbytes), or None for a temporary one (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        tmp = None
+        if workspace is None:
+            nb = self.lib.acm_line_select_workspace_bytes(capacity)
+            tmp = DeviceArray(max(nb, 16))
+            workspace = (tmp.ptr, nb)
+        try:
+            check(self.lib.acm_line_select_async(_ptr(line_start), capacity, _ptr(info), text_origin, text_end,
+                                                 _ptr(off_plane), max_records, 1 if invert else 0, _ptr(rel_out),
+                                                 _ptr(begin_out), _ptr(next_out), out_capacity, _ptr(workspace[0]),
+                                                 workspace[1], st), "acm_line_select_async")
+        finally:
+            if tmp is not None:
+                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
+                tmp.free()
+
+    def scan_lines(self, text, delimiter=b"\n", per_line=False, all_patterns=False, invert=False, init_state=0):
+        """grep -n: scan host bytes, find the lines on the device (acm_line_index_async), number every
+        record's line (acm_line_number_async) and list the lines that hold a record, or with invert the
+        others (acm_line_select_async).  per_line: the device-made index goes to the segment pass first,
+        so no match spans two lines.  all_patterns: every pattern that ends at an offset.  Nothing is
+        split on the host.  A convenience call: a text of n bytes may have n lines, so the starts and the
+        three select planes are sized for that (about 16 bytes of device memory per text byte besides the
+        record planes, 0.6 GB for 32 MiB), allocated and freed on every call; a caller who knows a bound on
+        its lines uses the three *_async calls with its own buffers.  Returns (patterns int32[], offsets
+        uint32[], lines int64[] 1-based,
+        selected int64[k, 3] of (1-based line, first byte, first byte behind), number of lines)."""
+        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) \
+            else np.ascontiguousarray(text, dtype=np.uint8)
+        n = int(t.size)
+        self.reserve(max(n, 1))
+        cap = self.plane_capacity
+        max_records = cap - 2
+        lcap = n + 1
+        states = per_line or all_patterns
+        idx_ws = self.lib.acm_line_index_workspace_bytes(n)
+        sel_ws = self.lib.acm_line_select_workspace_bytes(lcap)
+        bufs = [DeviceArray.from_numpy(t, stream=self.stream), DeviceArray(lcap * 4), DeviceArray(32),
+                DeviceArray(max(idx_ws, sel_ws))]
+        d, starts, info, ws = bufs
+        try:
+            self.scan_async(d, n, init_state, report=_lib.REPORT_STATE if states else _lib.REPORT_HEAD)
+            self.line_index_async(d, n, starts, lcap, info, delimiter=delimiter, workspace=(ws.ptr, idx_ws))
+            pat, off, rcap = self.pat_plane, self.off_plane, cap
+            if per_line:
+                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
+                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
+                bufs += sb
+                self.segment_async(pat, off, max_records, starts, lcap, n, sb[1], sb[2], cap,
+                                   report=_lib.REPORT_STATE if all_patterns else _lib.REPORT_HEAD,
+                                   workspace=(sb[0].ptr, seg_ws))
+                pat, off = sb[1], sb[2]
+            if all_patterns:
+                rcap = 8 * cap
+                ex_ws = self.lib.acm_expand_workspace_bytes(max_records)
+                xb = [DeviceArray(ex_ws), DeviceArray(rcap * 4), DeviceArray(rcap * 4)]
+                bufs += xb
+                check(self.lib.acm_expand_matches_async(self.dfa, pat.ptr, off.ptr, max_records, xb[1].ptr, xb[2].ptr,
+                                                        rcap, xb[0].ptr, ex_ws, self.stream), "acm_expand_matches_async")
+                pat, off = xb[1], xb[2]
+            ob = [DeviceArray(rcap * 4)] + [DeviceArray((lcap + 2) * 4) for _ in range(3)]
+            bufs += ob
+            num, rel, beg, nxt = ob
+            self.line_number_async(starts, lcap, info, off.ptr + 4, rcap - 2, num, d_count=off)
+            self.line_select_async(starts, lcap, info, 0, n, off, rcap - 2, rel, beg, nxt, lcap + 2, invert=invert,
+                                   workspace=(ws.ptr, sel_ws))
+            m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
+            if m > rcap - 2:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_lines", "%d records but planes hold %d"
+                               % (m, rcap - 2))
+            h_info = info.to_numpy(np.int32, 8, stream=self.stream)
+            first = 1 + (int(np.uint32(h_info[4])) | int(np.uint32(h_info[5])) << 32)
+            p = pat.to_numpy(np.int32, m + 1, stream=self.stream)[1:]
+            o = off.to_numpy(np.int32, m + 1, stream=self.stream)[1:].astype(np.uint32)
+            ln = num.to_numpy(np.int32, m, stream=self.stream).astype(np.int64) + first
+            k = int(rel.to_numpy(np.int32, 1, stream=self.stream)[0])
+            sel = np.stack([rel.to_numpy(np.int32, k + 1, stream=self.stream)[1:].astype(np.int64) + first,
+                            beg.to_numpy(np.int32, k + 1, stream=self.stream)[1:].astype(np.int64),
+                            nxt.to_numpy(np.int32, k + 1, stream=self.stream)[1:].astype(np.int64)], axis=1)
+            lines = int(h_info[0]) + (1 if n and not h_info[2] else 0)
+            return p.copy(), o, ln, sel, lines
+        finally:
+            for b in bufs:
+                b.free()
+
     def scan(self, text, init_state=0):
         """Scan host bytes: upload, scan, download."""
         t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \

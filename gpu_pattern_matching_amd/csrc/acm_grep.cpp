@@ -53,7 +53,7 @@ double now_us()
 	printf("\nUsage:\n"
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
-	       "             [-w cpu_threads] [-R max] [-tvxFMAiSWc]\n"
+	       "             [-w cpu_threads] [-R max] [-tvxFMAiSWcn]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -86,6 +86,10 @@ double now_us()
 	       "                 \"Count file '<path>': <n>\" per input file and one line\n"
 	       "                 \"Count pattern <id> ('<bytes>'): <n>\" per pattern with n > 0; a record\n"
 	       "                 belongs to the file that holds its last byte\n"
+	       "  -n             line numbers (grep -n, extension; binary mode only): the lines of every buffer are\n"
+	       "                 found on the device, the -v line becomes \"... found in file '<path>' at line <l>\n"
+	       "                 offset <o> [relative: <r>]\" with the 1-based line number of the match's last byte\n"
+	       "                 in its file, and STATS gains \"Processed lines\", the newlines counted on the device\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -126,7 +130,7 @@ std::vector<std::string> regular_files_in(std::string dir)
 struct Config {
 	std::string pat_path, data_path;
 	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0,
-	    words = 0, count = 0;
+	    words = 0, count = 0, lineno = 0;
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
 	long global_ws = -1, local_ws = -1, chunk = -1;
@@ -171,6 +175,12 @@ struct Buffer {   // one of the two staging buffers of a worker
 	size_t cnt_ws_bytes = 0;
 	std::vector<int32_t> cnt_starts, cnt_files;   // stream offset and file of every start
 	int cnt_prev_file = -1;      // file of the worker's last chunk in front of this buffer
+	// -n only: the line starts of this buffer's stream and their info, the delimiters in front of every record
+	// (a plane in the records' layout, bucketed like the patterns) and in front of every file start
+	void *d_line_start = nullptr, *d_line_info = nullptr, *d_line_ws = nullptr, *d_line_plane = nullptr, *d_results3 = nullptr,
+	     *d_results3_off = nullptr, *d_start_line = nullptr;   // (d_results3_off: the bucket pass's second output, not read)
+	int32_t *h_results3 = nullptr, *h_start_line = nullptr, *h_line_info = nullptr;
+	size_t line_ws_bytes = 0;
 	const void *text = nullptr;  // the scanned stream on the device (d_data, or d_packed)
 	size_t stream_len = 0;
 	bool packed = true;          // the chunks lie back to back in h_data: no offset remapping
@@ -197,7 +207,9 @@ struct Worker {
 	void *d_tail[2] = { nullptr, nullptr };   // -W: the last max_pattern_len bytes of the stream so far, ping-pong
 	int tail_cur = 0;
 	size_t tail_len = 0;
-	int cnt_file = -1;        // -c: file of the last chunk prepared
+	int cnt_file = -1;        // -c, -n: file of the last chunk prepared
+	const int32_t *line_prev_info = nullptr;   // -n: d_line_info of the buffer indexed last
+	uint64_t line_carry = 0;  // -n: newlines of the file the last collected buffer ended in, up to that buffer's end
 	void *d_pat_total = nullptr, *d_one_class = nullptr;   // -c: uint64 per pattern, summed over the buffers on the device; a map of every pattern to class 0
 	std::vector<uint64_t> pat_total, file_total;            // -c: the worker's counts per pattern (at its end) and per file
 	size_t matches = 0, reported = 0, bytes = 0, lines = 0, rounds = 0;
@@ -211,7 +223,7 @@ void die_acm(const char *what)
 
 #define CK(call) do { if ((call) != ACM_OK) die_acm(#call); } while (0)
 
-void buffer_alloc(Buffer &b, const Config &c)
+void buffer_alloc(Buffer &b, const Config &c, void *stream)
 {
 	const size_t size = (size_t)c.global_ws * c.chunk, G = (size_t)c.global_ws;
 	const size_t plane = ((size_t)c.max_results * G + 1) * 4;
@@ -243,9 +255,25 @@ void buffer_alloc(Buffer &b, const Config &c)
 		CK(acm_rt_malloc(&b.d_word_off, (size + 2) * 4));
 		CK(acm_rt_malloc(&b.d_word_ws, b.word_ws_bytes));
 	}
+	if (c.lineno) {
+		const size_t cells = c.all_patterns ? size * kAllFactor + 2 : size + 2;
+		b.line_ws_bytes = acm_line_index_workspace_bytes(size);
+		CK(acm_rt_malloc(&b.d_line_start, (size + 1) * 4));
+		CK(acm_rt_malloc(&b.d_line_info, 32));
+		CK(acm_rt_malloc(&b.d_line_ws, b.line_ws_bytes));
+		CK(acm_rt_malloc(&b.d_line_plane, cells * 4));
+		CK(acm_rt_malloc(&b.d_results3, plane));
+		CK(acm_rt_malloc(&b.d_results3_off, plane));
+		CK(acm_rt_memset(b.d_line_plane, 0, cells * 4, stream));   // cells behind the records, the trailer among them, stay 0
+		CK(acm_rt_malloc(&b.d_start_line, (G + 1) * 4));
+		CK(acm_rt_host_alloc((void **)&b.h_results3, plane));
+		CK(acm_rt_host_alloc((void **)&b.h_start_line, (G + 1) * 4));
+		CK(acm_rt_host_alloc((void **)&b.h_line_info, 64));
+	}
+	if (c.count || c.lineno)
+		CK(acm_rt_malloc(&b.d_cnt_start, (G + 1) * 4));
 	if (c.count) {
 		b.cnt_ws_bytes = acm_tally_workspace_bytes(size * kAllFactor, 1);
-		CK(acm_rt_malloc(&b.d_cnt_start, (G + 1) * 4));
 		CK(acm_rt_malloc(&b.d_cnt_rows, (G + 1) * 4));
 		CK(acm_rt_malloc(&b.d_cnt_lead, 16));
 		CK(acm_rt_malloc(&b.d_cnt_total, 16));
@@ -335,7 +363,7 @@ void prepare(Worker &w, Buffer &b)
 	}
 	b.starts[chunks] = (int32_t)stream_len;
 	b.stream_len = stream_len;
-	if (c.count) {   // a start at every chunk of another file than the chunk before it, across buffers too
+	if (c.count || c.lineno) {   // a start at every chunk of another file than the chunk before it, across buffers too
 		b.cnt_starts.clear();
 		b.cnt_files.clear();
 		b.cnt_prev_file = w.cnt_file;
@@ -468,6 +496,24 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		cap = b.all_cap;
 		CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
 	}
+	if (c.lineno) {
+		// the lines of this buffer's stream, chained to the buffer in front of it on the device; then the
+		// newlines in front of every record and of every file start, in stream coordinates (before the remap)
+		const size_t nstart = b.cnt_starts.size(), lcap = (size_t)c.global_ws * c.chunk + 1;
+		CK(acm_line_index_async(b.text, b.stream_len, 0, '\n', -1, w.line_prev_info, (int32_t *)b.d_line_start, lcap,
+		    (int32_t *)b.d_line_info, b.d_line_ws, b.line_ws_bytes, s));
+		w.line_prev_info = (const int32_t *)b.d_line_info;
+		CK(acm_rt_memcpy_d2d(b.d_line_plane, off, 4, s));   // the header cell; the trailer cell is not used
+		CK(acm_line_number_async((const int32_t *)b.d_line_start, lcap, (const int32_t *)b.d_line_info, off + 1, off, cap - 2,
+		    (int32_t *)b.d_line_plane + 1, s));
+		if (nstart) {
+			CK(acm_rt_memcpy_h2d(b.d_cnt_start, b.cnt_starts.data(), nstart * 4, s));
+			CK(acm_line_number_async((const int32_t *)b.d_line_start, lcap, (const int32_t *)b.d_line_info,
+			    (const int32_t *)b.d_cnt_start, nullptr, nstart, (int32_t *)b.d_start_line, s));
+			CK(acm_rt_memcpy_d2h(b.h_start_line, b.d_start_line, nstart * 4, s));
+		}
+		CK(acm_rt_memcpy_d2h(b.h_line_info, b.d_line_info, 32, s));
+	}
 	if (c.count && !w.sh->pat_iid.empty()) {
 		// exact counts of the records as they are reported (pattern indices by now, whatever passes ran),
 		// in stream coordinates: per pattern into the worker's running totals, per file over the grid of
@@ -491,6 +537,11 @@ void finish(Worker &w, Buffer &b, int next_byte)
 	CK(acm_bucketize(pat, off, (const int32_t *)b.d_indices,
 	    (const int32_t *)b.d_sizes, chunks, c.max_results, (int32_t *)b.d_results, (int32_t *)b.d_results2, cap, s));
 	const size_t cells = (size_t)c.max_results * chunks + 1;
+	if (c.lineno) {   // the line plane through the same buckets: cell for cell where the pattern plane's cells went
+		CK(acm_bucketize((const int32_t *)b.d_line_plane, off, (const int32_t *)b.d_indices, (const int32_t *)b.d_sizes, chunks,
+		    c.max_results, (int32_t *)b.d_results3, (int32_t *)b.d_results3_off, cap, s));
+		CK(acm_rt_memcpy_d2h(b.h_results3, b.d_results3, cells * 4, s));
+	}
 	CK(acm_rt_memcpy_d2h(b.h_results, b.d_results, cells * 4, s));
 	CK(acm_rt_memcpy_d2h(b.h_results2, b.d_results2, cells * 4, s));
 	if (!b.done)
@@ -522,7 +573,12 @@ void collect(Worker &w, Buffer &b)
 	const size_t chunks = b.chunks;
 	const int R = c.max_results;
 	w.last_state = b.h_results[chunks * R];
+	long k_start = -1;   // -n: the file start the chunk lies behind (-1: its file began in an earlier buffer)
+	if (c.lineno)
+		w.lines += (size_t)b.h_line_info[1];
 	for (size_t i = 0; i < chunks; i++) {
+		while (c.lineno && k_start + 1 < (long)b.cnt_starts.size() && b.cnt_starts[(size_t)k_start + 1] <= b.starts[i])
+			k_start++;
 		const int n = b.h_results[i];
 		w.matches += (size_t)n;
 		for (int j = 0; j < n && j < R - 1; j++) {
@@ -532,9 +588,19 @@ void collect(Worker &w, Buffer &b)
 			if (!c.verbose)
 				continue;
 			pthread_mutex_lock(&w.sh->print_lock);
-			printf("Pattern %d ('%s') found in file '%s' at offset %d [relative: %d]\n",
-			    w.sh->pat_iid[p_idx], w.sh->pat_bytes[p_idx].c_str(),
-			    w.sh->files[b.file_ids[i]].c_str(), off, off - b.h_indices[i]);
+			if (c.lineno) {
+				// newlines in front of the record less those in front of its file's start; a file that began
+				// in an earlier buffer adds what those buffers counted for it
+				const uint64_t d_rec = (uint64_t)b.h_results3[(size_t)(j + 1) * chunks + i];
+				const uint64_t line = 1 + (k_start >= 0 ? d_rec - (uint64_t)b.h_start_line[k_start] : d_rec + w.line_carry);
+				printf("Pattern %d ('%s') found in file '%s' at line %lu offset %d [relative: %d]\n",
+				    w.sh->pat_iid[p_idx], w.sh->pat_bytes[p_idx].c_str(),
+				    w.sh->files[b.file_ids[i]].c_str(), (unsigned long)line, off, off - b.h_indices[i]);
+			} else {
+				printf("Pattern %d ('%s') found in file '%s' at offset %d [relative: %d]\n",
+				    w.sh->pat_iid[p_idx], w.sh->pat_bytes[p_idx].c_str(),
+				    w.sh->files[b.file_ids[i]].c_str(), off, off - b.h_indices[i]);
+			}
 			if (c.text_mode) {   // the matching line
 				fwrite(b.h_data + b.h_indices[i], 1, (size_t)b.h_sizes[i], stdout);
 			} else {             // some context around the match, up to a newline
@@ -551,6 +617,11 @@ void collect(Worker &w, Buffer &b)
 			pthread_mutex_unlock(&w.sh->print_lock);
 		}
 	}
+	if (c.lineno) {   // what the file this buffer ends in has counted so far
+		const size_t ns = b.cnt_starts.size();
+		const uint64_t all = (uint64_t)b.h_line_info[1];
+		w.line_carry = ns ? all - (uint64_t)b.h_start_line[ns - 1] : w.line_carry + all;
+	}
 	b.chunks = 0;
 	b.bytes = 0;
 	w.rounds++;
@@ -565,8 +636,8 @@ void *worker_main(void *arg)
 	CK(acm_rt_stream_create(&w.stream));
 	w.ws_bytes = acm_scan_workspace_bytes(w.dfa, (size_t)c.global_ws * c.chunk);
 	CK(acm_rt_malloc(&w.ws, w.ws_bytes));
-	buffer_alloc(w.buf[0], c);
-	buffer_alloc(w.buf[1], c);
+	buffer_alloc(w.buf[0], c, w.stream);
+	buffer_alloc(w.buf[1], c, w.stream);
 	if (c.words)
 		for (void *&t : w.d_tail)
 			CK(acm_rt_malloc(&t, (size_t)sh.max_pattern_len + 16));
@@ -668,7 +739,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWc")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcn")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -699,6 +770,7 @@ int main(int argc, char **argv)
 		case 'S': c.segmented = 1; break;
 		case 'W': c.words = 1; break;
 		case 'c': c.count = 1; break;
+		case 'n': c.lineno = 1; break;
 		default: usage();
 		}
 	}
@@ -718,6 +790,10 @@ int main(int argc, char **argv)
 	if (c.max_results <= 0) { printf("ERROR: The maximum result cells should be >= 1\n"); err++; }
 	if (c.words && c.follow) {   // a buffer's word test needs the byte after it, unknown while the input pauses
 		printf("ERROR: -W cannot be combined with -F: the byte after a paused input is not known\n");
+		err++;
+	}
+	if (c.lineno && c.text_mode) {
+		printf("ERROR: -n needs binary mode: -t already makes every line a chunk\n");
 		err++;
 	}
 	if (err)
@@ -847,7 +923,7 @@ int main(int argc, char **argv)
 	printf("Automaton states:    %d\n", states);
 	printf("Automaton size (MB): %.3f\n", (double)automaton_bytes / 1048576);
 	printf("Processed bytes:     %lu\n", (unsigned long)bytes);
-	if (lines)
+	if (lines || c.lineno)
 		printf("Processed lines:     %lu\n", (unsigned long)lines);
 	printf("Processed files:     %d\n", (int)sh.files.size());
 	printf("Kernel launches:     %d\n", (int)rounds);

@@ -380,6 +380,64 @@ int acm_tally_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
     uint64_t *d_class_total, int32_t *d_seg_class, int32_t *d_lead, void *d_workspace,
     size_t workspace_bytes, void *stream);
 
+/* Line index: where the lines of a text that is already on the device begin, so that the start array
+ * the segment, word and tally passes take (d_seg_start) need not be made on the host.  No acm_dfa is
+ * involved.  d_text follows the scan's contract (16-byte aligned, readable up to n rounded up to 16,
+ * n <= 2^31 - 17); d_text[i] is the byte at offset text_origin + i, text_end = text_origin + n.
+ * delimiter: any byte value 0..255 ('\n' for lines).  The starts, ascending, in the scan's coordinates:
+ *   text_origin   if n > 0 and the text begins a line: prev_byte == -1 (start of the stream) or
+ *                 prev_byte == delimiter.  With d_prev_info != NULL prev_byte is ignored and the rule
+ *                 is taken on the device from the d_info of the index call over the piece in front
+ *                 of this one (on the same stream, or complete; as acm_scan_batch.d_init_plane): the
+ *                 origin is a start iff that piece's [3] is set.  d_prev_info must not be d_info.
+ *   p + 1         for every delimiter at p in [text_origin, text_end) with p + 1 < text_end.  A
+ *                 delimiter on the last byte opens the NEXT piece's first line: "a\nb\n" has two lines.
+ * Output:
+ *   d_line_start  int32[capacity], written whole: the first min(m, capacity) starts, INT32_MAX in
+ *                 every cell behind them.  Starts at or beyond text_end are allowed as d_seg_start, so
+ *                 the array can be handed on with segments = capacity and nobody reads m on the host.
+ *   d_info        int32[8]: [0] m, the full count (m > capacity: overflow, the first capacity starts
+ *                 are stored, the scan's contract); [1] delimiters in [text_origin, text_end); [2] 1 if
+ *                 the origin is a start; [3] 1 if the next piece's origin is a start (an empty piece
+ *                 hands on what it was given); [4..5] uint64 (lo, hi) delimiters of the stream in front
+ *                 of text_origin (the previous piece's [4..5] + [1], 0 without d_prev_info); [6..7] 0.
+ * n == 0 is legal (m = 0; sentinels and d_info are written).  Bytes in [n, round16(n)) never count.
+ * Stream-ordered, no host sync, no allocation, no host read of device data; argument errors (a NULL
+ * output, capacity == 0, a misaligned d_text, n over the limit, delimiter outside 0..255, prev_byte
+ * outside -1..255, a short workspace) return ACM_ERR_ARG before anything is enqueued.  The workspace
+ * query is monotone and a multiple of 256.  Two launches; the text is read once (csrc/lines.hip). */
+size_t acm_line_index_workspace_bytes(size_t max_text);
+int acm_line_index_async(const void *d_text, size_t n, long text_origin, int delimiter,
+    int prev_byte, const int32_t *d_prev_info, int32_t *d_line_start, size_t capacity,
+    int32_t *d_info, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Delimiters in front of each offset.  For i < min(count, d_count ? max(*d_count, 0) : count):
+ * d_line_out[i] = number of delimiters in [text_origin, d_offsets[i]) = k + 1 - info[2], k the index
+ * of the last start <= d_offsets[i] (-1: none); cells behind that bound are not written.  The 1-based
+ * line number in the stream is 1 + info[4..5] + d_line_out[i]: the caller adds that after the fetch.
+ * For a scan's records pass d_offsets = d_off_plane + 1, d_count = d_off_plane, count = max_records;
+ * for arbitrary offsets d_count = NULL.  Offsets need not be sorted (a binary search each).  Only
+ * offsets in [text_origin, text_end) are guaranteed, and only when info[0] <= capacity. */
+int acm_line_number_async(const int32_t *d_line_start, size_t capacity, const int32_t *d_info,
+    const int32_t *d_offsets, const int32_t *d_count, size_t count, int32_t *d_line_out,
+    void *stream);
+
+/* The lines that hold a record (invert != 0: the lines that hold none).  The lines of the piece: the
+ * lead [text_origin, start[0]) if the origin is not a start and the piece is not empty, then
+ * [start[k], start[k + 1]) for k < m; the last line ends at text_end.  A line keeps its delimiter.  A
+ * record belongs to the line that holds its offset (the tally's rule); only d_off_plane is read (at
+ * most min([0], max_records) records), so any pass's planes can be given.  Output, the scan's cell
+ * layout and overflow contract in all three planes ([0] = full count, entries ascending, trailer cell
+ * at min(count + 1, out_capacity - 1) = 0): per entry d_rel_out = delimiters in front of the line
+ * (what acm_line_number_async gives for its first byte), d_begin_out and d_next_out = its first byte
+ * and the first byte behind it.  Exact when info[0] <= capacity.  Stream-ordered, no host sync, no
+ * allocation; cost per record and per line, never per text byte. */
+size_t acm_line_select_workspace_bytes(size_t capacity);
+int acm_line_select_async(const int32_t *d_line_start, size_t capacity, const int32_t *d_info,
+    long text_origin, long text_end, const int32_t *d_off_plane, size_t max_records, int invert,
+    int32_t *d_rel_out, int32_t *d_begin_out, int32_t *d_next_out, size_t out_capacity,
+    void *d_workspace, size_t workspace_bytes, void *stream);
+
 int acm_scan_batch_async(const acm_dfa *, const acm_scan_batch *);
 
 /* count batches with one call, enqueued in array order: what a worker pool
