@@ -6,33 +6,30 @@
 //   k_line_mask   each lane loads 16 B (dwordx4) per step, four steps in flight, and tests the four words
 //                 with a carry-free SWAR byte equality (exact per byte); the 16 hits become one uint16 of
 //                 a 1-bit-per-byte mask in the workspace (n / 8 bytes), their popcount is summed per block
-//   k_line_write  sums the counts of the blocks in front of its own (as k_segment<true> does), reads the
-//                 mask 64 bits per lane, ranks the set bits with popcount, a wave prefix and an LDS prefix
-//                 over the block's waves, and writes the starts in order: no atomics.  Every block then
-//                 takes a share of the INT32_MAX tail, block 0 writes d_info.
+//   k_line_write  reads the mask 64 bits per lane, ranks the set bits with popcount and the block
+//                 primitives of record_pass.h, and writes the starts in order.  Every
+//                 block then takes a share of the INT32_MAX tail, block 0 writes d_info.
 // Bytes in [n, round16(n)) are loaded (the scan's contract allows it) and masked off before they count.
 //
 // acm_line_number_async: a binary search per offset.  acm_line_select_async: a bit per line in the
 // workspace, zeroed, set by one launch over the records (atomic or, skipped where the bit is already
-// set), then an ordered compaction over the bits in two launches (count, write), as segment.hip does
-// over records.  Cost per record and per line, never per text byte.
+// set), then the two-launch ordered write of record_pass.h over the bits.  Cost per record and per line,
+// never per text byte.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "acm_internal.h"
+#include "record_pass.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr uint32_t kMaxBlocks = 1024;            // 4 blocks of 256 threads on each of 256 CUs
+using namespace acm_rp;
+
 constexpr size_t kCountBytes = kMaxBlocks * 4;   // the block counts in front of the masks / flags
 constexpr uint32_t kTileWords = kThreads;        // 64-bit mask words per tile: 16 KiB of text
 constexpr int kInFlight = 4;                     // 16-byte loads a lane has in flight in k_line_mask
 constexpr int32_t kSentinel = 0x7FFFFFFF;
-
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0)); }
 
 // 4 bits: byte j of w equals the byte every byte of pat repeats.  No carry crosses a byte: exact.
 __device__ __forceinline__ uint32_t eq4(uint32_t w, uint32_t pat)
@@ -42,66 +39,14 @@ __device__ __forceinline__ uint32_t eq4(uint32_t w, uint32_t pat)
 	return (((t >> 7) * 0x00204081u) >> 21) & 0xFu;   // bits 0, 8, 16, 24 -> 0, 1, 2, 3 (all partial products distinct)
 }
 
-struct Share {
+struct Words {
 	uint32_t w_begin, w_end;   // the block's mask words
 };
 
-__device__ __forceinline__ Share share_of(uint32_t words)
+__device__ __forceinline__ Words words_of(uint32_t words)
 {
-	const uint32_t tiles = (words + kTileWords - 1) / kTileWords, per = (tiles + gridDim.x - 1) / gridDim.x;
-	const uint32_t t_begin = min(blockIdx.x * per, tiles), t_end = min(t_begin + per, tiles);
-	return Share{ t_begin * kTileWords, min(t_end * kTileWords, words) };
-}
-
-// sum over the block of v; red: kWaves cells of LDS.  Every thread gets the sum.
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *red)
-{
-	for (int o = 32; o > 0; o >>= 1)
-		v += __shfl_xor(v, o, 64);
-	__syncthreads();   // (red of an earlier call is no longer read)
-	if (lane_id() == 0)
-		red[threadIdx.x / 64] = v;
-	__syncthreads();
-	uint32_t s = 0;
-	for (int w = 0; w < kWaves; w++)
-		s += red[w];
-	return s;
-}
-
-// exclusive prefix of v over the block in thread order, and the block's total
-__device__ __forceinline__ uint32_t block_prefix(uint32_t v, uint32_t *red, uint32_t &total)
-{
-	const uint32_t lane = lane_id(), wave = threadIdx.x / 64;
-	uint32_t inc = v;
-	for (int o = 1; o < 64; o <<= 1) {
-		const uint32_t up = __shfl_up(inc, o, 64);
-		inc += lane >= (uint32_t)o ? up : 0;
-	}
-	__syncthreads();
-	if (lane == 63)
-		red[wave] = inc;
-	__syncthreads();
-	uint32_t before = 0;
-	total = 0;
-	for (uint32_t w = 0; w < (uint32_t)kWaves; w++) {
-		before += w < wave ? red[w] : 0;
-		total += red[w];
-	}
-	return before + inc - v;
-}
-
-// counts of the blocks in front of this one, and of all blocks
-__device__ __forceinline__ uint32_t blocks_before(const int32_t *block_counts, uint32_t *red, uint32_t &all)
-{
-	uint32_t before = 0, sum = 0;
-	for (uint32_t j = threadIdx.x; j < gridDim.x; j += kThreads) {
-		const uint32_t c = (uint32_t)block_counts[j];
-		sum += c;
-		before += j < blockIdx.x ? c : 0;
-	}
-	before = block_sum(before, red);
-	all = block_sum(sum, red);
-	return before;
+	const Share sh = share_of((words + kTileWords - 1) / kTileWords);
+	return Words{ sh.t_begin * kTileWords, min(sh.t_end * kTileWords, words) };
 }
 
 // ------------------------------------------------------------------ index
@@ -123,7 +68,7 @@ struct IndexArgs {
 __global__ __launch_bounds__(kThreads) void k_line_mask(IndexArgs g)
 {
 	__shared__ uint32_t red[kWaves];
-	const Share sh = share_of(g.words);
+	const Words sh = words_of(g.words);
 	const uint32_t g_end = sh.w_end * 4, pat = g.delim * 0x01010101u;
 	uint32_t count = 0;
 	for (uint32_t base = sh.w_begin * 4; base < g_end; base += kThreads * kInFlight) {
@@ -156,7 +101,7 @@ __global__ __launch_bounds__(kThreads) void k_line_mask(IndexArgs g)
 
 __global__ __launch_bounds__(kThreads) void k_line_write(IndexArgs g)
 {
-	__shared__ uint32_t red[kWaves];
+	__shared__ uint32_t red[2 * kWaves];
 	const unsigned long long *mask64 = (const unsigned long long *)g.mask16;
 	uint32_t delims;
 	const uint32_t before = blocks_before(g.block_counts, red, delims);
@@ -166,7 +111,7 @@ __global__ __launch_bounds__(kThreads) void k_line_write(IndexArgs g)
 	const bool ends = g.n && (mask64[last_word] >> last_bit & 1);   // a delimiter on the last byte opens no line here
 	const uint32_t m = org + delims - (ends ? 1 : 0);
 
-	const Share sh = share_of(g.words);
+	const Words sh = words_of(g.words);
 	uint32_t base = org + before;
 	for (uint32_t w0 = sh.w_begin; w0 < sh.w_end; w0 += kTileWords) {
 		const uint32_t w = w0 + threadIdx.x;
@@ -207,19 +152,6 @@ __global__ __launch_bounds__(kThreads) void k_line_write(IndexArgs g)
 }
 
 // ------------------------------------------------------------------ number
-
-__device__ __forceinline__ uint32_t upper_bound_i32(const int32_t *a, uint32_t n, int32_t key)
-{
-	uint32_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (a[mid] <= key)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
 
 __device__ __forceinline__ uint32_t stored_starts(const int32_t *info, uint32_t capacity)
 {
@@ -284,18 +216,18 @@ __global__ __launch_bounds__(kThreads) void k_line_mark(SelectArgs g)
 template <bool WRITE>
 __global__ __launch_bounds__(kThreads) void k_line_select(SelectArgs g)
 {
-	__shared__ uint32_t red[kWaves];
+	__shared__ uint32_t red[2 * kWaves];
 	uint32_t L, lead;
 	const uint32_t lines = lines_of(g, L, lead);
 	const uint32_t words = (lines + 31) / 32;
-	const Share sh = share_of(words);
+	const Words sh = words_of(words);
 	uint32_t base = 0, total = 0;
 	if (WRITE) {
 		base = blocks_before(g.block_counts, red, total);
 		if (blockIdx.x == 0 && threadIdx.x == 0) {
-			const uint32_t tail = min(total + 1, g.cap - 1);
-			g.rel_out[0] = g.begin_out[0] = g.next_out[0] = (int32_t)total;
-			g.rel_out[tail] = g.begin_out[tail] = g.next_out[tail] = 0;
+			write_ends(g.rel_out, g.cap, total, 0);
+			write_ends(g.begin_out, g.cap, total, 0);
+			write_ends(g.next_out, g.cap, total, 0);
 		}
 	}
 	uint32_t kept = 0;
@@ -334,8 +266,6 @@ __global__ __launch_bounds__(kThreads) void k_line_select(SelectArgs g)
 			g.block_counts[blockIdx.x] = (int32_t)kept;
 	}
 }
-
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 size_t mask_words(size_t n) { return ((n + 15) / 16 + 3) / 4; }
 
@@ -448,7 +378,7 @@ extern "C" int acm_line_select_async(const int32_t *d_line_start, size_t capacit
 	g.rel_out = d_rel_out;
 	g.begin_out = d_begin_out;
 	g.next_out = d_next_out;
-	g.cap = (uint32_t)(out_capacity > 0xFFFFFFFFul ? 0xFFFFFFFFul : out_capacity);
+	g.cap = clamp_cap(out_capacity);
 	g.block_counts = (int32_t *)d_workspace;
 	g.flags = (uint32_t *)((char *)d_workspace + kCountBytes);
 	ACM_HIP_TRY(hipMemsetAsync(g.flags, 0, (capacity / 32 + 1) * 4, s));

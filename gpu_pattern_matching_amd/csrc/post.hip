@@ -19,6 +19,7 @@
 
 #include "acm_internal.h"
 #include "device_dfa.h"
+#include "record_pass.h"
 
 namespace {
 
@@ -365,13 +366,8 @@ __global__ void k_expand_scatter(const int32_t *state_plane, const int32_t *off_
 	if (i == 0) {   // header and trailer cells, as the scan writes them
 		const uint32_t t = (uint32_t)*total;
 		const int32_t last = state_plane[1 + m];   // trailer of the input (a scan with more records than cells clamps it there)
-		uint32_t tail = t + 1;
-		if (tail > out_capacity - 1)
-			tail = out_capacity - 1;
-		pat_out[0] = (int32_t)t;
-		off_out[0] = (int32_t)t;
-		pat_out[tail] = last;
-		off_out[tail] = last;
+		acm_rp::write_ends(pat_out, out_capacity, t, last);
+		acm_rp::write_ends(off_out, out_capacity, t, last);
 	}
 }
 
@@ -402,7 +398,7 @@ extern "C" int acm_expand_matches_async(const acm_dfa *d, const int32_t *d_state
 	int32_t *counts = (int32_t *)ws, *cells = (int32_t *)(ws + plane), *total = (int32_t *)(ws + 2 * plane);
 	void *scan_ws = ws + 2 * plane + 256;
 	const uint32_t n = (uint32_t)max_records, blocks = (n + 255) / 256;
-	const uint32_t cap = (uint32_t)(out_capacity > 0xFFFFFFFFul ? 0xFFFFFFFFul : out_capacity);
+	const uint32_t cap = acm_rp::clamp_cap(out_capacity);
 	hipLaunchKernelGGL(k_expand_count, dim3(blocks), dim3(256), 0, s, d_state_plane, n, d->d_list_len, counts);
 	ACM_HIP_TRY(hipGetLastError());
 	const int rc = acm_exclusive_scan_i32(counts, cells, n, total, scan_ws,

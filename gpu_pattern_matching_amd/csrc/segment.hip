@@ -11,27 +11,20 @@
 // costs per record, not per text byte, and the clamp only does work within max_pattern_len bytes of
 // a segment start.
 //
-// Two launches over a fixed grid (every block owns a contiguous run of 1024-record tiles):
+// The pass is a two-launch ordered write over a fixed grid (record_pass.h):
 //   k_segment<false>  clamps every record and writes the number its block keeps
-//   k_segment<true>   clamps again, sums the counts of the blocks in front of its own, and writes
-//                     the kept records in position order: ranks inside a wave from a 64-bit ballot
-//                     and mbcnt, across the block's waves from LDS, no atomics for ordering
-// The segment of a record is found in the slice of the start array that its tile spans, staged in
-// LDS (a wave-wide 64-ary search finds the slice's bounds); a tile whose slice is larger than the
-// LDS budget (many empty segments) searches the start array in global memory instead.
+//   k_segment<true>   clamps again and writes the kept records in position order, ranks inside a wave
+//                     from a 64-bit ballot
+// The segment of a record is found in the slice of the start array that its tile spans (stage_slice).
 #include <hip/hip_runtime.h>
 
 #include "acm_internal.h"
 #include "device_dfa.h"
+#include "record_pass.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kPer = 4;                      // records per thread per tile
-constexpr uint32_t kTile = kThreads * kPer;  // 1024
-constexpr uint32_t kSliceMax = 2048;         // segment starts staged in LDS per tile (8 KiB)
-constexpr uint32_t kMaxBlocks = 1024;
+using namespace acm_rp;
 
 struct SegArgs {
 	const int32_t *state_plane, *off_plane;
@@ -50,49 +43,6 @@ struct SegArgs {
 	int32_t *block_counts;       // [gridDim.x]
 };
 
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0)); }
-
-__device__ __forceinline__ uint32_t mbcnt64(uint64_t m)
-{
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-}
-
-// Number of starts <= key (so the segment is that minus one), found by the whole wave: 64 samples per
-// step, each step shrinks the range 64-fold (three steps for 240 k segments).  Every lane passes the
-// same key and gets the same answer.
-__device__ uint32_t wave_upper_bound(const int32_t *a, uint32_t n, int64_t key)
-{
-	const uint32_t lane = lane_id();
-	uint32_t lo = 0, hi = n;   // the answer lies in [lo, hi]
-	while (lo < hi) {
-		const uint32_t step = (hi - lo + 63) / 64;
-		const uint32_t idx = lo + lane * step;
-		const bool le = idx < hi && (int64_t)a[idx] <= key;
-		const uint32_t c = (uint32_t)__popcll(__ballot(le));   // a prefix of the lanes: a is sorted
-		if (step == 1)
-			return lo + c;
-		if (c == 0)
-			return lo;
-		const uint32_t nlo = lo + (c - 1) * step + 1, nhi = min(hi, lo + c * step);
-		lo = nlo;
-		hi = nhi;
-	}
-	return lo;
-}
-
-__device__ __forceinline__ uint32_t upper_bound_i32(const int32_t *a, uint32_t n, int32_t key)
-{
-	uint32_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (a[mid] <= key)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
 // the first state on s's fail chain whose depth is <= b
 __device__ __forceinline__ uint32_t clamp_state(const SegArgs &g, uint32_t s, int64_t b)
 {
@@ -106,23 +56,16 @@ __device__ __forceinline__ uint32_t clamp_state(const SegArgs &g, uint32_t s, in
 	return s;
 }
 
-struct Staged {
-	uint32_t k0, len;   // starts [k0, k0 + len) of the tile are in LDS (len <= kSliceMax), else global
-	bool in_lds;
-};
-
 // One record: its segment, its clamped state, whether it survives and the value it reports.
 __device__ __forceinline__ bool one_record(const SegArgs &g, int32_t o, uint32_t s, const int32_t *slice,
-    const Staged &st, int32_t &val, int32_t &seg)
+    const Slice &st, int32_t &val, int32_t &seg)
 {
 	if (s >= g.num_states)   // not the planes of a STATE scan: nothing to report
 		return false;
 	const uint32_t s_in = s;
 	int32_t k = -1;
 	if (g.segments) {
-		const uint32_t ub = st.in_lds ? st.k0 + upper_bound_i32(slice, st.len, o)
-		                              : upper_bound_i32(g.seg_start, g.segments, o);
-		k = (int32_t)ub - 1;
+		k = (int32_t)starts_le(st, slice, g.seg_start, g.segments, o) - 1;
 		if (k >= 0)
 			s = clamp_state(g, s, (int64_t)o - g.seg_start[k] + 1);
 	}
@@ -139,38 +82,19 @@ __global__ __launch_bounds__(kThreads) void k_segment(SegArgs g)
 	__shared__ int32_t slice[kSliceMax];
 	__shared__ uint32_t bounds[2];
 	__shared__ uint32_t wave_cnt[kPer * kWaves];
-	__shared__ uint32_t red[kWaves * 2];
+	__shared__ uint32_t red[2 * kWaves];
 
-	const uint32_t tid = threadIdx.x, wave = tid / 64, lane = lane_id();
+	const uint32_t tid = threadIdx.x, lane = lane_id();
 	const uint32_t m = min((uint32_t)g.state_plane[0], g.max_records);
-	const uint32_t tiles = (m + kTile - 1) / kTile, per = (tiles + gridDim.x - 1) / gridDim.x;
-	const uint32_t t_begin = min(blockIdx.x * per, tiles), t_end = min(t_begin + per, tiles);
+	const Share sh = share_of((m + kTile - 1) / kTile);
 
-	if (WRITE && t_begin == t_end && blockIdx.x != 0)   // nothing to write (a batch with few records)
+	if (WRITE && sh.t_begin == sh.t_end && blockIdx.x != 0)   // nothing to write (a batch with few records)
 		return;
 	uint32_t base = 0;   // WRITE: records kept by the blocks in front of this one
 	if (WRITE) {
-		uint32_t before = 0, all = 0;
-		for (uint32_t j = tid; j < gridDim.x; j += kThreads) {
-			const uint32_t c = (uint32_t)g.block_counts[j];
-			all += c;
-			before += j < blockIdx.x ? c : 0;
-		}
-		for (int o = 32; o > 0; o >>= 1) {
-			before += __shfl_xor(before, o, 64);
-			all += __shfl_xor(all, o, 64);
-		}
-		if (lane == 0) {
-			red[wave] = before;
-			red[kWaves + wave] = all;
-		}
-		__syncthreads();
-		uint32_t total = 0;
-		for (int w = 0; w < kWaves; w++) {
-			base += red[w];
-			total += red[kWaves + w];
-		}
-		if (blockIdx.x == 0 && wave == 0) {   // header and trailer cells, as the scan writes them
+		uint32_t total;
+		base = blocks_before(g.block_counts, red, total);
+		if (blockIdx.x == 0 && tid < 64) {   // the trailer: the input's, clamped at the text's end
 			uint32_t last = (uint32_t)g.state_plane[1 + m];
 			if (g.segments && last < g.num_states) {
 				const uint32_t ub = wave_upper_bound(g.seg_start, g.segments, g.text_end);
@@ -178,21 +102,16 @@ __global__ __launch_bounds__(kThreads) void k_segment(SegArgs g)
 					last = clamp_state(g, last, g.text_end - g.seg_start[ub - 1]);
 			}
 			if (lane == 0) {
-				const uint32_t tail = min(total + 1, g.cap - 1);
-				g.pat_out[0] = (int32_t)total;
-				g.off_out[0] = (int32_t)total;
-				g.pat_out[tail] = (int32_t)last;
-				g.off_out[tail] = (int32_t)last;
-				if (g.seg_out) {
-					g.seg_out[0] = (int32_t)total;
-					g.seg_out[tail] = (int32_t)last;
-				}
+				write_ends(g.pat_out, g.cap, total, (int32_t)last);
+				write_ends(g.off_out, g.cap, total, (int32_t)last);
+				if (g.seg_out)
+					write_ends(g.seg_out, g.cap, total, (int32_t)last);
 			}
 		}
 	}
 
 	uint32_t kept = 0;
-	for (uint32_t t = t_begin; t < t_end; t++) {
+	for (uint32_t t = sh.t_begin; t < sh.t_end; t++) {
 		const uint32_t r0 = t * kTile, r1 = min(r0 + kTile, m);
 		int32_t off[kPer];
 		uint32_t state[kPer];
@@ -202,24 +121,11 @@ __global__ __launch_bounds__(kThreads) void k_segment(SegArgs g)
 			off[q] = i < r1 ? g.off_plane[1 + i] : 0;
 			state[q] = i < r1 ? (uint32_t)g.state_plane[1 + i] : 0;
 		}
-		Staged st{ 0, 0, false };
+		Slice st{};
 		if (g.segments) {
-			__syncthreads();   // (the slice of the previous tile is no longer read)
-			if (wave < 2) {
-				const uint32_t ub = wave_upper_bound(g.seg_start, g.segments,
-				    (int64_t)g.off_plane[1 + (wave == 0 ? r0 : r1 - 1)]);
-				if (lane == 0)
-					bounds[wave] = ub;
-			}
-			__syncthreads();
-			st.k0 = bounds[0] > 0 ? bounds[0] - 1 : 0;
-			st.len = bounds[1] - st.k0;
-			st.in_lds = st.len <= kSliceMax;
-			if (st.in_lds) {
-				for (uint32_t j = tid; j < st.len; j += kThreads)
-					slice[j] = g.seg_start[st.k0 + j];
+			st = stage_slice(g.off_plane, r0, r1, g.seg_start, g.segments, slice, bounds);
+			if (st.in_lds)
 				__syncthreads();
-			}
 		}
 		bool keep[kPer];
 		int32_t val[kPer], seg[kPer];
@@ -231,28 +137,19 @@ __global__ __launch_bounds__(kThreads) void k_segment(SegArgs g)
 			seg[q] = -1;
 			keep[q] = i < r1 && one_record(g, off[q], state[q], slice, st, val[q], seg[q]);
 			mask[q] = __ballot(keep[q]);
+			kept += (uint32_t)__popcll(mask[q]);   // (of the wave)
 		}
-		if (!WRITE) {
-#pragma unroll
-			for (int q = 0; q < kPer; q++)
-				kept += (uint32_t)__popcll(mask[q]);
+		if (!WRITE)
 			continue;
-		}
-		if (lane == 0)
+		uint32_t wave_total[kPer];
 #pragma unroll
-			for (int q = 0; q < kPer; q++)
-				wave_cnt[q * kWaves + wave] = (uint32_t)__popcll(mask[q]);
-		__syncthreads();
+		for (int q = 0; q < kPer; q++)
+			wave_total[q] = (uint32_t)__popcll(mask[q]);
+		tile_publish(wave_total, wave_cnt);
 		uint32_t tile_total = 0;
 #pragma unroll
 		for (int q = 0; q < kPer; q++) {
-			// record r0 + q * 256 + tid: behind every record of rows q' < q, then of waves w' < wave of row q
-			uint32_t before = base + tile_total;
-			for (uint32_t w = 0; w < (uint32_t)kWaves; w++)
-				before += w < wave ? wave_cnt[q * kWaves + w] : 0;
-			for (uint32_t w = 0; w < (uint32_t)kWaves; w++)
-				tile_total += wave_cnt[q * kWaves + w];
-			const uint32_t d = before + mbcnt64(mask[q]);
+			const uint32_t d = base + tile_row(wave_cnt, q, tile_total) + mbcnt64(mask[q]);
 			if (keep[q] && d + 2 < g.cap) {
 				g.pat_out[1 + d] = val[q];
 				g.off_out[1 + d] = off[q];
@@ -276,32 +173,19 @@ __global__ __launch_bounds__(kThreads) void k_segment(SegArgs g)
 			}
 		}
 		base += tile_total;
-		__syncthreads();   // (wave_cnt is rewritten by the next tile)
 	}
 	if (!WRITE) {
-		if (lane == 0)
-			red[wave] = kept;
-		__syncthreads();
-		if (tid == 0) {
-			uint32_t sum = 0;
-			for (int w = 0; w < kWaves; w++)
-				sum += red[w];
-			g.block_counts[blockIdx.x] = (int32_t)sum;
-		}
+		kept = block_sum_of_waves(kept, red);
+		if (tid == 0)
+			g.block_counts[blockIdx.x] = (int32_t)kept;
 	}
-}
-
-uint32_t grid_for(size_t max_records)
-{
-	const size_t tiles = (max_records + kTile - 1) / kTile;
-	return (uint32_t)std::max<size_t>(1, std::min<size_t>(tiles, kMaxBlocks));
 }
 
 }  // namespace
 
 extern "C" size_t acm_segment_workspace_bytes(size_t max_records)
 {
-	return ((size_t)grid_for(max_records) * sizeof(int32_t) + 255) & ~(size_t)255;
+	return block_counts_bytes(grid_for(max_records));
 }
 
 extern "C" int acm_segment_matches_async(const acm_dfa *d, const int32_t *d_state_plane, const int32_t *d_off_plane,
@@ -337,7 +221,7 @@ extern "C" int acm_segment_matches_async(const acm_dfa *d, const int32_t *d_stat
 	g.pat_out = d_pat_out;
 	g.off_out = d_off_out;
 	g.seg_out = d_seg_out;
-	g.cap = (uint32_t)(out_capacity > 0xFFFFFFFFul ? 0xFFFFFFFFul : out_capacity);
+	g.cap = clamp_cap(out_capacity);
 	g.seg_counts = segments ? d_seg_counts : nullptr;
 	g.block_counts = (int32_t *)d_workspace;
 	const uint32_t blocks = grid_for(max_records);

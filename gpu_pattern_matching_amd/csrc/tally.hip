@@ -4,14 +4,14 @@
 // or every entry of that list (ACM_TALLY_ALL_PATTERNS).  Its class is class_of[pattern] (the pattern
 // itself without a map), its segment the last start <= its offset.  Sums are integers and a tally keeps
 // no order, so one launch over the records does it (segment.hip and word.hip need two: count, write):
-//   k_tally   a fixed grid, every block owns a contiguous run of 1024-record tiles
+//   k_tally   the fixed grid of record_pass.h, every block owns a contiguous run of 1024-record tiles
 // in front of it hipMemsetAsync zeroes the outputs that are written whole; everything the kernel adds to
 // global memory is an atomic add, so blocks and tiles need no order among themselves.
 //
 // Class totals: num_classes <= kLdsClasses: one uint32 bin per class in LDS per block (ds atomics), one
 // 64-bit global atomic per non-zero bin when the block is done.  Above that: a global atomic per entry,
 // lanes of a wave that share a class merged into one add first.
-// Segment rows: the slice of the start array a tile spans is found and staged as in segment.hip; the
+// Segment rows: the slice of the start array a tile spans is found and staged (record_pass.h); the
 // rows a tile touches are contiguous (records and starts are both in offset order), so when rows x
 // classes <= kRowCells they are summed in LDS and added to global memory once per tile (rows at a tile's
 // edges are shared with its neighbours: atomics only).  Otherwise a global atomic per entry, merged per
@@ -26,16 +26,14 @@
 
 #include "acm_internal.h"
 #include "device_dfa.h"
+#include "record_pass.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPer = 4;                      // records per thread per tile
-constexpr uint32_t kTile = kThreads * kPer;  // 1024
-constexpr uint32_t kSliceMax = 2048;         // segment starts staged in LDS per tile (8 KiB)
+using namespace acm_rp;
+
 constexpr uint32_t kRowCells = 2048;         // (segment, class) cells of a tile summed in LDS (8 KiB)
 constexpr uint32_t kLdsClasses = 5632;       // class bins per block in LDS (22 KiB)
-constexpr uint32_t kMaxBlocks = 1024;
 constexpr size_t kWorkspace = 256;           // the pass needs no scratch; the query keeps its siblings' shape
 
 struct TallyArgs {
@@ -52,43 +50,6 @@ struct TallyArgs {
 	int32_t *seg_class, *lead;
 	uint32_t flush_tiles;        // tiles a block may sum into its uint32 bins before it must flush them
 };
-
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0)); }
-
-// Number of starts <= key, found by the whole wave (segment.hip): 64 samples per step, each step
-// shrinks the range 64-fold.  Every lane passes the same key and gets the same answer, in [0, n].
-__device__ uint32_t wave_upper_bound(const int32_t *a, uint32_t n, int64_t key)
-{
-	const uint32_t lane = lane_id();
-	uint32_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint32_t step = (hi - lo + 63) / 64;
-		const uint32_t idx = lo + lane * step;
-		const bool le = idx < hi && (int64_t)a[idx] <= key;
-		const uint32_t c = (uint32_t)__popcll(__ballot(le));
-		if (step == 1)
-			return lo + c;
-		if (c == 0)
-			return lo;
-		const uint32_t nlo = lo + (c - 1) * step + 1, nhi = min(hi, lo + c * step);
-		lo = nlo;
-		hi = nhi;
-	}
-	return lo;
-}
-
-__device__ __forceinline__ uint32_t upper_bound_i32(const int32_t *a, uint32_t n, int32_t key)
-{
-	uint32_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (a[mid] <= key)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
 
 // One add per distinct key among the active lanes of the wave: the first lane that holds a key adds the
 // number of lanes that hold it.  Called by every lane of the wave (active or not).
@@ -116,11 +77,10 @@ __global__ __launch_bounds__(kThreads) void k_tally(TallyArgs g)
 	__shared__ uint32_t bins[kLdsClasses];
 	__shared__ uint32_t bounds[2];
 
-	const uint32_t tid = threadIdx.x, wave = tid / 64, lane = lane_id();
+	const uint32_t tid = threadIdx.x;
 	const uint32_t m = min((uint32_t)g.pat_plane[0], g.max_records);
-	const uint32_t tiles = (m + kTile - 1) / kTile, per = (tiles + gridDim.x - 1) / gridDim.x;
-	const uint32_t t_begin = min(blockIdx.x * per, tiles), t_end = min(t_begin + per, tiles);
-	if (t_begin == t_end)   // a batch with few records: most of the grid has nothing to do
+	const Share sh = share_of((m + kTile - 1) / kTile);
+	if (sh.t_begin == sh.t_end)   // a batch with few records: most of the grid has nothing to do
 		return;
 	const uint32_t C = g.num_classes;
 	const bool lds_bins = C <= kLdsClasses;
@@ -141,7 +101,7 @@ __global__ __launch_bounds__(kThreads) void k_tally(TallyArgs g)
 	};
 
 	uint32_t since_flush = 0;
-	for (uint32_t t = t_begin; t < t_end; t++) {
+	for (uint32_t t = sh.t_begin; t < sh.t_end; t++) {
 		const uint32_t r0 = t * kTile, r1 = min(r0 + kTile, m);
 		int32_t off[kPer];
 		uint32_t cell[kPer];
@@ -151,31 +111,20 @@ __global__ __launch_bounds__(kThreads) void k_tally(TallyArgs g)
 			off[q] = i < r1 ? g.off_plane[1 + i] : 0;
 			cell[q] = i < r1 ? (uint32_t)g.pat_plane[1 + i] : 0;
 		}
-		uint32_t k0 = 0, len = 0, n_rows = 0, row_cells = 0;
+		Slice st{};
+		uint32_t n_rows = 0, row_cells = 0;
 		int32_t k_first = 0;
-		bool slice_in_lds = false, rows_in_lds = false;
+		bool rows_in_lds = false;
 		if (want_rows) {
-			__syncthreads();   // (the slice and the rows of the previous tile are no longer read)
-			if (wave < 2) {
-				const uint32_t ub = wave_upper_bound(g.seg_start, g.segments,
-				    (int64_t)g.off_plane[1 + (wave == 0 ? r0 : r1 - 1)]);
-				if (lane == 0)
-					bounds[wave] = ub;
-			}
-			__syncthreads();
-			k0 = bounds[0] > 0 ? bounds[0] - 1 : 0;
-			len = bounds[1] - k0;
-			slice_in_lds = len <= kSliceMax;
-			// rows k_first .. bounds[1] - 1 (row -1: the lead)
-			k_first = (int32_t)bounds[0] - 1;
-			if (bounds[1] >= bounds[0]) {
-				n_rows = bounds[1] - bounds[0] + 1;
+			// (behind stage_slice's first barrier the rows of the previous tile are no longer read either)
+			st = stage_slice(g.off_plane, r0, r1, g.seg_start, g.segments, slice, bounds);
+			// rows k_first .. st.ub1 - 1 (row -1: the lead)
+			k_first = (int32_t)st.ub0 - 1;
+			if (st.ub1 >= st.ub0) {
+				n_rows = st.ub1 - st.ub0 + 1;
 				rows_in_lds = (uint64_t)n_rows * C <= kRowCells;
 			}
 			row_cells = rows_in_lds ? n_rows * C : 0;
-			if (slice_in_lds)
-				for (uint32_t j = tid; j < len; j += kThreads)
-					slice[j] = g.seg_start[k0 + j];
 			for (uint32_t j = tid; j < row_cells; j += kThreads)
 				rows[j] = 0;
 			__syncthreads();
@@ -199,11 +148,8 @@ __global__ __launch_bounds__(kThreads) void k_tally(TallyArgs g)
 				}
 			}
 			int32_t k = -1;
-			if (want_rows && cnt) {
-				const uint32_t ub = slice_in_lds ? k0 + upper_bound_i32(slice, len, off[q])
-				                                 : upper_bound_i32(g.seg_start, g.segments, off[q]);
-				k = (int32_t)ub - 1;   // in [-1, segments - 1] whatever the offset is
-			}
+			if (want_rows && cnt)   // in [-1, segments - 1] whatever the offset is
+				k = (int32_t)starts_le(st, slice, g.seg_start, g.segments, off[q]) - 1;
 			for (uint32_t j = 0; __ballot(j < cnt); j++) {
 				bool ok = j < cnt;
 				uint32_t cls = 0;
@@ -258,7 +204,7 @@ __global__ __launch_bounds__(kThreads) void k_tally(TallyArgs g)
 				}
 			}
 		}
-		if (lds_bins && ++since_flush >= g.flush_tiles && t + 1 < t_end) {   // (uniform over the block)
+		if (lds_bins && ++since_flush >= g.flush_tiles && t + 1 < sh.t_end) {   // (uniform over the block)
 			__syncthreads();
 			flush_bins();
 			__syncthreads();
@@ -269,12 +215,6 @@ __global__ __launch_bounds__(kThreads) void k_tally(TallyArgs g)
 		__syncthreads();
 		flush_bins();
 	}
-}
-
-uint32_t grid_for(size_t max_records)
-{
-	const size_t tiles = (max_records + kTile - 1) / kTile;
-	return (uint32_t)std::max<size_t>(1, std::min<size_t>(tiles, kMaxBlocks));
 }
 
 }  // namespace

@@ -14,26 +14,20 @@
 // (one length load and one text-byte gather per entry) as far as the head form needs, the first
 // word-bounded entry, or whole for the all form.
 //
-// Two launches over a fixed grid (every block owns a contiguous run of 1024-record tiles), as in
-// segment.hip:
-//   k_word<false>  counts the records every block writes (head: 0 or 1 per input record; all: the
+// The pass is a two-launch ordered write over a fixed grid (record_pass.h):
+//   k_word<false>  counts the cells every block writes (head: 0 or 1 per input record; all: the
 //                  word-bounded entries of the list)
-//   k_word<true>   counts again, sums the counts of the blocks in front of its own, and writes in
-//                  position order: a wave's ranks from a 64-lane prefix sum, across the block's
-//                  waves from LDS, no atomics.  Block 0 also writes the header, the trailer and the
-//                  tail bytes a streaming caller hands to its next call.
+//   k_word<true>   counts again and writes in position order.  Block 0 also writes the tail bytes a
+//                  streaming caller hands to its next call.
 #include <hip/hip_runtime.h>
 
 #include "acm_internal.h"
 #include "device_dfa.h"
+#include "record_pass.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kPer = 4;                      // records per thread per tile
-constexpr uint32_t kTile = kThreads * kPer;  // 1024
-constexpr uint32_t kMaxBlocks = 1024;
+using namespace acm_rp;
 
 struct WordArgs {
 	const int32_t *state_plane, *off_plane;
@@ -58,8 +52,6 @@ struct WordArgs {
 	int32_t *block_counts;       // [gridDim.x]
 };
 
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0)); }
-
 // the byte at stream offset p, or -1 where there is none: in front of the bytes the caller gave (a
 // text start), at text_end when next_byte is -1, and beyond text_end.  Never reads outside
 // [text_origin, text_end) of the text or [0, before_len) of before.
@@ -77,19 +69,6 @@ __device__ __forceinline__ int byte_at(const WordArgs &g, int64_t p)
 __device__ __forceinline__ bool is_word(const uint32_t *wset, int c)
 {
 	return c >= 0 && ((wset[c >> 5] >> (c & 31)) & 1u);
-}
-
-__device__ __forceinline__ uint32_t upper_bound_i32(const int32_t *a, uint32_t n, int64_t key)
-{
-	uint32_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if ((int64_t)a[mid] <= key)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
 }
 
 // One record: the number of entries it writes (head: 0 or 1) and, for the head form, the pattern.
@@ -143,48 +122,26 @@ __global__ __launch_bounds__(kThreads) void k_word(WordArgs g)
 {
 	__shared__ uint32_t wset[8];
 	__shared__ uint32_t wave_cnt[kPer * kWaves];
-	__shared__ uint32_t red[kWaves * 2];
+	__shared__ uint32_t red[2 * kWaves];
 
-	const uint32_t tid = threadIdx.x, wave = tid / 64, lane = lane_id();
+	const uint32_t tid = threadIdx.x;
 	if (tid < 8)
 		wset[tid] = g.wset[tid];
 	const uint32_t m = min((uint32_t)g.state_plane[0], g.max_records);
-	const uint32_t tiles = (m + kTile - 1) / kTile, per = (tiles + gridDim.x - 1) / gridDim.x;
-	const uint32_t t_begin = min(blockIdx.x * per, tiles), t_end = min(t_begin + per, tiles);
+	const Share sh = share_of((m + kTile - 1) / kTile);
 	__syncthreads();
 
-	if (WRITE && t_begin == t_end && blockIdx.x != 0)   // nothing to write (a batch with few records)
+	if (WRITE && sh.t_begin == sh.t_end && blockIdx.x != 0)   // nothing to write (a batch with few records)
 		return;
-	uint32_t base = 0;   // WRITE: records written by the blocks in front of this one
+	uint32_t base = 0;   // WRITE: cells written by the blocks in front of this one
 	if (WRITE) {
-		uint32_t before = 0, all = 0;
-		for (uint32_t j = tid; j < gridDim.x; j += kThreads) {
-			const uint32_t c = (uint32_t)g.block_counts[j];
-			all += c;
-			before += j < blockIdx.x ? c : 0;
-		}
-		for (int o = 32; o > 0; o >>= 1) {
-			before += __shfl_xor(before, o, 64);
-			all += __shfl_xor(all, o, 64);
-		}
-		if (lane == 0) {
-			red[wave] = before;
-			red[kWaves + wave] = all;
-		}
-		__syncthreads();
-		uint32_t total = 0;
-		for (int w = 0; w < kWaves; w++) {
-			base += red[w];
-			total += red[kWaves + w];
-		}
+		uint32_t total;
+		base = blocks_before(g.block_counts, red, total);
 		if (blockIdx.x == 0) {
-			if (tid == 0) {   // header and trailer cells, as the scan writes them; the trailer is the input's
-				const int32_t last = g.state_plane[1 + m];
-				const uint32_t tail = min(total + 1, g.cap - 1);
-				g.pat_out[0] = (int32_t)total;
-				g.off_out[0] = (int32_t)total;
-				g.pat_out[tail] = last;
-				g.off_out[tail] = last;
+			if (tid == 0) {
+				const int32_t last = g.state_plane[1 + m];   // the trailer is the input's
+				write_ends(g.pat_out, g.cap, total, last);
+				write_ends(g.off_out, g.cap, total, last);
 			}
 			if (g.tail_out)   // the last tail_len bytes of before ++ text, for the next piece's before
 				for (uint32_t j = tid; j < g.tail_len; j += kThreads)
@@ -193,7 +150,7 @@ __global__ __launch_bounds__(kThreads) void k_word(WordArgs g)
 	}
 
 	uint32_t kept = 0;
-	for (uint32_t t = t_begin; t < t_end; t++) {
+	for (uint32_t t = sh.t_begin; t < sh.t_end; t++) {
 		const uint32_t r0 = t * kTile, r1 = min(r0 + kTile, m);
 		int32_t off[kPer];
 		uint32_t state[kPer];
@@ -209,38 +166,21 @@ __global__ __launch_bounds__(kThreads) void k_word(WordArgs g)
 		for (int q = 0; q < kPer; q++) {
 			head[q] = 0;
 			cnt[q] = one_record<false>(g, wset, off[q], state[q], 0, head[q]);
+			kept += cnt[q];
 		}
-		if (!WRITE) {
-#pragma unroll
-			for (int q = 0; q < kPer; q++)
-				kept += cnt[q];
+		if (!WRITE)
 			continue;
-		}
-		// inclusive prefix sums over the wave's lanes, one per row
-		uint32_t incl[kPer];
+		uint32_t incl[kPer], wave_total[kPer];
 #pragma unroll
 		for (int q = 0; q < kPer; q++) {
-			incl[q] = cnt[q];
-			for (int k = 1; k < 64; k <<= 1) {
-				const uint32_t v = __shfl_up(incl[q], k, 64);
-				incl[q] += lane >= (uint32_t)k ? v : 0u;
-			}
+			incl[q] = wave_inclusive(cnt[q]);
+			wave_total[q] = (uint32_t)__shfl((int)incl[q], 63, 64);
 		}
-		if (lane == 63)
-#pragma unroll
-			for (int q = 0; q < kPer; q++)
-				wave_cnt[q * kWaves + wave] = incl[q];
-		__syncthreads();
+		tile_publish(wave_total, wave_cnt);
 		uint32_t tile_total = 0;
 #pragma unroll
 		for (int q = 0; q < kPer; q++) {
-			// record r0 + q * 256 + tid: behind every record of rows q' < q, then of waves w' < wave of row q
-			uint32_t before = base + tile_total;
-			for (uint32_t w = 0; w < (uint32_t)kWaves; w++)
-				before += w < wave ? wave_cnt[q * kWaves + w] : 0;
-			for (uint32_t w = 0; w < (uint32_t)kWaves; w++)
-				tile_total += wave_cnt[q * kWaves + w];
-			const uint32_t d = before + incl[q] - cnt[q];
+			const uint32_t d = base + tile_row(wave_cnt, q, tile_total) + incl[q] - cnt[q];
 			if (cnt[q]) {
 				if (!g.all) {
 					if (d + 2 < g.cap) {
@@ -254,34 +194,19 @@ __global__ __launch_bounds__(kThreads) void k_word(WordArgs g)
 			}
 		}
 		base += tile_total;
-		__syncthreads();   // (wave_cnt is rewritten by the next tile)
 	}
 	if (!WRITE) {
-		for (int o = 32; o > 0; o >>= 1)
-			kept += __shfl_xor(kept, o, 64);
-		if (lane == 0)
-			red[wave] = kept;
-		__syncthreads();
-		if (tid == 0) {
-			uint32_t sum = 0;
-			for (int w = 0; w < kWaves; w++)
-				sum += red[w];
-			g.block_counts[blockIdx.x] = (int32_t)sum;
-		}
+		kept = block_sum(kept, red);
+		if (tid == 0)
+			g.block_counts[blockIdx.x] = (int32_t)kept;
 	}
-}
-
-uint32_t grid_for(size_t max_records)
-{
-	const size_t tiles = (max_records + kTile - 1) / kTile;
-	return (uint32_t)std::max<size_t>(1, std::min<size_t>(tiles, kMaxBlocks));
 }
 
 }  // namespace
 
 extern "C" size_t acm_word_workspace_bytes(size_t max_records)
 {
-	return ((size_t)grid_for(max_records) * sizeof(int32_t) + 255) & ~(size_t)255;
+	return block_counts_bytes(grid_for(max_records));
 }
 
 extern "C" int acm_word_matches_async(const acm_dfa *d, const int32_t *d_state_plane, const int32_t *d_off_plane,
@@ -333,7 +258,7 @@ extern "C" int acm_word_matches_async(const acm_dfa *d, const int32_t *d_state_p
 	g.num_patterns = d->num_patterns;
 	g.pat_out = d_pat_out;
 	g.off_out = d_off_out;
-	g.cap = (uint32_t)(out_capacity > 0xFFFFFFFFul ? 0xFFFFFFFFul : out_capacity);
+	g.cap = clamp_cap(out_capacity);
 	g.tail_out = (uint8_t *)d_tail_out;
 	g.tail_len = (uint32_t)std::min<int64_t>((int64_t)d->max_pattern_len, (int64_t)before_len + (text_end - text_origin));
 	g.block_counts = (int32_t *)d_workspace;

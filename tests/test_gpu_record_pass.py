@@ -1,0 +1,323 @@
+"""The record-pass core (csrc/record_pass.h) through every pass that uses it -- segment, word, tally, line
+select, expand -- at the record counts where tile ownership, ordered ranks and the header / trailer cells
+can go wrong.  Planes are built by hand in numpy; expected outputs are plain numpy and the models of the
+suite, never the library.
+
+The automaton is {a, ba, cba}: the state of "cba" lists three patterns, of "ba" two, of "a" one.  Record i
+ends at offset 4 i + 3 and holds one of those states or (a quarter of the records) a value that is no state
+and is dropped by segment, word and tally: the kept records are an arbitrary subset, known on the host.
+A record's kind is its longest pattern's length; its match list holds that pattern and every shorter one,
+in the oracle's order.
+Starts are multiples of 4, so every record lies 4 bytes or more into its segment and no state is clamped."""
+import numpy as np
+import pytest
+
+import line_model
+import orc
+import poison
+import tally_model
+from gpu_pattern_matching_amd import Automaton, DeviceArray, Matcher, _lib
+
+pytestmark = pytest.mark.gpu
+
+PATS = [b"a", b"ba", b"cba"]
+NO_STATE = 0x7FFFFF00
+WORD = b"x"                                  # the word set: every other byte bounds a word
+COUNTS = [0, 1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2047, 2049]
+BIG = 1024 * 1024 + 1025                     # some blocks own two tiles, the last tile is partial
+P = poison.PLANE_POISON
+PV = poison.cell(P)
+
+
+class Env:
+    def __init__(self):
+        a = Automaton()
+        for p in PATS:
+            a.add(p)
+        a.compile()
+        self.m = Matcher(a, 0, max_text=4096)
+        self.num_states = a.num_states
+        o = orc.Oracle()
+        for i, p in enumerate(PATS):
+            o.add(p, i)
+        o.compile()
+        self.state = {k: int(o.scan(PATS[k - 1])[2]) for k in (1, 2, 3)}   # kind -> state
+        self.lists = np.full((4, 3), -1, dtype=np.int32)                     # [kind, j] -> pattern
+        for k in (1, 2, 3):
+            lst = o.match_list(self.state[k])
+            assert sorted(lst) == list(range(k))
+            self.lists[k, :k] = lst
+        self.cache = {}
+
+    def planes(self, m, valid_only=False):
+        """(kinds, offsets, host state plane, device state plane, device offset plane, text) of m records"""
+        key = (m, valid_only)
+        if key not in self.cache:
+            if m >= BIG:
+                self.cache = {k: v for k, v in self.cache.items() if k[0] < BIG}
+            rng = np.random.default_rng(1000 + m)
+            kind = rng.integers(1 if valid_only else 0, 4, m)
+            off = (np.arange(m, dtype=np.int64) * 4 + 3).astype(np.int32)
+            lut = np.array([NO_STATE, self.state[1], self.state[2], self.state[3]], dtype=np.int32)
+            sp = np.concatenate([[m], lut[kind], [self.state[1]]]).astype(np.int32)
+            op = np.concatenate([[m], off, [self.state[1]]]).astype(np.int32)
+            text = rng.choice(np.frombuffer(b" x", dtype=np.uint8), 4 * m + 4)
+            for k in (1, 2, 3):   # the bytes of the record's longest pattern end at its offset
+                sel = off[kind == k].astype(np.int64)
+                for j, c in enumerate(PATS[k - 1][::-1]):
+                    text[sel - j] = c
+            self.cache[key] = (kind, off, sp, DeviceArray.from_numpy(sp), DeviceArray.from_numpy(op), text)
+        return self.cache[key]
+
+
+@pytest.fixture(scope="module")
+def env(gpu):
+    e = Env()
+    yield e
+    e.m.close()
+
+
+def max_records_of(m):
+    return sorted({max(m - 1, 0), m, m + 5})
+
+
+def caps_of(total):
+    """total + 2 == cap, total + 1 == cap, total >= cap; and room to spare"""
+    return sorted({max(total + 2, 2), max(total + 1, 2), max(total, 2), total + 9})
+
+
+def entries(env, kind, off, all_patterns):
+    """(offsets, patterns, record index, index in the list) of the match-list entries of the valid records"""
+    n = np.where(kind > 0, kind if all_patterns else 1, 0)
+    rec = np.repeat(np.arange(kind.size), n)
+    j = np.arange(rec.size) - np.repeat(np.cumsum(n) - n, n)
+    return off[rec], env.lists[kind[rec], j], rec, j
+
+
+def out_planes(cap, count=2):
+    bufs = [DeviceArray(cap * 4) for _ in range(count)]
+    poison.fill(bufs, P)
+    return bufs
+
+
+def poisoned_ws(nbytes):
+    ws = DeviceArray(max(nbytes, 16))
+    ws.fill(0xA5)
+    return ws
+
+
+# ------------------------------------------------------------------ segment
+
+
+def check_segment(env, m, starts, report, with_seg, with_counts, max_records=None, cap=None):
+    kind, off, sp, d_sp, d_op, _ = env.planes(m)
+    mr = m if max_records is None else max_records
+    mm = min(m, mr)
+    keep = kind[:mm] > 0
+    S = len(starts)
+    seg = np.searchsorted(np.asarray(starts, dtype=np.int64), off[:mm], side="right").astype(np.int32) - 1
+    val = env.lists[kind[:mm], 0] if report == _lib.REPORT_HEAD else sp[1:1 + mm]
+    exp = (off[:mm][keep], val[keep].astype(np.int32), int(sp[1 + mm]))
+    total = int(keep.sum())
+    cap = total + 9 if cap is None else cap
+    pat, o, sg = out_planes(cap, 3)
+    d_st = DeviceArray.from_numpy(np.asarray(starts, dtype=np.int32), pad_to=0) if S else None
+    cnt = DeviceArray(max(S, 1) * 4)
+    cnt.fill(P)
+    nb = env.m.lib.acm_segment_workspace_bytes(mr)
+    ws = poisoned_ws(nb)
+    env.m.segment_async(d_sp, d_op, mr, d_st, S, 4 * m + 4, pat, o, cap, seg_out=sg if with_seg else None,
+                        seg_counts=cnt if with_counts and S else None, report=report, workspace=(ws.ptr, nb))
+    what = "segment m=%d max_records=%d cap=%d S=%d" % (m, mr, cap, S)
+    poison.check_planes(pat, o, cap, exp, what=what)
+    got = sg.to_numpy(np.int32, cap)
+    if with_seg:
+        stored = min(total, cap - 2)
+        assert got[0] == total and np.array_equal(got[1:1 + stored], seg[keep][:stored]), what
+        assert got[stored + 1] == exp[2] and np.all(got[stored + 2:] == PV), what
+    else:
+        assert np.all(got == PV), what
+    if with_counts and S:
+        k = seg[keep]
+        assert np.array_equal(cnt.to_numpy(np.int32, S), np.bincount(k[k >= 0], minlength=S)), what
+
+
+@pytest.mark.parametrize("m", COUNTS + [BIG])
+def test_segment(env, m):
+    starts = np.arange(0, 4 * m + 4, 12 * 4, dtype=np.int64)
+    for report in (_lib.REPORT_HEAD, _lib.REPORT_STATE):
+        for with_seg in (True, False):
+            for with_counts in (True, False):
+                check_segment(env, m, starts, report, with_seg, with_counts)
+    if m == BIG:
+        return
+    check_segment(env, m, [], _lib.REPORT_HEAD, True, False)
+    total = int((env.planes(m)[0] > 0).sum())
+    for mr in max_records_of(m):
+        check_segment(env, m, starts, _lib.REPORT_HEAD, True, True, max_records=mr)
+    for cap in caps_of(total):
+        check_segment(env, m, starts, _lib.REPORT_STATE, True, True, cap=cap)
+
+
+@pytest.mark.parametrize("slice_len", [0, 2048, 2049])
+def test_segment_slice(env, slice_len):
+    """the slice of starts that tile 0 spans: empty, exactly the LDS budget, one more (searched in global
+    memory); tile 1 of the 1025 records follows with a slice of its own"""
+    m = 1025
+    starts = [4 * m + 100] if slice_len == 0 else [0] + [4] * (slice_len - 1) + [4096]
+    check_segment(env, m, starts, _lib.REPORT_HEAD, True, True)
+
+
+# ------------------------------------------------------------------ word
+
+
+def word_expected(env, m, mr, all_patterns):
+    kind, off, sp, _, _, text = env.planes(m)
+    mm = min(m, mr)
+    eo, ep, rec, j = entries(env, kind[:mm], off[:mm], True)
+    is_w = text == WORD[0]
+    ok = ~is_w[eo.astype(np.int64) + 1] & ~is_w[eo.astype(np.int64) - (ep + 1)]   # pattern p is p + 1 bytes long
+    if not all_patterns:   # the first word-bounded entry of each record
+        seen = np.zeros(kind.size, dtype=bool)
+        pick = np.zeros(rec.size, dtype=bool)
+        for step in range(3):
+            sel = ok & (j == step) & ~seen[rec]
+            pick |= sel
+            seen[rec[sel]] = True
+        ok = pick
+    return eo[ok], ep[ok], int(sp[1 + mm])
+
+
+def check_word(env, m, all_patterns, max_records=None, cap=None):
+    _, _, _, d_sp, d_op, text = env.planes(m)
+    mr = m if max_records is None else max_records
+    exp = word_expected(env, m, mr, all_patterns)
+    cap = len(exp[0]) + 9 if cap is None else cap
+    pat, o = out_planes(cap)
+    nb = env.m.lib.acm_word_workspace_bytes(mr)
+    ws = poisoned_ws(nb)
+    d_text = DeviceArray.from_numpy(text)
+    env.m.word_async(d_sp, d_op, mr, d_text, 0, text.size, pat, o, cap, word_mask=Matcher.word_mask(WORD),
+                     all_patterns=all_patterns, workspace=(ws.ptr, nb))
+    poison.check_planes(pat, o, cap, exp, what="word m=%d max_records=%d cap=%d all=%d" % (m, mr, cap, all_patterns))
+    return exp
+
+
+@pytest.mark.parametrize("m", COUNTS + [BIG])
+def test_word(env, m):
+    for all_patterns in (False, True):
+        exp = check_word(env, m, all_patterns)
+        if m == BIG:
+            continue
+        for mr in max_records_of(m):
+            check_word(env, m, all_patterns, max_records=mr)
+        for cap in caps_of(len(exp[0])):
+            check_word(env, m, all_patterns, cap=cap)
+
+
+def test_word_list_across_the_cut(env):
+    """a record whose list writes entries on both sides of the cap - 2 cut"""
+    m = 257
+    eo, _, _ = word_expected(env, m, m, True)
+    i = int(np.flatnonzero((eo[1:] == eo[:-1]))[-1])   # entries i and i + 1 are one record's
+    check_word(env, m, True, cap=i + 1 + 2)
+
+
+# ------------------------------------------------------------------ tally
+
+
+def check_tally(env, m, all_patterns, starts, class_of=None, C=3, max_records=None):
+    kind, off, _, d_sp, d_op, _ = env.planes(m)
+    mr = m if max_records is None else max_records
+    mm = min(m, mr)
+    eo, ep, _, _ = entries(env, kind[:mm], off[:mm], all_patterns)
+    S = len(starts)
+    exp = tally_model.tally(eo, ep, class_of, C, np.asarray(starts, dtype=np.int64) if S else None)
+    tot, rows, lead = DeviceArray(C * 8), DeviceArray(max(S * C, 1) * 4), DeviceArray(C * 4)
+    poison.fill([tot, rows, lead], P)
+    d_st = DeviceArray.from_numpy(np.asarray(starts, dtype=np.int32), pad_to=0) if S else None
+    d_map = DeviceArray.from_numpy(np.asarray(class_of, dtype=np.int32), pad_to=0) if class_of is not None else None
+    nb = env.m.lib.acm_tally_workspace_bytes(mr, C)
+    ws = poisoned_ws(nb)
+    env.m.tally_async(d_sp, d_op, mr, tot, report=_lib.REPORT_STATE, all_patterns=all_patterns, class_of=d_map,
+                      num_classes=C, seg_start=d_st, segments=S, seg_class=rows if S else None, lead=lead,
+                      workspace=(ws.ptr, nb))
+    what = "tally m=%d max_records=%d all=%d S=%d C=%d" % (m, mr, all_patterns, S, C)
+    assert np.array_equal(tot.to_numpy(np.uint64, C), exp[0]), what
+    assert np.array_equal(lead.to_numpy(np.int32, C), exp[2]), what
+    if S:
+        assert np.array_equal(rows.to_numpy(np.int32, S * C).reshape(S, C), exp[1]), what
+
+
+@pytest.mark.parametrize("m", COUNTS + [BIG])
+def test_tally(env, m):
+    starts = np.arange(48, 4 * m + 4, 12 * 4, dtype=np.int64)   # the first records are the lead's
+    for all_patterns in (False, True):
+        check_tally(env, m, all_patterns, [])
+        check_tally(env, m, all_patterns, starts)
+    if m != BIG:
+        for mr in max_records_of(m):
+            check_tally(env, m, True, starts, max_records=mr)
+
+
+@pytest.mark.parametrize("n_rows,C,class_of", [(1024, 2, [0, 1, 0]), (683, 3, None), (682, 3, None)])
+def test_tally_rows_in_lds_and_not(env, n_rows, C, class_of):
+    """the rows of tile 0 times the classes: 2048 cells (the LDS budget), 2049 (global atomics), 2046"""
+    starts = [0] + list(range(4, 4 * n_rows, 4)) + [4096]
+    assert len(starts) == n_rows + 1
+    check_tally(env, 1025, True, starts, class_of=class_of, C=C)
+
+
+# ------------------------------------------------------------------ line select
+
+
+@pytest.mark.parametrize("lines", [1, 31, 32, 33, 256 * 32, 256 * 32 + 1])
+@pytest.mark.parametrize("lead", [False, True])
+def test_line_select(env, lines, lead):
+    m = 1025
+    _, off, _, _, d_op, _ = env.planes(m)
+    L = lines - (1 if lead else 0)
+    end = 4 * m + 4
+    rng = np.random.default_rng(lines)
+    # starts over the offsets' span and beyond it, so that some lines hold records and some none
+    st = np.sort(rng.choice(np.arange(1 if lead else 0, 3 * end), L, replace=False)).astype(np.int64)
+    if not lead and L:
+        st[0] = 0
+    end = int(max(end, st[-1] + 1 if L else end))
+    capacity = L + 3
+    ls = np.full(capacity, 0x7FFFFFFF, dtype=np.int32)
+    ls[:L] = st
+    info = np.array([L, L, 0 if lead else 1, 0, 0, 0, 0, 0], dtype=np.int32)
+    d_ls, d_info = DeviceArray.from_numpy(ls, pad_to=0), DeviceArray.from_numpy(info, pad_to=0)
+    nb = env.m.lib.acm_line_select_workspace_bytes(capacity)
+    for invert in (False, True):
+        ent = line_model.select(st, info, 0, end, off, invert=invert)
+        for cap in caps_of(len(ent[0])):
+            outs = out_planes(cap, 3)
+            ws = poisoned_ws(nb)
+            env.m.line_select_async(d_ls, capacity, d_info, 0, end, d_op, m, outs[0], outs[1], outs[2], cap,
+                                    invert=invert, workspace=(ws.ptr, nb))
+            for got, exp in zip(outs, line_model.planes(ent, cap, PV)):
+                assert np.array_equal(got.to_numpy(np.int32, cap), exp), "lines=%d lead=%d invert=%d cap=%d" % (
+                    lines, lead, invert, cap)
+
+
+# ------------------------------------------------------------------ expand
+
+
+@pytest.mark.parametrize("m", [1, 65, 257, 1025])
+def test_expand_header_and_trailer(env, m):
+    kind, off, sp, d_sp, d_op, _ = env.planes(m, valid_only=True)
+    for mr in max_records_of(m):
+        if mr == 0:
+            continue
+        mm = min(m, mr)
+        eo, ep, _, _ = entries(env, kind[:mm], off[:mm], True)
+        exp = (eo, ep, int(sp[1 + mm]))
+        nb = env.m.lib.acm_expand_workspace_bytes(mr)
+        for cap in caps_of(len(eo)):
+            pat, o = out_planes(cap)
+            ws = poisoned_ws(nb)
+            _lib.check(env.m.lib.acm_expand_matches_async(env.m.dfa, d_sp.ptr, d_op.ptr, mr, pat.ptr, o.ptr, cap, ws.ptr,
+                                                          nb, None), "acm_expand_matches_async")
+            poison.check_planes(pat, o, cap, exp, what="expand m=%d max_records=%d cap=%d" % (m, mr, cap))
