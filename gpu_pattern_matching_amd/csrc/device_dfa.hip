@@ -34,12 +34,12 @@
 #include <algorithm>
 #include <cstring>
 #include <new>
-#include <unordered_map>
 
 #include "acm_internal.h"
 #include "case_fold.h"
 #include "device_dfa.h"
 #include "lds_walk.h"
+#include "sieve_image.h"
 #include "sieve_tables.h"
 #include "sparse.h"
 
@@ -87,170 +87,33 @@ void free_small(acm_dfa *d, void *p)
 		hipFree(p);
 }
 
-// Tables of the sparse pipeline (sieve_tables.h).  sparse_ok stays false for sets the
-// pipeline does not apply to (a pattern shorter than 3 bytes, or none at all).
+// Tables of the sparse pipeline, built on the host (sieve_image.cpp) and uploaded as they are.  sparse_ok
+// stays false for sets the pipeline does not apply to (a pattern shorter than 3 bytes, or none at all).
 int build_sieve(const acm_automaton &a, acm_dfa *d)
 {
 	d->sparse_ok = false;
-	size_t shortest = SIZE_MAX;
-	for (const auto &p : a.patterns)
-		shortest = std::min(shortest, p.bytes.size());
-	if (a.patterns.empty() || shortest < 3)
+	acm::SieveImage img;
+	acm::build_sieve_image(a, img);
+	if (!img.applies)
 		return ACM_OK;
-	const uint32_t n = a.num_states, F = a.first_final;
-	uint32_t W = acm::sieve_stride((uint32_t)std::min<size_t>(shortest, 64));
-	if (const char *e = getenv("ACM_SIEVE_STRIDE")) {   // debugging aid: a smaller stride than the set allows
-		const uint32_t v = (uint32_t)atoi(e);
-		if ((v == 1 || v == 2 || v == 4 || v == 8) && v <= W)
-			W = v;
-	}
-	const uint32_t D = (uint32_t)std::min<size_t>(shortest, acm::kSieveMaxPrefix);
-	d->sv_stride = W;
-	d->sv_prefix_len = D;
-	// runs of one byte that can start a pattern: D copies of b down the trie
-	memset(d->sv_run_ok, 0, sizeof(d->sv_run_ok));
-	for (uint32_t b = 0; b < 256; b++) {
-		uint32_t s = 0, k = 0;
-		for (; k < D; k++) {
-			uint32_t next = UINT32_MAX;
-			for (uint32_t e = a.child_begin[s]; e < a.child_begin[s + 1]; e++)
-				if (a.child_list[e].byte == b)
-					next = a.child_list[e].to;
-			if (next == UINT32_MAX)
-				break;
-			s = next;
-		}
-		if (k == D)
-			d->sv_run_ok[b >> 5] |= 1u << (b & 31);
-	}
-	if (a.nocase)   // (the bulk kernel tests a run of raw bytes: a run of 'a' is one of 'A')
-		for (uint32_t b = 'a'; b <= 'z'; b++)
-			if ((d->sv_run_ok[acm::fold_byte(b) >> 5] >> (acm::fold_byte(b) & 31)) & 1u)
-				d->sv_run_ok[b >> 5] |= 1u << (b & 31);
-
-	// 3-grams at offsets < W of every pattern, with the offsets they occur at
-	std::unordered_map<uint32_t, uint32_t> grams;
-	grams.reserve(a.patterns.size() * W * 2);
-	for (const auto &p : a.patterns)
-		for (uint32_t o = 0; o < W; o++) {
-			const uint32_t g = (uint32_t)p.bytes[o] | ((uint32_t)p.bytes[o + 1] << 8) | ((uint32_t)p.bytes[o + 2] << 16);
-			grams[g] |= 1u << o;
-		}
-	// the filter's keys: the 3-grams, or the 6 bytes at the sampled offsets where every pattern has them
-	const uint32_t LG = (W + 5 <= shortest && W >= 4) ? 6u : 3u;
-	d->sv_gram_len = LG;
-	std::unordered_map<uint64_t, bool> fkeys;
-	for (const auto &p : a.patterns)
-		for (uint32_t o = 0; o < W; o++) {
-			const uint64_t g3 = (uint32_t)p.bytes[o] | ((uint32_t)p.bytes[o + 1] << 8) | ((uint32_t)p.bytes[o + 2] << 16);
-			const uint64_t m3 = LG == 6 ? (uint32_t)p.bytes[o + 3] | ((uint32_t)p.bytes[o + 4] << 8) | ((uint32_t)p.bytes[o + 5] << 16) : 0u;
-			fkeys[g3 | (m3 << 24)] = true;
-		}
-	uint32_t lw = acm::kSieveMinLogWords;
-	while (lw < acm::kSieveMaxLogWords && ((size_t)1 << lw) < fkeys.size())
-		lw++;
-	if (const char *e = getenv("ACM_BLOOM_LOG_WORDS")) {   // debugging aid
-		const int v = atoi(e);
-		if (v >= (int)acm::kSieveMinLogWords && v <= (int)acm::kSieveMaxLogWords)
-			lw = (uint32_t)v;
-	}
-	d->sv_bloom_log_words = lw;
-	std::vector<uint32_t> bloom((size_t)1 << lw, 0);
-	for (const auto &kv : fkeys) {
-		const uint32_t g3 = (uint32_t)(kv.first & 0xFFFFFFu), m3 = (uint32_t)(kv.first >> 24);
-		const uint32_t blk = acm::sieve_bloom_block(g3, m3, lw);
-		const uint64_t bits = acm::sieve_bloom_bits(g3, m3);
-		bloom[2 * blk] |= (uint32_t)bits;
-		bloom[2 * blk + 1] |= (uint32_t)(bits >> 32);
-	}
-
-	// gram table: buckets of four, one gram per bucket on average (a full bucket costs the
-	// lookup a second, dependent load: 2 % of the buckets)
-	uint32_t lb = 4;
-	while (((size_t)1 << lb) < grams.size())
-		lb++;
-	std::vector<uint32_t> gt((size_t)4 << lb, 0);
-	uint32_t gprobes = 1;
-	for (const auto &kv : grams) {
-		uint32_t b = acm::sieve_gram_bucket(kv.first, lb), probes = 1;
-		for (;; b = (b + 1) & ((1u << lb) - 1), probes++) {
-			uint32_t *slot = &gt[(size_t)b * 4];
-			int k = 0;
-			while (k < 4 && slot[k] != 0)
-				k++;
-			if (k < 4) {
-				slot[k] = kv.first | (kv.second << 24);
-				break;
-			}
-		}
-		gprobes = std::max(gprobes, probes);
-	}
-	d->sv_gram_log_buckets = lb;
-	d->sv_gram_probes = gprobes;
-
-	// prefix table: every depth-D node under its D path bytes
-	std::vector<uint32_t> nodes;
-	for (uint32_t r = 0; r < n; r++)
-		if (a.depth[r] == D)
-			nodes.push_back(r);
-	uint32_t ls = 4;   // an eighth full: a lookup ends at the first slot it reads, nearly always
-	while (((size_t)1 << ls) < 8 * nodes.size())
-		ls++;
-	std::vector<uint32_t> pt((size_t)4 << ls, 0);
-	uint32_t pprobes = 1;
-	for (uint32_t r : nodes) {
-		uint8_t key[12] = { 0 };
-		uint32_t s = r;
-		for (uint32_t k = D; k-- > 0; s = a.parent[s])
-			key[k] = a.in_byte[s];
-		uint32_t k0, k1, k2;
-		memcpy(&k0, key, 4);
-		memcpy(&k1, key + 4, 4);
-		memcpy(&k2, key + 8, 4);
-		const uint32_t dev = a.ref2dev[r];
-		uint32_t at = acm::sieve_prefix_slot(k0, k1, k2, ls), probes = 1;
-		while (pt[(size_t)at * 4 + 3] != 0) {
-			at = (at + 1) & ((1u << ls) - 1);
-			probes++;
-		}
-		pt[(size_t)at * 4 + 0] = k0;
-		pt[(size_t)at * 4 + 1] = k1;
-		pt[(size_t)at * 4 + 2] = k2 | ((uint32_t)a.dev_run[dev] << 16);
-		pt[(size_t)at * 4 + 3] = dev;
-		pprobes = std::max(pprobes, probes);
-	}
-	d->sv_prefix_log_slots = ls;
-	d->sv_prefix_probes = pprobes;
-
-	// node records and edges
-	std::vector<acm::SieveRec> rec(n, acm::sieve_rec(0, 0, 0, false, 0, 0, 0)), edges;
-	for (uint32_t dev = 0; dev < n; dev++) {
-		const uint32_t r = a.dev2ref[dev];
-		const uint32_t cb = a.child_begin[r], ce = a.child_begin[r + 1], nc = ce - cb;
-		auto leaf = [&](uint32_t child_ref) { return a.child_begin[child_ref + 1] == a.child_begin[child_ref]; };
-		auto outp = [&](uint32_t child_ref) { return a.is_final_ref(child_ref) ? (uint32_t)a.head_of(child_ref) : 0xFFFFFFFFu; };
-		if (nc == 1) {
-			const uint32_t c = a.child_list[cb].to, cd = a.ref2dev[c];
-			rec[dev] = acm::sieve_rec(cd, a.child_list[cb].byte, 1, leaf(c), a.dev_run[cd], outp(c), c);
-		} else if (nc >= 2) {
-			rec[dev] = acm::sieve_rec((uint32_t)edges.size(), 0, nc, false, 0, 0, 0);
-			for (uint32_t e = cb; e < ce; e++) {
-				const uint32_t c = a.child_list[e].to, cd = a.ref2dev[c];
-				edges.push_back(acm::sieve_edge(a.child_list[e].byte, cd, leaf(c), a.dev_run[cd], outp(c), c));
-			}
-		}
-	}
-	if (edges.size() >= (1u << 24))
+	d->sv_stride = img.W;
+	d->sv_prefix_len = img.D;
+	memcpy(d->sv_run_ok, img.run_ok, sizeof(d->sv_run_ok));
+	d->sv_gram_len = img.LG;
+	d->sv_bloom_log_words = img.bloom_log_words;
+	d->sv_gram_log_buckets = img.gram_log_buckets;
+	d->sv_gram_probes = img.gram_probes;
+	d->sv_prefix_log_slots = img.prefix_log_slots;
+	d->sv_prefix_probes = img.prefix_probes;
+	if (!img.ok)
 		return ACM_OK;   // edge index does not fit a record: the set stays on the chain pipeline
-	edges.push_back(acm::sieve_edge(0, 0, false, 0, 0, 0));
-	(void)F;
 
-	int rc = upload_small(d, &d->d_sv_bloom, bloom.data(), bloom.size());
-	if (rc == ACM_OK) rc = upload_small(d, &d->d_sv_gram, gt.data(), gt.size());
-	if (rc == ACM_OK) rc = upload_small(d, &d->d_sv_prefix, pt.data(), pt.size());
+	int rc = upload_small(d, &d->d_sv_bloom, img.bloom.data(), img.bloom.size());
+	if (rc == ACM_OK) rc = upload_small(d, &d->d_sv_gram, img.gram.data(), img.gram.size());
+	if (rc == ACM_OK) rc = upload_small(d, &d->d_sv_prefix, img.prefix.data(), img.prefix.size());
 	acm::SieveRec *drec = nullptr, *dedges = nullptr;
-	if (rc == ACM_OK) rc = upload_small(d, &drec, rec.data(), rec.size());
-	if (rc == ACM_OK) rc = upload_small(d, &dedges, edges.data(), edges.size());
+	if (rc == ACM_OK) rc = upload_small(d, &drec, img.rec.data(), img.rec.size());
+	if (rc == ACM_OK) rc = upload_small(d, &dedges, img.edges.data(), img.edges.size());
 	d->d_sv_rec = drec;
 	d->d_sv_edges = dedges;
 	if (rc == ACM_OK)
@@ -318,11 +181,10 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 			hot[i] = (uint16_t)((t < acm::kHotSentinel && t < F) ? t : acm::kHotSentinel);
 		}
 		std::vector<int32_t> outp(n);
-		std::vector<uint8_t> inb((size_t)n + 224, 0);   // (the followers read up to 192 bytes past a state's own)
+		const std::vector<uint8_t> inb = acm::device_in_byte(*a);   // [n + 224] (sieve_image.cpp: the self-test reads the same)
 		for (uint32_t s = 0; s < n; s++) {
 			const uint32_t r = a->dev2ref[s];
 			outp[s] = a->is_final_ref(r) ? a->head_of(r) : -1;
-			inb[s] = a->in_byte[r];
 		}
 		{
 			std::vector<uint32_t> plane(cells.size());

@@ -1,5 +1,5 @@
 // Tables of the sparse ("sieve") scan pipeline, and the hash functions the host
-// builder (device_dfa.hip) and the kernels (sparse.hip) must agree on.
+// builder (sieve_image.cpp) and the kernels (sparse.hip) must agree on.
 //
 // Idea (details and the proof sketch are in sparse.hip).  With m = length of the
 // shortest pattern, every final state has trie depth >= m.  Sample the text every
@@ -16,7 +16,8 @@
 
 #include <cstdint>
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__)   // (hipcc compiles the host-only sources as HIP too)
+#include <hip/hip_runtime.h>
 #define ACM_HD __host__ __device__ __forceinline__
 #else
 #define ACM_HD inline

@@ -371,7 +371,7 @@ __device__ __forceinline__ Follow follow(const SieveArgs &a, LaneHits &h, uint32
 			// (a signature is one unary run from its prefix to its leaf more often than not: the whole of
 			// it in one level where the text has the room, 64 bytes near its end)
 			const bool roomy = x + 1 + kLongLevel <= a.n_pad;
-			const uint32_t step = min(run, roomy ? kLongLevel : 64u), want = min(step, a.n - 1 - x);
+			const uint32_t step = min(run, kLongLevel), want = min(step, a.n - 1 - x);
 			// with the compare, what the node at the end of the stretch needs if the stretch is the
 			// whole run: its record and the byte behind it -- one level instead of two
 			c = acm::fold_if<NOCASE>(a.text[min(x + step + 1, a.n_pad - 1)]);
@@ -379,9 +379,7 @@ __device__ __forceinline__ Follow follow(const SieveArgs &a, LaneHits &h, uint32
 			uint32_t same;
 			if (roomy) {
 				same = agree<kLongLevel / 16, NOCASE>(a.in_byte + node + 1, a.text + x + 1);
-			} else if (x + 65 <= a.n_pad) {
-				same = agree<4, NOCASE>(a.in_byte + node + 1, a.text + x + 1);
-			} else {
+			} else {   // fewer than kLongLevel bytes to the padded end of the text
 				same = 0;
 				while (same < want && a.in_byte[node + 1 + same] == (NOCASE ? (uint8_t)acm::fold_byte(a.text[x + 1 + same]) : a.text[x + 1 + same]))
 					same++;

@@ -110,6 +110,24 @@ int acm_automaton_byte_classes(const acm_automaton *, uint8_t *class_of);
  * bytes, rows beyond the mandatory ones, simple records, side entries ending in a row, side entries
  * deferring to the fail state. */
 int acm_compact_selftest(const acm_automaton *, uint32_t lds_bytes, uint32_t *stats);
+/* The tables of the sparse pipeline (Bloom filter, gram buckets, prefix slots, node records and edges:
+ * csrc/sieve_tables.h), built on the host exactly as acm_dfa_upload builds them and looked up again by
+ * plain serial code -- no device needed.  Checked: every pattern's 3-gram at every sampled offset is
+ * found within the recorded number of buckets with its offset bit set, and no entry has a bit that no
+ * pattern justifies; every filter key has its four bits; every depth-D trie node is found under its
+ * path bytes within the recorded number of slots, with the automaton's run; the records and the
+ * sorted edges reproduce the children of every state; the byte into each state of a unary run is the
+ * trie edge's.  Returns 1 if all of that holds, 0 if the set does not qualify for the pipeline (no
+ * pattern, one shorter than 3 bytes, 2^24 edges or more), negative on error or when a check fails
+ * (acm_last_error names the first failing item).  stats, if not NULL, gets ACM_SIEVE_STATS words:
+ *  [0] stride W  [1] prefix length D  [2] filter key bytes LG  [3] log2 of the Bloom filter's words
+ *  [4] bits set in the filter  [5] distinct filter keys  [6] distinct 3-grams  [7] log2 of the gram
+ *  buckets  [8] full buckets  [9] gram probe bound  [10] log2 of the prefix slots  [11] occupied slots
+ *  [12] prefix probe bound  [13] largest number of children of a state of depth >= D  [14] longest
+ *  unary run behind such a state  [15] edges  [16..20] FNV-1a (32 bits) of the bytes of the Bloom
+ *  words, gram buckets, prefix slots, records and edges as uploaded.  All zero when 0 is returned. */
+#define ACM_SIEVE_STATS 21
+int acm_sieve_selftest(const acm_automaton *, uint32_t *stats);
 /* tuning aid, host only: walks text through the LDS form from the root; counts[5] = steps, steps
  * decided by the record or a row alone, by one side entry, by more than one hop, final states entered.
  * Returns 1, or 0 if the set does not qualify. */
