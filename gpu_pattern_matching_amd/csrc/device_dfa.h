@@ -4,6 +4,7 @@
 #include <atomic>
 #include <cstdint>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "acmatch.h"
@@ -52,7 +53,7 @@ struct acm_dfa {
 	void *arena = nullptr;               // one allocation for the small tables (device_dfa.hip, upload_small)
 	size_t arena_bytes = 0, arena_used = 0;
 
-	// adaptive AUTO mode (scan.hip, pick_sparse): sparse batches that turned out dense in matches,
+	// adaptive AUTO mode (dispatch.cpp, pick_sparse): sparse batches that turned out dense in matches,
 	// counted by the device in pinned host memory
 	uint32_t *h_giveups = nullptr, *d_giveups = nullptr;
 	mutable std::atomic<uint32_t> sparse_batches{0}, giveups_seen{0}, chain_hold{0};
@@ -75,19 +76,14 @@ struct acm_dfa {
 	int chain_bytes = 0;                 // 0 = pick automatically
 	int chains_per_lane = 4;             // 2 or 4 independent chains per lane in the walk
 
-	// HIP graphs of batches that repeat (scan.hip, acm_scan_batch_async)
+	// HIP graphs of batches that repeat (dispatch.cpp, acm_scan_batch_async)
 	struct GraphKey {
-		const void *text;
-		size_t n, halo;
-		long offset_shift, init_state;
-		void *workspace;
-		size_t workspace_bytes;
-		void *pat_plane, *off_plane;
-		size_t plane_capacity;
-		int report, mode, chain_bytes, chains_per_lane;
-		const void *init_plane;
-		size_t init_plane_capacity;
+		acm_scan_batch batch;   // stream null (no event fields, not timed: such batches are not captured)
+		int mode, chain_bytes, chains_per_lane, zero;
 	};
+	// Keys are compared with memcmp, so neither struct may have padding; and a field added to acm_scan_batch
+	// that does not change what is enqueued has to be cleared in graph_key, or every lookup misses.
+	static_assert(std::has_unique_object_representations_v<GraphKey>, "GraphKey must have no padding");
 	struct GraphEntry {
 		GraphKey key;
 		void *exec;          // hipGraphExec_t, null until the key has been seen twice
@@ -104,8 +100,8 @@ struct acm_dfa {
 	mutable uint64_t graph_tick = 0;
 	mutable std::atomic<uint64_t> graphs_captured{0}, graphs_launched{0};   // acm_scan_graph_stats: instantiated, hipGraphLaunch calls
 
-	// optional in-line timing (acm_scan_profile_*): event triples
-	// {before walk, after walk, after last kernel} per recorded launch
+	// optional in-line timing (acm_scan_profile_*): event quadruples
+	// {before the first kernel, after the first stage, after the second, after the last kernel} per recorded launch
 	mutable bool profile = false;
 	mutable std::vector<void *> profile_events;
 	mutable std::vector<void *> profile_pool;   // idle events, reused

@@ -1,4 +1,4 @@
-// Interface between scan.hip (dispatch, workspace layout) and lds_walk.hip.
+// Interface between dispatch.cpp (which cuts a job's areas out of the workspace layout of chain.h) and lds_walk.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

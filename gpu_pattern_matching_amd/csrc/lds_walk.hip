@@ -855,7 +855,7 @@ void lds_walk_release(acm_dfa *d)
 }
 
 // Two launches for up to 16 batches of one size on one stream.  The areas of a batch's workspace are
-// handed over by the caller (scan.hip lays the workspace out).
+// handed over by the caller (dispatch.cpp, from the workspace layout of chain.h).
 int lds_walk_enqueue(const acm_dfa *d, const LdsJob *jobs, uint32_t count, hipStream_t s, hipEvent_t after_walk,
     hipEvent_t after_walk2)
 {
@@ -921,7 +921,7 @@ int lds_walk_enqueue(const acm_dfa *d, const LdsJob *jobs, uint32_t count, hipSt
 	return ACM_OK;
 }
 
-// what a batch of n bytes needs of each workspace area (scan.hip checks them against its layout)
+// what a batch of n bytes needs of each workspace area (dispatch.cpp checks them against the workspace layout)
 void lds_walk_needs(const acm_dfa *d, size_t n, size_t *stage_words, size_t *cnt_bytes, size_t *tile_words)
 {
 	const size_t chains = (n + kChainBytes - 1) >> kLogChain;

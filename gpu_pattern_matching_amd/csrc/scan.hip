@@ -48,16 +48,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <climits>
 #include <cstdint>
-#include <atomic>
 #include <cstring>
-#include <mutex>
 
 #include "acm_internal.h"
+#include "chain.h"
 #include "deep_walk.h"
 #include "device_dfa.h"
-#include "lds_walk.h"
 #include "sparse.h"
 
 namespace {
@@ -852,29 +849,155 @@ __global__ void k_finalize_empty(ScanArgs a)
 }
 
 // ---------------------------------------------------------------------------
-// host side
+// host side: the workspace layout and what the dispatcher enqueues (chain.h)
 // ---------------------------------------------------------------------------
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct Layout {
-	size_t end_state, c1f, k2info, wend, probe, rflag, cnt, off, wave_cnt1, wave_cnt2, misc, stage1,
-	    stage2, scan_ws, sparse;
-	size_t scan_ws_bytes;
-	size_t total;
+// geometry: enough chains to give every lane of every CU work, chains as long as that allows (longer chains = fewer look-back steps)
+struct Geometry {
+	int C;                // chains per lane
+	uint32_t S;           // chain bytes
+	bool wide_pre;        // speculative mode with 64-byte chains: two chains per lane, 16 waves per CU, text loaded up front
+	uint32_t halo_mode, halo_bytes, halo_pre;   // halo mode (walk_tile): the longest pattern fits the chain -- no speculation to resolve
 };
 
-// sized for the smallest chain length (16 B) so any geometry fits
-Layout layout_for(const acm_dfa *d, size_t max_text)
+Geometry chain_geometry(const acm_dfa *d, size_t n)
 {
-	Layout l;
+	Geometry g = { d->chains_per_lane == 2 ? 2 : 4, (uint32_t)d->chain_bytes, false, 0, 0, 0 };
+	const uint32_t hb = ((d->max_pattern_len > 1 ? d->max_pattern_len - 1 : 0u) + 15u) & ~15u;
+	auto halo_fits = [&] { return d->use_halo && hb <= g.S; };   // a chain can walk the longest pattern's halo in front of its own bytes
+	if (g.S == 0) {
+		const size_t lanes = (size_t)d->num_cus * kBlock1 * g.C;
+		g.S = 16;
+		while (g.S < 256 && (size_t)g.S * 2 * lanes <= n)
+			g.S *= 2;
+		// halo mode walks L - 1 bytes per chain twice: with half the waves of every CU still busy a
+		// chain of four halos is the better deal when batches are in flight side by side (sentiment
+		// set, 32 MiB: 650 instead of 574 GB/s; alone the walk takes 89 instead of 56 us)
+		uint32_t want = 16;
+		while (want < 4 * hb)
+			want *= 2;
+		if (halo_fits() && g.C == 4 && hb > 0 && want > g.S && want <= 256 && (size_t)want * lanes <= 2 * n)
+			g.S = want;
+		// speculative mode (patterns longer than a chain): a chain's look-back window is ceil(L / S) chains, and
+		// it is the probe and resolve kernels' slowest lanes -- chains of dependent loads through that window --
+		// that those kernels take as long as.  Chains of a third of the longest pattern: half the chains of the
+		// same text at 32 MiB, i.e. half of every CU's lanes idle in the walk kernel -- which batches in flight
+		// side by side fill (ClamAV signatures, 3 streams: 635 instead of 489 GB/s; a batch alone 111 instead of
+		// 98 us).  Large texts only: a small one is short of chains as it is.
+		if (!halo_fits() && n >= ((size_t)16 << 20)) {
+			while (g.S < 256 && (d->max_pattern_len + g.S - 1) / g.S > 3)
+				g.S *= 2;
+			static const bool no_wide = getenv("ACM_SCAN_NO_WIDE_PRE") != nullptr;   // debugging aid
+			if (g.S == 64 && g.C == 4 && d->use_preload && !no_wide) {
+				g.wide_pre = true;
+				g.C = 2;
+			}
+		}
+	}
+	g.halo_mode = (halo_fits() && g.C == 4) ? 1u : 0u;
+	g.halo_bytes = g.halo_mode ? hb : 0u;
+	g.halo_pre = (g.halo_mode && ((g.S + hb) >> 4) <= (uint32_t)kPreGroups && d->use_preload) ? 1u : 0u;
+	if (!g.halo_mode && g.S == 64 && d->use_preload && (g.C == 4 || g.wide_pre))
+		g.halo_pre = 1u;   // (speculative mode, chains of 64 bytes: k_halo_walk<CLS, false, ...>)
+	return g;
+}
+
+ScanArgs scan_args(const acm_dfa *d, const acm_scan_batch *b, const acm::ScanLayout &l, const Geometry &g, uint32_t init_dev,
+    const uint32_t *init_ptr)
+{
+	char *ws = (char *)b->d_workspace;
+	ScanArgs a;
+	memset(&a, 0, sizeof(a));
+	a.cold = d->d_cold;
+	a.deep = d->d_deep;
+	a.hot = d->d_hot;
+	a.cls = d->d_class;
+	a.ls = d->log_stride;
+	a.halo_bytes = g.halo_bytes;
+	a.halo_mode = g.halo_mode;
+	a.halo_pre = g.halo_pre;
+	// the plane value of a record is a per-state table lookup: the head pattern, or the state's
+	// reference id when the caller wants to expand the whole match list afterwards
+	a.out = b->report == ACM_REPORT_STATE ? (const int32_t *)d->d_dev2ref : d->d_out;
+	a.dev2ref = d->d_dev2ref;
+	a.in_byte = d->d_in_byte;
+	a.text16 = (const uint4 *)b->d_text;
+	a.text = (const uint8_t *)b->d_text;
+	a.n = (uint32_t)b->n;
+	a.n_pad = (uint32_t)((b->n + 15) & ~(size_t)15);
+	a.S = g.S;
+	while ((1u << a.logS) < g.S)
+		a.logS++;
+	a.n_chains = (uint32_t)((b->n + g.S - 1) >> a.logS);
+	a.n_tiles = (a.n_chains + g.C * 64 - 1) / (g.C * 64);
+	a.H = d->hot_rows;
+	a.hot_depth1 = d->hot_depth1;
+	a.F = d->first_final;
+	a.L = d->max_pattern_len;
+	a.q = std::max(1u, (a.L + g.S - 1) / g.S);
+	a.init_state = init_dev;
+	a.init_ptr = init_ptr;
+	a.drop_before = (uint32_t)b->halo;
+	a.off_shift = (int32_t)b->offset_shift;
+	a.end_state = (uint32_t *)(ws + l.end_state);
+	a.c1f = (uint32_t *)(ws + l.c1f);
+	a.k2info = (uint32_t *)(ws + l.k2info);
+	a.wend = (uint32_t *)(ws + l.wend);
+	a.probe = (uint8_t *)(ws + l.probe);
+	a.rflag = (uint8_t *)(ws + l.rflag);
+	a.cnt = (int32_t *)(ws + l.cnt);
+	a.off = (int32_t *)(ws + l.off);
+	a.wave_cnt1 = (uint32_t *)(ws + l.wave_cnt1);
+	a.wave_cnt2 = (uint32_t *)(ws + l.wave_cnt2);
+	a.misc = (uint32_t *)(ws + l.misc);
+	a.stage1 = (uint2 *)(ws + l.stage1);
+	a.stage2 = (uint2 *)(ws + l.stage2);
+	a.pat_plane = b->d_pat_plane;
+	a.off_plane = b->d_off_plane;
+	a.plane_capacity = (uint32_t)std::min<size_t>(b->plane_capacity, 0xFFFFFFFFul);
+	return a;
+}
+
+template <int C>
+int launch_spec_walk(const ScanArgs &a, int num_cus, hipStream_t s)
+{
+	const size_t lds = acm::kHotBytes + 256;   // rows + class map; above 48 KiB: allowed by acm::scan_prepare
+	const bool cls = a.ls != 8;
+	void (*walk)(ScanArgs);
+	uint32_t block = kBlock1;
+	if (C == 2 && a.halo_pre && !a.halo_mode) {   // (speculative mode, 64-byte chains: 16 waves of two chains per lane)
+		walk = cls ? k_halo_walk<true, false, 2, 1024> : k_halo_walk<false, false, 2, 1024>;
+		block = 1024;
+	} else if (C == 4 && a.halo_pre) {
+		walk = a.halo_mode ? (cls ? k_halo_walk<true, true> : k_halo_walk<false, true>)
+		                   : (cls ? k_halo_walk<true, false> : k_halo_walk<false, false>);
+		block = kBlockPre;
+	} else if (a.halo_mode && C == 4) {
+		walk = cls ? k_spec_walk<4, true, true> : k_spec_walk<4, false, true>;
+	} else {
+		walk = cls ? k_spec_walk<C, true, false> : k_spec_walk<C, false, false>;
+	}
+	const uint32_t blocks = std::min((a.n_tiles + block / 64 - 1) / (block / 64), (uint32_t)num_cus);   // a wave per tile, a workgroup per CU
+	hipLaunchKernelGGL(walk, dim3(blocks), dim3(block), lds, s, a);
+	ACM_HIP_TRY(hipGetLastError());
+	return ACM_OK;
+}
+
+}  // namespace
+
+namespace acm {
+
+// sized for the smallest chain length (16 B) so any geometry fits
+ScanLayout scan_layout(const acm_dfa *d, size_t max_text)
+{
+	ScanLayout l;
 	const size_t chains = max_text / 16 + 64 * 4 + 64;
 	const size_t waves = chains / 64 + 2;
 	const size_t stage_recs = max_text + (size_t)4 * 64 * 256;
 	size_t o = 0;
 	auto take = [&](size_t bytes) {
 		size_t at = o;
-		o = align_up(o + bytes, 256);
+		o = (o + bytes + 255) / 256 * 256;
 		return at;
 	};
 	l.end_state = take(chains * 4);
@@ -897,322 +1020,6 @@ Layout layout_for(const acm_dfa *d, size_t max_text)
 	return l;
 }
 
-template <int C>
-int launch_spec_walk(const ScanArgs &a, int num_cus, hipStream_t s)
-{
-	const size_t lds = acm::kHotBytes + 256;   // rows + class map; above 48 KiB: allowed by acm::scan_prepare
-	uint32_t blocks = (a.n_tiles + kWaves1 - 1) / kWaves1;
-	if (blocks > (uint32_t)num_cus)
-		blocks = (uint32_t)num_cus;
-	if (C == 2 && a.halo_pre && !a.halo_mode) {   // (speculative mode, 64-byte chains: 16 waves of two chains per lane)
-		uint32_t pblocks = (a.n_tiles + 1024 / 64 - 1) / (1024 / 64);
-		if (pblocks > (uint32_t)num_cus)
-			pblocks = (uint32_t)num_cus;
-		if (a.ls == 8)
-			hipLaunchKernelGGL((k_halo_walk<false, false, 2, 1024>), dim3(pblocks), dim3(1024), lds, s, a);
-		else
-			hipLaunchKernelGGL((k_halo_walk<true, false, 2, 1024>), dim3(pblocks), dim3(1024), lds, s, a);
-	} else if (C == 4 && a.halo_pre) {
-		uint32_t pblocks = (a.n_tiles + kBlockPre / 64 - 1) / (kBlockPre / 64);
-		if (pblocks > (uint32_t)num_cus)
-			pblocks = (uint32_t)num_cus;
-		if (a.halo_mode) {
-			if (a.ls == 8)
-				hipLaunchKernelGGL((k_halo_walk<false, true>), dim3(pblocks), dim3(kBlockPre), lds, s, a);
-			else
-				hipLaunchKernelGGL((k_halo_walk<true, true>), dim3(pblocks), dim3(kBlockPre), lds, s, a);
-		} else {
-			if (a.ls == 8)
-				hipLaunchKernelGGL((k_halo_walk<false, false>), dim3(pblocks), dim3(kBlockPre), lds, s, a);
-			else
-				hipLaunchKernelGGL((k_halo_walk<true, false>), dim3(pblocks), dim3(kBlockPre), lds, s, a);
-		}
-	} else if (a.halo_mode && C == 4) {
-		if (a.ls == 8)
-			hipLaunchKernelGGL((k_spec_walk<4, false, true>), dim3(blocks), dim3(kBlock1), lds, s, a);
-		else
-			hipLaunchKernelGGL((k_spec_walk<4, true, true>), dim3(blocks), dim3(kBlock1), lds, s, a);
-	} else if (a.ls == 8) {
-		hipLaunchKernelGGL((k_spec_walk<C, false, false>), dim3(blocks), dim3(kBlock1), lds, s, a);
-	} else {
-		hipLaunchKernelGGL((k_spec_walk<C, true, false>), dim3(blocks), dim3(kBlock1), lds, s, a);
-	}
-	ACM_HIP_TRY(hipGetLastError());
-	return ACM_OK;
-}
-
-}  // namespace
-
-extern "C" size_t acm_scan_workspace_bytes(const acm_dfa *d, size_t max_text)
-{
-	return layout_for(d, max_text).total;
-}
-
-extern "C" int acm_scan_set_chain_bytes(acm_dfa *d, int chain_bytes)
-{
-	if (!d)
-		return 0;
-	if (chain_bytes == 0 || (chain_bytes >= 16 && chain_bytes <= 256 &&
-	    (chain_bytes & (chain_bytes - 1)) == 0))
-		d->chain_bytes = chain_bytes;
-	return d->chain_bytes;
-}
-
-extern "C" int acm_scan_set_chains_per_lane(acm_dfa *d, int chains)
-{
-	if (!d)
-		return 0;
-	if (chains == 2 || chains == 4)
-		d->chains_per_lane = chains;
-	return d->chains_per_lane;
-}
-
-extern "C" int acm_scan_kernel_count(void) { return 4; }
-
-namespace {
-// Which pipeline the next batch gets.  Tiny texts are not worth the sieve's tables.  In AUTO
-// mode the choice adapts: the sparse pipeline is exact on any text but slow on one that is dense
-// in matches or in flagged samples (its emit kernel counts such batches, sparse.hip), so when
-// half of the last 16 sparse batches were dense the next 64 go to the chain pipeline, then the
-// sparse one is tried again -- for 4 batches; if half of those are dense again the chain
-// pipeline gets four times as many batches as last time (up to 4096), and so on until a look
-// finds the text quiet.
-bool pick_sparse(const acm_dfa *d, size_t n)
-{
-	if (!d->sparse_ok || d->scan_mode == ACM_SCAN_MODE_CHAIN || n < 64)
-		return false;
-	if (d->scan_mode != ACM_SCAN_MODE_AUTO || !d->h_giveups)
-		return true;
-	uint32_t hold = d->chain_hold.load(std::memory_order_relaxed);
-	while (hold > 0)
-		if (d->chain_hold.compare_exchange_weak(hold, hold - 1, std::memory_order_relaxed))
-			return false;
-	const uint32_t count = d->sparse_batches.fetch_add(1, std::memory_order_relaxed) + 1;
-	const uint32_t window = d->auto_window.load(std::memory_order_relaxed);
-	if (count >= window) {
-		d->sparse_batches.store(0, std::memory_order_relaxed);
-		const uint32_t seen = *(volatile uint32_t *)d->h_giveups;   // written by k_sieve_emit, may lag
-		const uint32_t before = d->giveups_seen.exchange(seen, std::memory_order_relaxed);
-		if (seen - before >= window / 2) {
-			const uint32_t stay = d->auto_next_hold.load(std::memory_order_relaxed);
-			d->chain_hold.store(stay, std::memory_order_relaxed);
-			d->auto_next_hold.store(std::min<uint32_t>(stay * 4, 4096u), std::memory_order_relaxed);
-			d->auto_window.store(4, std::memory_order_relaxed);
-		} else {
-			d->auto_next_hold.store(64, std::memory_order_relaxed);
-			d->auto_window.store(16, std::memory_order_relaxed);
-		}
-	}
-	return true;
-}
-}  // namespace
-
-extern "C" int acm_scan_set_mode(acm_dfa *d, int mode)
-{
-	if (!d)
-		return ACM_SCAN_MODE_CHAIN;
-	if (mode == ACM_SCAN_MODE_AUTO || mode == ACM_SCAN_MODE_CHAIN || mode == ACM_SCAN_MODE_SPARSE)
-		d->scan_mode = mode;
-	return d->scan_mode;
-}
-
-extern "C" int acm_scan_sparse_eligible(const acm_dfa *d) { return d && d->sparse_ok ? 1 : 0; }
-extern "C" int acm_scan_lds_resident(const acm_dfa *d) { return d && d->lds_ok && d->use_halo ? 1 : 0; }
-extern "C" int acm_scan_group_capable(const acm_dfa *d)
-{
-	if (!d || d->use_graphs || d->max_group <= 1)
-		return 0;
-	const bool sparse = d->sparse_ok && d->scan_mode != ACM_SCAN_MODE_CHAIN;
-	return (sparse || (d->lds_ok && d->use_halo)) ? 1 : 0;
-}
-
-extern "C" int acm_scan_path_taken(const acm_dfa *d, const void *d_workspace, size_t n, void *stream)
-{
-	if (!d || !d_workspace)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_path_taken: bad arguments");
-	ACM_HIP_TRY(hipSetDevice(d->device));
-	ACM_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-	if (n == 0)
-		return ACM_SCAN_MODE_CHAIN;
-	const Layout l = layout_for(d, n);
-	uint32_t marker = 0;   // misc[2]: written by whichever pipeline produced the planes
-	ACM_HIP_TRY(hipMemcpy(&marker, (const char *)d_workspace + l.misc + 8, 4, hipMemcpyDeviceToHost));
-	return (int)marker;
-}
-
-extern "C" int acm_scan_async(const acm_dfa *d, const void *d_text, size_t n, long init_state,
-    void *d_workspace, size_t workspace_bytes, int32_t *d_pat_plane, int32_t *d_off_plane,
-    size_t plane_capacity, void *stream)
-{
-	return acm_scan_shard_async(d, d_text, n, 0, 0, init_state, d_workspace, workspace_bytes,
-	    d_pat_plane, d_off_plane, plane_capacity, stream);
-}
-
-extern "C" int acm_scan_shard_async(const acm_dfa *d, const void *d_text, size_t n, size_t halo,
-    long offset_shift, long init_state, void *d_workspace, size_t workspace_bytes,
-    int32_t *d_pat_plane, int32_t *d_off_plane, size_t plane_capacity, void *stream)
-{
-	acm_scan_batch b;
-	memset(&b, 0, sizeof(b));
-	b.d_text = d_text;
-	b.n = n;
-	b.halo = halo;
-	b.offset_shift = offset_shift;
-	b.init_state = init_state;
-	b.d_workspace = d_workspace;
-	b.workspace_bytes = workspace_bytes;
-	b.d_pat_plane = d_pat_plane;
-	b.d_off_plane = d_off_plane;
-	b.plane_capacity = plane_capacity;
-	b.stream = stream;
-	return acm_scan_batch_async(d, &b);
-}
-
-namespace {
-bool pick_sparse(const acm_dfa *d, size_t n);
-// what enqueue_batch leaves to the caller when it defers the launches of a batch that joins a group
-struct Deferred {
-	acm::SieveJob sieve;
-	acm::LdsJob lds;
-};
-int enqueue_batch(const acm_dfa *d, const acm_scan_batch *batch, bool sparse, Deferred *defer);
-// the chain pipeline's LDS-resident form takes launch groups too (lds_walk.hip)
-bool lds_path(const acm_dfa *d, bool sparse, size_t n) { return !sparse && d->lds_ok && d->use_halo && n > 0; }
-
-// consecutive sparse batches of one size on one stream, each with its own workspace and planes,
-// that wait for nothing and are not timed: one group for the sparse kernels
-bool groupable(const acm_dfa *d, const acm_scan_batch &b)
-{
-	return !d->profile && !b.wait_before_walk && !b.record_after_walk && !b.d_init_plane && b.n > 0;
-}
-bool joins(const acm_scan_batch *const *group, uint32_t m, const acm_scan_batch &b)
-{
-	if (b.stream != group[0]->stream || b.n != group[0]->n || (b.profile != 0) != (group[0]->profile != 0))
-		return false;   // (a group is timed as a whole or not at all)
-	for (uint32_t i = 0; i < m; i++)
-		if (b.d_workspace == group[i]->d_workspace || b.d_pat_plane == group[i]->d_pat_plane ||
-		    b.d_off_plane == group[i]->d_off_plane)
-			return false;
-	return true;
-}
-}  // namespace
-
-extern "C" int acm_scan_batches_async(const acm_dfa *d, const acm_scan_batch *batches, size_t count)
-{
-	if (!batches && count)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_batches_async: null batches");
-	if (!d || d->use_graphs || d->max_group <= 1) {
-		for (size_t i = 0; i < count; i++) {
-			const int rc = acm_scan_batch_async(d, &batches[i]);
-			if (rc != ACM_OK)
-				return rc;
-		}
-		return ACM_OK;
-	}
-	const uint32_t cap = std::min<uint32_t>((uint32_t)d->max_group, std::min(acm::sparse_max_group(), acm::lds_walk_max_group()));
-	const acm_scan_batch *group[32];
-	uint32_t m = 0;
-	bool group_sparse = true;   // the pipeline of the group being collected
-	// Failure contract: "stops at the first batch that fails; the batches before it stay enqueued" --
-	// also inside a group: the members in front of the one that failed validation are launched (as a
-	// shorter group), and events taken from the pool go back to it on every error path.
-	auto flush = [&]() -> int {
-		int rc = ACM_OK;
-		const uint32_t members = m;
-		m = 0;
-		if (members == 1) {
-			rc = enqueue_batch(d, group[0], group_sparse, nullptr);
-		} else if (members > 1) {
-			Deferred jobs[32];
-			uint32_t good = 0;
-			int first_bad = ACM_OK;
-			for (; good < members; good++) {
-				first_bad = enqueue_batch(d, group[good], group_sparse, &jobs[good]);
-				if (first_bad != ACM_OK)
-					break;
-			}
-			hipStream_t gs = (hipStream_t)group[0]->stream;
-			hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-			auto give_back = [&]() {
-				std::lock_guard<std::mutex> lock(d->profile_mutex);
-				for (auto &e : ev)
-					if (e) {
-						d->profile_pool.push_back((void *)e);
-						e = nullptr;
-					}
-			};
-			if (good > 0 && group[0]->profile) {   // the group's kernels, timed like a single batch's
-				std::lock_guard<std::mutex> lock(d->profile_mutex);
-				for (auto &e : ev) {
-					if (!d->profile_pool.empty()) {
-						e = (hipEvent_t)d->profile_pool.back();
-						d->profile_pool.pop_back();
-					} else if (hipEventCreate(&e) != hipSuccess) {
-						e = nullptr;
-						rc = acm::fail(ACM_ERR_HIP, "acm_scan_batches_async: hipEventCreate failed");
-						break;
-					}
-				}
-			}
-			if (rc != ACM_OK) {
-				give_back();
-				return rc;
-			}
-			if (good > 0) {
-				if (ev[0] && hipEventRecord(ev[0], gs) != hipSuccess)
-					rc = acm::fail(ACM_ERR_HIP, "acm_scan_batches_async: hipEventRecord failed");
-				if (rc == ACM_OK && group_sparse) {
-					acm::SieveJob sj[32];
-					for (uint32_t i = 0; i < good; i++)
-						sj[i] = jobs[i].sieve;
-					rc = acm::sparse_group_enqueue(d, sj, good, gs, ev[1], ev[2]);
-				} else if (rc == ACM_OK) {
-					acm::LdsJob lj[32];
-					for (uint32_t i = 0; i < good; i++)
-						lj[i] = jobs[i].lds;
-					rc = acm::lds_walk_enqueue(d, lj, good, gs, ev[1], nullptr);
-					if (rc == ACM_OK && ev[2] && hipEventRecord(ev[2], gs) != hipSuccess)   // (the walk is the first stage, there is no second)
-						rc = acm::fail(ACM_ERR_HIP, "acm_scan_batches_async: hipEventRecord failed");
-				}
-				if (rc == ACM_OK && ev[0] && hipEventRecord(ev[3], gs) != hipSuccess)
-					rc = acm::fail(ACM_ERR_HIP, "acm_scan_batches_async: hipEventRecord failed");
-				if (rc == ACM_OK && ev[0]) {
-					std::lock_guard<std::mutex> lock(d->profile_mutex);
-					for (auto &e : ev) {
-						d->profile_events.push_back((void *)e);
-						e = nullptr;
-					}
-				}
-				give_back();   // (only what an error left behind)
-			}
-			if (rc == ACM_OK)
-				rc = first_bad;
-		}
-		return rc;
-	};
-	for (size_t i = 0; i < count; i++) {
-		const acm_scan_batch &b = batches[i];
-		const bool sparse = pick_sparse(d, b.n);   // (counts the batch: once per batch)
-		if ((sparse || lds_path(d, sparse, b.n)) && groupable(d, b)) {
-			if (m && (m >= cap || sparse != group_sparse || !joins(group, m, b))) {
-				const int rc = flush();
-				if (rc != ACM_OK)
-					return rc;
-			}
-			group_sparse = sparse;
-			group[m++] = &b;
-			continue;
-		}
-		int rc = flush();
-		if (rc == ACM_OK)
-			rc = enqueue_batch(d, &b, sparse, nullptr);
-		if (rc != ACM_OK)
-			return rc;
-	}
-	return flush();
-}
-
-namespace acm {
 int scan_prepare(const acm_dfa *)
 {
 	const void *walks[] = { (const void *)k_spec_walk<4, false, false>, (const void *)k_spec_walk<4, true, false>,
@@ -1225,402 +1032,35 @@ int scan_prepare(const acm_dfa *)
 		ACM_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(acm::kHotBytes + 256)));
 	return ACM_OK;
 }
-}  // namespace acm
 
-namespace {
-int enqueue_batch(const acm_dfa *d, const acm_scan_batch *batch, bool sparse, Deferred *defer = nullptr);
-
-// what a cached graph was captured for: every input of enqueue_batch except the stream
-acm_dfa::GraphKey graph_key(const acm_dfa *d, const acm_scan_batch *b, bool sparse)
+int carry_init_enqueue(const acm_dfa *d, const acm_scan_batch *b, uint32_t *misc, hipStream_t s)
 {
-	acm_dfa::GraphKey k;
-	memset(&k, 0, sizeof(k));
-	k.text = b->d_text;
-	k.n = b->n;
-	k.halo = b->halo;
-	k.offset_shift = b->offset_shift;
-	k.init_state = b->init_state;
-	k.workspace = b->d_workspace;
-	k.workspace_bytes = b->workspace_bytes;
-	k.pat_plane = b->d_pat_plane;
-	k.off_plane = b->d_off_plane;
-	k.plane_capacity = b->plane_capacity;
-	k.report = b->report;
-	k.init_plane = b->d_init_plane;
-	k.init_plane_capacity = b->init_plane_capacity;
-	k.mode = sparse ? ACM_SCAN_MODE_SPARSE : ACM_SCAN_MODE_CHAIN;
-	k.chain_bytes = d->chain_bytes;
-	k.chains_per_lane = d->chains_per_lane;
-	return k;
-}
-}  // namespace
-
-// The kernels of one scan are short and many; a host that scans with the same
-// buffers over and over (a worker with its staging buffers, as the reference's
-// workers do) pays more for launching them than the GPU for running them.  So
-// the enqueue of a batch that repeats is captured once into a HIP graph and
-// replayed with one hipGraphLaunch.
-extern "C" int acm_scan_batch_async(const acm_dfa *d, const acm_scan_batch *batch)
-{
-	if (!batch)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_batch_async: null batch");
-	const bool sparse = d && pick_sparse(d, batch->n);
-	if (!d || !d->use_graphs || d->profile || batch->profile || !batch->stream || batch->wait_before_walk ||
-	    batch->record_after_walk || batch->n == 0)
-		return enqueue_batch(d, batch, sparse);
-	hipStream_t s = (hipStream_t)batch->stream;
-	const acm_dfa::GraphKey key = graph_key(d, batch, sparse);
-	hipGraphExec_t exec = nullptr;
-	bool capture = false;
-	{
-		std::lock_guard<std::mutex> lock(d->graph_mutex);
-		acm_dfa::GraphEntry *e = nullptr;
-		for (auto &g : d->graphs)
-			if (!memcmp(&g.key, &key, sizeof(key)))
-				e = &g;
-		if (!e) {   // first sighting: remember it, enqueue the plain way
-			if (d->graphs.size() >= acm_dfa::kMaxGraphs) {
-				size_t oldest = 0;
-				for (size_t i = 1; i < d->graphs.size(); i++)
-					if (d->graphs[i].last_use < d->graphs[oldest].last_use)
-						oldest = i;
-				// its last launch may still be running: an exec is only ever destroyed by
-				// acm_dfa_release; an evicted one is parked until then
-				if (d->graphs[oldest].exec)
-					d->parked_graphs.push_back(d->graphs[oldest].exec);
-				d->graphs.erase(d->graphs.begin() + (long)oldest);
-			}
-			acm_dfa::GraphEntry fresh;
-			fresh.key = key;
-			fresh.exec = nullptr;
-			fresh.last_use = ++d->graph_tick;
-			d->graphs.push_back(fresh);
-		} else {
-			e->last_use = ++d->graph_tick;
-			exec = (hipGraphExec_t)e->exec;
-			capture = !exec;
-		}
-	}
-	if (exec) {
-		ACM_HIP_TRY(hipSetDevice(d->device));
-		ACM_HIP_TRY(hipGraphLaunch(exec, s));
-		d->graphs_launched.fetch_add(1, std::memory_order_relaxed);
-		return ACM_OK;
-	}
-	if (!capture)
-		return enqueue_batch(d, batch, sparse);
-	// second sighting: capture.  Argument errors surface here exactly as in the plain path.
-	ACM_HIP_TRY(hipSetDevice(d->device));
-	if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-		(void)hipGetLastError();
-		d->use_graphs = false;   // e.g. the caller is capturing this stream itself
-		return enqueue_batch(d, batch, sparse);
-	}
-	const int rc = enqueue_batch(d, batch, sparse);
-	hipGraph_t graph = nullptr;
-	const hipError_t end = hipStreamEndCapture(s, &graph);
-	if (rc != ACM_OK || end != hipSuccess || !graph) {
-		if (graph)
-			hipGraphDestroy(graph);
-		(void)hipGetLastError();
-		d->use_graphs = false;
-		return rc != ACM_OK ? rc : enqueue_batch(d, batch, sparse);
-	}
-	const hipError_t inst = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-	hipGraphDestroy(graph);
-	if (inst != hipSuccess || !exec) {
-		(void)hipGetLastError();
-		d->use_graphs = false;
-		return enqueue_batch(d, batch, sparse);
-	}
-	d->graphs_captured.fetch_add(1, std::memory_order_relaxed);
-	{
-		std::lock_guard<std::mutex> lock(d->graph_mutex);
-		bool stored = false;
-		for (auto &g : d->graphs)
-			if (!memcmp(&g.key, &key, sizeof(key)) && !g.exec) {
-				g.exec = (void *)exec;
-				stored = true;
-			}
-		if (!stored) {   // evicted, or another thread was quicker
-			d->parked_graphs.push_back((void *)exec);   // cannot be destroyed while in flight (nor leaked if the launch fails)
-			ACM_HIP_TRY(hipGraphLaunch(exec, s));
-			d->graphs_launched.fetch_add(1, std::memory_order_relaxed);
-			return ACM_OK;
-		}
-	}
-	ACM_HIP_TRY(hipGraphLaunch(exec, s));
-	d->graphs_launched.fetch_add(1, std::memory_order_relaxed);
+	hipLaunchKernelGGL(k_carry_init, dim3(1), dim3(64), 0, s, (const int32_t *)b->d_init_plane,
+	    (uint32_t)std::min<size_t>(b->init_plane_capacity, 0xFFFFFFFFul), (const uint32_t *)d->d_ref2dev,
+	    (const uint32_t *)(d->lds_ok ? d->d_lds_ref2code : nullptr), d->num_states, misc + kMiscInitDev, misc + kMiscInitCode);
+	ACM_HIP_TRY(hipGetLastError());
 	return ACM_OK;
 }
 
-extern "C" int acm_scan_graph_stats(const acm_dfa *d, uint64_t *captured, uint64_t *launched)
+int empty_scan_enqueue(const acm_dfa *d, const acm_scan_batch *b, const ScanLayout &l, uint32_t init_dev, const uint32_t *init_ptr,
+    hipStream_t s)
 {
-	if (!d)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_graph_stats: null dfa");
-	if (captured)
-		*captured = d->graphs_captured.load(std::memory_order_relaxed);
-	if (launched)
-		*launched = d->graphs_launched.load(std::memory_order_relaxed);
+	hipLaunchKernelGGL(k_finalize_empty, dim3(1), dim3(64), 0, s, scan_args(d, b, l, chain_geometry(d, 0), init_dev, init_ptr));
+	ACM_HIP_TRY(hipGetLastError());
 	return ACM_OK;
 }
 
-extern "C" int acm_scan_set_max_group(acm_dfa *d, int batches)
+int chain_scan_enqueue(const acm_dfa *d, const acm_scan_batch *b, const ScanLayout &l, uint32_t init_dev, const uint32_t *init_ptr,
+    hipStream_t s, hipEvent_t after_walk, hipEvent_t after_walk2)
 {
-	if (!d)
-		return 1;
-	if (batches >= 1)
-		d->max_group = std::min<int>(batches, (int)acm::sparse_max_group());
-	return d->max_group;
-}
-
-extern "C" int acm_scan_set_graphs(acm_dfa *d, int enable)
-{
-	if (!d)
-		return 0;
-	if (enable >= 0)
-		d->use_graphs = enable != 0;
-	return d->use_graphs ? 1 : 0;
-}
-
-namespace {
-// defer: (sparse pipeline, LDS walk) check and lay out as always, but leave the launches to the caller,
-// who enqueues a group of such batches with one set of kernels (acm_scan_batches_async)
-int enqueue_batch(const acm_dfa *d, const acm_scan_batch *batch, bool sparse, Deferred *defer)
-{
-	const void *d_text = batch->d_text;
-	const size_t n = batch->n, halo = batch->halo;
-	const long offset_shift = batch->offset_shift, init_state = batch->init_state;
-	void *d_workspace = batch->d_workspace;
-	const size_t workspace_bytes = batch->workspace_bytes;
-	int32_t *d_pat_plane = batch->d_pat_plane, *d_off_plane = batch->d_off_plane;
-	size_t plane_capacity = batch->plane_capacity;
-	void *stream = batch->stream;
-	if (!d || !d_pat_plane || !d_off_plane || plane_capacity < 2 || (n && !d_text))
-		return acm::fail(ACM_ERR_ARG, "acm_scan_async: bad arguments");
-	if (n > 0x7FFFFFEFul)
-		return acm::fail(ACM_ERR_LIMIT, "acm_scan_async: %zu bytes exceed the 2 GiB buffer limit", n);
-	if (((uintptr_t)d_text & 15) != 0)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_async: text must be 16-byte aligned");
-	if (batch->report != ACM_REPORT_HEAD && batch->report != ACM_REPORT_STATE)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_batch_async: report %d is not an ACM_REPORT_* value", batch->report);
-	if (halo > n || offset_shift < INT32_MIN || offset_shift > INT32_MAX ||
-	    (long)n + offset_shift > (long)INT32_MAX)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_shard_async: halo/offset_shift out of range");
-	if (batch->d_init_plane && batch->init_plane_capacity < 2)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_batch_async: d_init_plane needs the capacity its scan was given");
-	if (init_state < 0 || (uint64_t)init_state >= d->num_states)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_async: init_state %ld is not a state", init_state);
-	if (plane_capacity > 0xFFFFFFFFul)
-		plane_capacity = 0xFFFFFFFFul;
-	const Layout l = layout_for(d, n);
-	if (!d_workspace || workspace_bytes < l.total)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_async: workspace %zu B < required %zu B",
-		    workspace_bytes, l.total);
-	hipStream_t s = (hipStream_t)stream;
-	ACM_HIP_TRY(hipSetDevice(d->device));
-
-	// geometry: enough chains to give every lane of every CU work, chains
-	// as long as that allows (longer chains = fewer look-back steps)
-	int C = d->chains_per_lane == 2 ? 2 : 4;
-	uint32_t S = (uint32_t)d->chain_bytes;
-	bool wide_pre = false;   // speculative mode with 64-byte chains: two chains per lane, 16 waves per CU, text loaded up front
-	if (S == 0) {
-		const size_t lanes = (size_t)d->num_cus * kBlock1 * C;
-		S = 16;
-		while (S < 256 && (size_t)S * 2 * lanes <= n)
-			S *= 2;
-		// halo mode walks L - 1 bytes per chain twice: with half the waves of every CU still busy a
-		// chain of four halos is the better deal when batches are in flight side by side (sentiment
-		// set, 32 MiB: 650 instead of 574 GB/s; alone the walk takes 89 instead of 56 us)
-		const uint32_t hb = ((d->max_pattern_len > 1 ? d->max_pattern_len - 1 : 0u) + 15u) & ~15u;
-		uint32_t want = 16;
-		while (want < 4 * hb)
-			want *= 2;
-		if (d->use_halo && C == 4 && hb > 0 && hb <= S && want > S && want <= 256 && (size_t)want * lanes <= 2 * n)
-			S = want;
-		// speculative mode (patterns longer than a chain): a chain's look-back window is ceil(L / S) chains, and
-		// it is the probe and resolve kernels' slowest lanes -- chains of dependent loads through that window --
-		// that those kernels take as long as.  Chains of a third of the longest pattern: half the chains of the
-		// same text at 32 MiB, i.e. half of every CU's lanes idle in the walk kernel -- which batches in flight
-		// side by side fill (ClamAV signatures, 3 streams: 635 instead of 489 GB/s; a batch alone 111 instead of
-		// 98 us).  Large texts only: a small one is short of chains as it is.
-		if (!(d->use_halo && hb <= S) && n >= ((size_t)16 << 20)) {
-			while (S < 256 && (d->max_pattern_len + S - 1) / S > 3)
-				S *= 2;
-			static const bool no_wide = getenv("ACM_SCAN_NO_WIDE_PRE") != nullptr;   // debugging aid
-			if (S == 64 && C == 4 && d->use_preload && !no_wide) {
-				wide_pre = true;
-				C = 2;
-			}
-		}
-	}
-	uint32_t logS = 0;
-	while ((1u << logS) < S)
-		logS++;
-
-	char *ws = (char *)d_workspace;
-	ScanArgs a;
-	memset(&a, 0, sizeof(a));
-	a.cold = d->d_cold;
-	a.deep = d->d_deep;
-	a.hot = d->d_hot;
-	a.cls = d->d_class;
-	a.ls = d->log_stride;
-	// the plane value of a record is a per-state table lookup: the head pattern, or the state's
-	// reference id when the caller wants to expand the whole match list afterwards
-	a.out = batch->report == ACM_REPORT_STATE ? (const int32_t *)d->d_dev2ref : d->d_out;
-	a.dev2ref = d->d_dev2ref;
-	a.in_byte = d->d_in_byte;
-	a.text16 = (const uint4 *)d_text;
-	a.text = (const uint8_t *)d_text;
-	a.n = (uint32_t)n;
-	a.n_pad = (uint32_t)((n + 15) & ~(size_t)15);
-	a.S = S;
-	a.logS = logS;
-	a.n_chains = (uint32_t)((n + S - 1) >> logS);
-	a.n_tiles = (a.n_chains + C * 64 - 1) / (C * 64);
-	a.H = d->hot_rows;
-	a.hot_depth1 = d->hot_depth1;
-	a.F = d->first_final;
-	a.L = d->max_pattern_len;
-	a.q = (a.L + S - 1) / S;
-	if (a.q == 0)
-		a.q = 1;
-	a.init_state = d->ref2dev[(size_t)init_state];
-	{
-		// halo mode (walk_tile): the longest pattern fits the chain -- no speculation to resolve
-		const uint32_t hb = ((a.L > 1 ? a.L - 1 : 0u) + 15u) & ~15u;
-		a.halo_mode = (d->use_halo && C == 4 && hb <= S) ? 1u : 0u;
-		a.halo_bytes = a.halo_mode ? hb : 0u;
-		a.halo_pre = (a.halo_mode && ((S + hb) >> 4) <= (uint32_t)kPreGroups && d->use_preload) ? 1u : 0u;
-		if (!a.halo_mode && S == 64 && d->use_preload && (C == 4 || wide_pre))
-			a.halo_pre = 1u;   // (speculative mode, chains of 64 bytes: k_halo_walk<CLS, false, ...>)
-	}
-	a.drop_before = (uint32_t)halo;
-	a.off_shift = (int32_t)offset_shift;
-	a.end_state = (uint32_t *)(ws + l.end_state);
-	a.c1f = (uint32_t *)(ws + l.c1f);
-	a.k2info = (uint32_t *)(ws + l.k2info);
-	a.wend = (uint32_t *)(ws + l.wend);
-	a.probe = (uint8_t *)(ws + l.probe);
-	a.rflag = (uint8_t *)(ws + l.rflag);
-	a.cnt = (int32_t *)(ws + l.cnt);
-	a.off = (int32_t *)(ws + l.off);
-	a.wave_cnt1 = (uint32_t *)(ws + l.wave_cnt1);
-	a.wave_cnt2 = (uint32_t *)(ws + l.wave_cnt2);
-	a.misc = (uint32_t *)(ws + l.misc);
-	a.stage1 = (uint2 *)(ws + l.stage1);
-	a.stage2 = (uint2 *)(ws + l.stage2);
-	a.pat_plane = d_pat_plane;
-	a.off_plane = d_off_plane;
-	a.plane_capacity = (uint32_t)plane_capacity;
-
-	const bool empty = a.n_chains == 0;   // (header and trailer only: below, once the state to start in is known)
-
-	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-	const bool profile = !defer && (d->profile || batch->profile);   // (a deferred batch is timed with its group)
-	if (profile) {
-		std::lock_guard<std::mutex> lock(d->profile_mutex);
-		for (auto &e : ev) {
-			if (!d->profile_pool.empty()) {  // recycled: no create/destroy in a timed loop
-				e = (hipEvent_t)d->profile_pool.back();
-				d->profile_pool.pop_back();
-			} else {
-				ACM_HIP_TRY(hipEventCreate(&e));
-			}
-		}
-	}
-	if (batch->wait_before_walk)
-		ACM_HIP_TRY(hipStreamWaitEvent(s, (hipEvent_t)batch->wait_before_walk, 0));
-	if (profile)
-		ACM_HIP_TRY(hipEventRecord(ev[0], s));
-	int rc;
-	const uint32_t *init_dev_ptr = nullptr, *init_code_ptr = nullptr;
-	if (batch->d_init_plane) {   // the state to start in comes from another scan's planes, on the device
-		if (defer)
-			return acm::fail(ACM_ERR_ARG, "acm_scan_batches_async: a batch with d_init_plane cannot join a launch group");
-		hipLaunchKernelGGL(k_carry_init, dim3(1), dim3(64), 0, s, batch->d_init_plane,
-		    (uint32_t)std::min<size_t>(batch->init_plane_capacity, 0xFFFFFFFFul), (const uint32_t *)d->d_ref2dev,
-		    (const uint32_t *)(d->lds_ok ? d->d_lds_ref2code : nullptr), d->num_states, a.misc + 4, a.misc + 5);
-		ACM_HIP_TRY(hipGetLastError());
-		init_dev_ptr = a.misc + 4;
-		init_code_ptr = a.misc + 5;
-		a.init_ptr = init_dev_ptr;
-	}
-	if (empty) {
-		hipLaunchKernelGGL(k_finalize_empty, dim3(1), dim3(64), 0, s, a);
-		ACM_HIP_TRY(hipGetLastError());
-		if (batch->record_after_walk)   // (no walk: the batch behind this one waits for nothing older than this point)
-			ACM_HIP_TRY(hipEventRecord((hipEvent_t)batch->record_after_walk, s));
-		if (profile) {
-			for (int k = 1; k < 4; k++)
-				ACM_HIP_TRY(hipEventRecord(ev[k], s));
-			std::lock_guard<std::mutex> lock(d->profile_mutex);
-			for (auto e : ev)
-				d->profile_events.push_back((void *)e);
-		}
-		return ACM_OK;
-	}
-	if (sparse && defer) {
-		defer->sieve.batch = batch;
-		defer->sieve.init_dev = a.init_state;
-		defer->sieve.init_ptr = nullptr;
-		defer->sieve.sparse_ws = ws + l.sparse;
-		defer->sieve.path_marker = a.misc + 2;
-		return ACM_OK;
-	}
-	if (lds_path(d, sparse, n)) {   // the automaton fits the LDS whole: walk + scatter of lds_walk.hip
-		acm::LdsJob job;
-		job.batch = batch;
-		job.stage = (uint32_t *)(ws + l.stage1);
-		job.cnt = (uint8_t *)(ws + l.cnt);
-		job.tile_total = (uint32_t *)(ws + l.off);
-		job.misc = a.misc;
-		job.init_ptr = init_code_ptr;
-		size_t stage_words, cnt_bytes, tile_words;
-		acm::lds_walk_needs(d, n, &stage_words, &cnt_bytes, &tile_words);
-		if (stage_words * 4 > l.stage2 - l.stage1 || cnt_bytes > l.off - l.cnt || tile_words * 4 > l.wave_cnt1 - l.off)
-			return acm::fail(ACM_ERR_ARG, "acm_scan_async: workspace layout too small for the LDS walk");
-		if (defer) {
-			defer->lds = job;
-			return ACM_OK;
-		}
-		rc = acm::lds_walk_enqueue(d, &job, 1, s, profile ? ev[1] : nullptr, (hipEvent_t)batch->record_after_walk);
-		if (rc != ACM_OK)
-			return rc;
-		if (profile) {
-			ACM_HIP_TRY(hipEventRecord(ev[2], s));
-			ACM_HIP_TRY(hipEventRecord(ev[3], s));
-			std::lock_guard<std::mutex> lock(d->profile_mutex);
-			for (auto e : ev)
-				d->profile_events.push_back((void *)e);
-		}
-		return ACM_OK;
-	}
-	if (sparse) {   // three kernels of its own; it always produces the planes
-		rc = acm::sparse_scan_enqueue(d, batch, a.init_state, init_dev_ptr, ws + l.sparse, a.misc + 2, s, ev[1], ev[2]);
-		if (rc != ACM_OK)
-			return rc;
-		if (batch->record_after_walk)
-			ACM_HIP_TRY(hipEventRecord((hipEvent_t)batch->record_after_walk, s));
-		if (profile) {
-			ACM_HIP_TRY(hipEventRecord(ev[3], s));
-			std::lock_guard<std::mutex> lock(d->profile_mutex);
-			for (auto e : ev)
-				d->profile_events.push_back((void *)e);
-		}
-		return ACM_OK;
-	}
-	rc = C == 4 ? launch_spec_walk<4>(a, d->num_cus, s) : launch_spec_walk<2>(a, d->num_cus, s);
+	const Geometry g = chain_geometry(d, b->n);
+	ScanArgs a = scan_args(d, b, l, g, init_dev, init_ptr);
+	int rc = g.C == 4 ? launch_spec_walk<4>(a, d->num_cus, s) : launch_spec_walk<2>(a, d->num_cus, s);
 	if (rc != ACM_OK)
 		return rc;
-	if (batch->record_after_walk)
-		ACM_HIP_TRY(hipEventRecord((hipEvent_t)batch->record_after_walk, s));
-	if (profile) {   // the walk is the first stage, there is no second
-		ACM_HIP_TRY(hipEventRecord(ev[1], s));
-		ACM_HIP_TRY(hipEventRecord(ev[2], s));
-	}
+	for (hipEvent_t e : { (hipEvent_t)b->record_after_walk, after_walk, after_walk2 })
+		if (e)
+			ACM_HIP_TRY(hipEventRecord(e, s));
 	const uint32_t nb = (a.n_chains + kBlock2 - 1) / kBlock2;   // K2 blocks == scatter blocks
 	if (!a.halo_mode) {
 		if (d->nocase) {
@@ -1637,64 +1077,40 @@ int enqueue_batch(const acm_dfa *d, const acm_scan_batch *batch, bool sparse, De
 	} else if (nb <= kTopMax) {
 		hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kTopThreads), 0, s, a, nb);
 	} else {  // > 16M chains: generic multi-level scan of the block totals
-		rc = acm_exclusive_scan_i32(a.off, a.off, nb, (int32_t *)(a.misc + 1), ws + l.scan_ws,
+		rc = acm_exclusive_scan_i32(a.off, a.off, nb, (int32_t *)(a.misc + 1), (char *)b->d_workspace + l.scan_ws,
 		    l.scan_ws_bytes, s);
 		if (rc != ACM_OK)
 			return rc;
 	}
 	static_assert(kBlock2 % (4 * 64) == 0, "a scatter block must hold whole K1 wave tiles");
-	if (C == 4)
-		hipLaunchKernelGGL(k_scatter_all<4>, dim3(nb), dim3(kBlock2), 0, s, a);
-	else
-		hipLaunchKernelGGL(k_scatter_all<2>, dim3(nb), dim3(kBlock2), 0, s, a);
+	hipLaunchKernelGGL(g.C == 4 ? k_scatter_all<4> : k_scatter_all<2>, dim3(nb), dim3(kBlock2), 0, s, a);
 	ACM_HIP_TRY(hipGetLastError());
-	if (profile) {
-		ACM_HIP_TRY(hipEventRecord(ev[3], s));
-		std::lock_guard<std::mutex> lock(d->profile_mutex);
-		for (auto e : ev)
-			d->profile_events.push_back((void *)e);
-	}
 	return ACM_OK;
 }
 
-}  // namespace
+}  // namespace acm
 
-extern "C" int acm_scan_profile_enable(acm_dfa *d, int enable)
+extern "C" size_t acm_scan_workspace_bytes(const acm_dfa *d, size_t max_text)
+{
+	return acm::scan_layout(d, max_text).total;
+}
+
+extern "C" int acm_scan_set_chain_bytes(acm_dfa *d, int chain_bytes)
 {
 	if (!d)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_profile_enable: null dfa");
-	d->profile = enable != 0;
-	return ACM_OK;
+		return 0;
+	if (chain_bytes == 0 || (chain_bytes >= 16 && chain_bytes <= 256 && (chain_bytes & (chain_bytes - 1)) == 0))
+		d->chain_bytes = chain_bytes;
+	return d->chain_bytes;
 }
 
-extern "C" int acm_scan_profile_read(acm_dfa *d, double *first_ms, double *second_ms, double *pipeline_ms,
-    int *launches)
+extern "C" int acm_scan_set_chains_per_lane(acm_dfa *d, int chains)
 {
 	if (!d)
-		return acm::fail(ACM_ERR_ARG, "acm_scan_profile_read: null dfa");
-	double first = 0, second = 0, pipe = 0;
-	int n = 0;
-	std::lock_guard<std::mutex> lock(d->profile_mutex);
-	for (size_t i = 0; i + 3 < d->profile_events.size(); i += 4) {
-		hipEvent_t e[4];
-		for (int k = 0; k < 4; k++)
-			e[k] = (hipEvent_t)d->profile_events[i + k];
-		float a = 0, b = 0, c = 0;
-		ACM_HIP_TRY(hipEventSynchronize(e[3]));
-		ACM_HIP_TRY(hipEventElapsedTime(&a, e[0], e[1]));
-		ACM_HIP_TRY(hipEventElapsedTime(&b, e[1], e[2]));
-		ACM_HIP_TRY(hipEventElapsedTime(&c, e[0], e[3]));
-		first += a;
-		second += b;
-		pipe += c;
-		n++;
-		for (int k = 0; k < 4; k++)
-			d->profile_pool.push_back((void *)e[k]);
-	}
-	d->profile_events.clear();
-	if (first_ms) *first_ms = first;
-	if (second_ms) *second_ms = second;
-	if (pipeline_ms) *pipeline_ms = pipe;
-	if (launches) *launches = n;
-	return ACM_OK;
+		return 0;
+	if (chains == 2 || chains == 4)
+		d->chains_per_lane = chains;
+	return d->chains_per_lane;
 }
+
+extern "C" int acm_scan_kernel_count(void) { return 4; }

@@ -1,4 +1,4 @@
-// Interface between scan.hip (dispatch, chain pipeline) and sparse.hip.
+// Interface between dispatch.cpp and sparse.hip (chain.h: the chain pipeline's, lds_walk.h: the LDS walk's).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -60,7 +60,7 @@
 // reach (geometry_for); the lists are address space, only what is written is touched.
 // A text that is dense in matches, or in 3-grams of the pattern set that are no pattern
 // prefixes (real binaries), is merely slow here -- the emit kernel counts such batches and
-// AUTO mode moves to the chain pipeline of scan.hip (pick_sparse).
+// AUTO mode moves to the chain pipeline of scan.hip (pick_sparse, dispatch.cpp).
 // A launch may carry up to sixteen batches of one size (SieveGroup, acm_scan_batches_async):
 // the kernels' fixed costs are then paid once for all of them.
 #include <hip/hip_runtime.h>
@@ -1505,7 +1505,7 @@ __global__ __launch_bounds__(kEmitBlock) void k_sieve_emit(SieveGroup g)
 		a.off_plane[tail] = last_ref;
 		*a.path_marker = (uint32_t)ACM_SCAN_MODE_SPARSE;
 		// a batch this dense in matches, or with this many samples for the check kernel to look at (real
-		// binaries: common 3-grams of code), is the chain pipeline's: AUTO mode counts them (scan.hip,
+		// binaries: common 3-grams of code), is the chain pipeline's: AUTO mode counts them (dispatch.cpp,
 		// pick_sparse)
 		if (a.giveups)   // what the host sizes the next check launches by (sparse_group_enqueue)
 			__hip_atomic_store(a.giveups + 1, s_samples, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

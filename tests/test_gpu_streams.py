@@ -36,6 +36,7 @@ KiB, MiB = 1 << 10, 1 << 20
 N = 192 * KiB + 37          # ragged: not a multiple of 16, of a chain or of a tile
 EE = poison.PLANE_POISON
 HEAD, STATE = _lib.REPORT_HEAD, _lib.REPORT_STATE
+ACM_ERR_ARG = -1          # acmatch.h
 
 
 class Pipe:
@@ -399,7 +400,7 @@ def test_wait_before_walk_is_honoured(gpu, monkeypatch, pipe):
     """Stream A: some milliseconds of copies, then the text copied into X, then batch k (another text)
     recording E.  Stream B, nothing in front: batch k + 1 scans X and waits for E.  X held other bytes
     before, so only a scan that waited sees the text.  (Seen red once with the hipStreamWaitEvent call
-    taken out of a scratch copy of scan.hip: wrong records, as expected.)"""
+    taken out of a scratch copy of the dispatcher (dispatch.cpp, then part of scan.hip): wrong records, as expected.)"""
     vs, o, m = setup(pipe, monkeypatch)
     rig = streams.Rig()
     try:
@@ -429,7 +430,7 @@ def test_wait_before_walk_is_honoured(gpu, monkeypatch, pipe):
 
 @pytest.mark.parametrize("pipe", [BY_NAME["sparse-W4"], BY_NAME["lds-walk"]], ids=["sparse-W4", "lds-walk"])
 def test_events_inside_enqueue_many(gpu, monkeypatch, pipe):
-    """a batch with event fields between groupable batches has its launches to itself (groupable, scan.hip):
+    """a batch with event fields between groupable batches has its launches to itself (groupable, dispatch.cpp):
     its event is recorded, its waiter on another stream waits, and every batch is right"""
     vs, o, m = setup(pipe, monkeypatch)
     rig = streams.Rig()
@@ -764,6 +765,56 @@ def test_profiled_launch_groups(gpu, monkeypatch, pipe):
         m.profile(False)
         run([True, True, False, False, True], "profiled and plain batches mixed", 2)
         run([False] * 4, "no profiling", 0)
+    finally:
+        rig.close()
+        m.close()
+        o.close()
+
+
+@pytest.mark.parametrize("bad", (0, 1, 2))
+@pytest.mark.parametrize("pipe", [BY_NAME["sparse-W4"], BY_NAME["lds-walk"]], ids=["sparse-W4", "lds-walk"])
+def test_group_stops_at_its_failing_member(gpu, monkeypatch, pipe, bad):
+    """acm_scan_batches_async "stops at the first batch that fails; the batches before it stay enqueued" --
+    inside a launch group too.  Four profiled batches of one size that would form one group; batch 'bad'
+    carries an init_state that is no state, which the host rejects before it enqueues anything of that
+    batch.  The batches in front of it run as a shorter group (timed as one launch), the planes of the rest
+    keep their poison, the call returns ACM_ERR_ARG.  The same four with valid states then form a group
+    that is timed as one launch: the events the failed call took went back to the pool."""
+    vs, o, m = setup(pipe, monkeypatch)
+    rig = streams.Rig()
+    try:
+        s = rig.stream()
+        assert m.group_capable()
+        trs = [rig.triple(m, variants.text(vs, N, 900 + k, "planted")) for k in range(4)]
+        exps = [o.scan(vs.text_of(tr.t), k) for k, tr in enumerate(trs)]
+
+        def poisoned():
+            for tr in trs:
+                tr.ws.fill(0xA5, s)
+                tr.poison(s)
+
+        poisoned()
+        with pytest.raises(_lib.AcmError) as err:
+            m.enqueue_many([tr.batch(s, init_state=o.num_states if k == bad else k, profile=True)
+                            for k, tr in enumerate(trs)])
+        assert err.value.code == ACM_ERR_ARG
+        rig.sync(s)
+        for k, tr in enumerate(trs):
+            what = "%s batch %d, batch %d invalid" % (pipe.name, k, bad)
+            if k < bad:
+                tr.check(exps[k], s, what)
+                assert tr.path(s) == pipe.path, what
+            else:
+                for plane in (tr.pat, tr.off):
+                    cells = plane.to_numpy(np.int32, tr.cap, stream=s)
+                    assert np.all(cells == poison.cell(EE)), what + ": written, but nothing of it was to be enqueued"
+        read_profile(m, 1 if bad else 0, "%s the group in front of batch %d" % (pipe.name, bad))
+        poisoned()
+        m.enqueue_many([tr.batch(s, init_state=k, profile=True) for k, tr in enumerate(trs)])
+        for k, tr in enumerate(trs):
+            tr.check(exps[k], s, "%s batch %d after the failed call" % (pipe.name, k))
+            assert tr.path(s) == pipe.path
+        read_profile(m, 1, pipe.name + " the whole group after the failed call")
     finally:
         rig.close()
         m.close()
