@@ -35,6 +35,7 @@ class ShardPlan(C.Structure):
 
 REPORT_HEAD, REPORT_STATE = 0, 1
 TALLY_ACCUMULATE, TALLY_ALL_PATTERNS = 1, 2
+PATTERN_NOCASE = 1
 
 
 class AcmError(RuntimeError):
@@ -55,6 +56,10 @@ NATIVE_API = {
     "acm_automaton_free": (None, [_vp]),
     "acm_automaton_add": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int]),
     "acm_automaton_load_file": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int]),
+    "acm_automaton_add_ex": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, C.c_uint]),
+    "acm_automaton_load_file_ex": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, C.c_uint]),
+    "acm_automaton_pattern_flags": (C.c_int, [_vp, C.c_int]),
+    "acm_automaton_mixed_case": (C.c_int, [_vp]),
     "acm_automaton_set_nocase": (C.c_int, [_vp, C.c_int]),
     "acm_automaton_nocase": (C.c_int, [_vp]),
     "acm_automaton_compile": (C.c_int, [_vp]),
@@ -95,6 +100,9 @@ NATIVE_API = {
     "acm_word_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "acm_word_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_long, C.c_long, _vp, C.c_size_t, C.c_int,
                                          _vp, C.c_size_t, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "acm_case_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "acm_case_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_long, C.c_long, _vp, C.c_size_t, C.c_int,
+                                         _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
     "acm_tally_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_tally_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t,
                                           _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -97,14 +97,36 @@ class Automaton:
     def nocase(self):
         return bool(self.lib.acm_automaton_nocase(self.h))
 
-    def add(self, pattern: bytes, iid: int = 0):
-        check(self.lib.acm_automaton_add(self.h, pattern, len(pattern), iid), "acm_automaton_add")
+    def add(self, pattern: bytes, iid: int = 0, nocase: bool = False):
+        """Append one pattern.  nocase: this pattern ignores ASCII case (acm_automaton_add_ex); an
+        automaton with both kinds is mixed: its scans give candidates, Matcher.scan_case the matches."""
+        if nocase:
+            check(self.lib.acm_automaton_add_ex(self.h, pattern, len(pattern), iid, _lib.PATTERN_NOCASE),
+                  "acm_automaton_add_ex")
+        else:
+            check(self.lib.acm_automaton_add(self.h, pattern, len(pattern), iid), "acm_automaton_add")
 
-    def load_file(self, path, hex=False, max_len=-1):
-        n = self.lib.acm_automaton_load_file(self.h, str(path).encode(), int(hex), int(max_len))
+    def load_file(self, path, hex=False, max_len=-1, nocase=False):
+        if nocase:
+            n = self.lib.acm_automaton_load_file_ex(self.h, str(path).encode(), int(hex), int(max_len),
+                                                    _lib.PATTERN_NOCASE)
+        else:
+            n = self.lib.acm_automaton_load_file(self.h, str(path).encode(), int(hex), int(max_len))
         if n < 0:
             check(n, "acm_automaton_load_file")
         return n
+
+    def pattern_flags(self, i):
+        """the flags pattern i was added with (acm_automaton_pattern_flags): _lib.PATTERN_NOCASE or 0"""
+        f = self.lib.acm_automaton_pattern_flags(self.h, i)
+        if f < 0:
+            check(f, "acm_automaton_pattern_flags")
+        return f
+
+    @property
+    def mixed_case(self):
+        """compiled, and some patterns ignore case while others do not (acm_automaton_mixed_case)"""
+        return bool(self.lib.acm_automaton_mixed_case(self.h))
 
     def compile(self):
         check(self.lib.acm_automaton_compile(self.h), "acm_automaton_compile")
@@ -541,6 +563,78 @@ class Matcher:
             m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
             if m > ocap - 2:
                 raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_words", "%d records but planes hold %d"
+                               % (m, ocap - 2))
+            p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
+            o = off.to_numpy(np.int32, m + 2, stream=self.stream)
+            return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1])
+        finally:
+            for b in bufs:
+                b.free()
+
+    def case_async(self, state_plane, off_plane, max_records, d_text, text_origin, text_end, pat_out, off_out,
+                   out_capacity, before=None, before_len=0, all_patterns=False, tail_out=None, workspace=None,
+                   stream=None):
+        """Enqueue the case pass (acm_case_matches_async) over caller-owned device planes: the records of
+        a REPORT_STATE scan (or of the segment pass in STATE form) of a mixed automaton, an exact pattern
+        kept only where the text equals its bytes as added.  workspace: (ptr, nbytes), or None for a
+        temporary one that lives until the stream has passed it (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        tmp = None
+        if workspace is None:
+            nb = self.lib.acm_case_workspace_bytes(max_records)
+            tmp = DeviceArray(max(nb, 16))
+            workspace = (tmp.ptr, nb)
+        try:
+            check(self.lib.acm_case_matches_async(
+                self.dfa, _ptr(state_plane), _ptr(off_plane), max_records, _ptr(d_text), text_origin, text_end,
+                _ptr(before), before_len, 1 if all_patterns else 0, _ptr(pat_out), _ptr(off_out), out_capacity,
+                _ptr(tail_out), _ptr(workspace[0]), workspace[1], st), "acm_case_matches_async")
+        finally:
+            if tmp is not None:
+                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
+                tmp.free()
+
+    def scan_case(self, text, all_patterns=False, texts=None, init_state=0, before=b"", out_capacity=None):
+        """Matches of an automaton with case sensitivity per pattern (Automaton.add(..., nocase=True)):
+        a REPORT_STATE scan, the segment pass when texts is given, then the case pass
+        (acm_case_matches_async).  text: host bytes; or None with texts: a list of bytes-like objects or
+        a (uint8 array, int32 starts) pair, each matched as if scanned alone.  before: the bytes in
+        front of text (a stream's previous piece).  all_patterns: every kept pattern, else the first
+        in list order.  Returns (offsets, patterns, last_state) as scan_all does."""
+        if texts is not None:
+            t, starts = self.pack_segments(texts)
+        else:
+            t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
+                else np.ascontiguousarray(text, dtype=np.uint8)
+            starts = np.zeros(0, dtype=np.int32)
+        bf = np.frombuffer(bytes(before), dtype=np.uint8)
+        self.reserve(max(t.size, 1))
+        d = DeviceArray.from_numpy(t, stream=self.stream)
+        d_bf = DeviceArray.from_numpy(bf, stream=self.stream) if bf.size else None
+        nseg = int(starts.size)
+        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
+        max_records = self.plane_capacity - 2
+        cap = self.plane_capacity
+        ocap = out_capacity if out_capacity is not None else (8 * cap if all_patterns else cap)
+        ws_bytes = self.lib.acm_case_workspace_bytes(max_records)
+        bufs = [DeviceArray(max(ws_bytes, 16)), DeviceArray(ocap * 4), DeviceArray(ocap * 4)]
+        ws, pat, off = bufs
+        bufs += [b for b in (d, d_bf, d_st) if b is not None]
+        try:
+            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
+            sp, so = self.pat_plane, self.off_plane
+            if nseg:
+                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
+                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
+                bufs += sb
+                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
+                                   report=_lib.REPORT_STATE, workspace=(sb[0].ptr, seg_ws))
+                sp, so = sb[1], sb[2]
+            self.case_async(sp, so, max_records, d, 0, t.size, pat, off, ocap, before=d_bf, before_len=int(bf.size),
+                            all_patterns=all_patterns, workspace=(ws.ptr, ws_bytes))
+            m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
+            if m > ocap - 2:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_case", "%d records but planes hold %d"
                                % (m, ocap - 2))
             p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
             o = off.to_numpy(np.int32, m + 2, stream=self.stream)

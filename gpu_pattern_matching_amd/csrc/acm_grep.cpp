@@ -53,7 +53,7 @@ double now_us()
 	printf("\nUsage:\n"
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
-	       "             [-w cpu_threads] [-R max] [-tvxFMAiSWcn]\n"
+	       "             [-w cpu_threads] [-R max] [-I file] [-tvxFMAiSWcn]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -75,6 +75,11 @@ double now_us()
 	       "                 reference reports (extension; off by default)\n"
 	       "  -i             ignore ASCII case in patterns and input (extension; the patterns\n"
 	       "                 are folded after -x decoding and the -m cut, -v prints them as written)\n"
+	       "  -I file        a second pattern file whose patterns ignore ASCII case, appended after those of -p\n"
+	       "                 (pattern indices continue; -x and -m apply to it as to -p).  The patterns of -p stay\n"
+	       "                 exact: every buffer's records go through the case pass on the device before they\n"
+	       "                 are bucketed, printed, counted (-c) or numbered (-n).  With -i it is a second -p\n"
+	       "                 (extension; not with -W or -F)\n"
 	       "  -S             every input unit is its own text: a file, or with -t a line; no match\n"
 	       "                 spans two of them (extension; data appended under -F continues its file\n"
 	       "                 when the worker's previous chunk came from the same file)\n"
@@ -128,9 +133,10 @@ std::vector<std::string> regular_files_in(std::string dir)
 }
 
 struct Config {
-	std::string pat_path, data_path;
+	std::string pat_path, data_path, loose_path;   // loose_path: -I
 	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0,
 	    words = 0, count = 0, lineno = 0;
+	int cased = 0;           // -I without -i: the records go through the case pass
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
 	long global_ws = -1, local_ws = -1, chunk = -1;
@@ -167,6 +173,8 @@ struct Buffer {   // one of the two staging buffers of a worker
 	const int32_t *end_plane = nullptr;   // plane whose trailer holds the state the next buffer starts in
 	void *d_word_pat = nullptr, *d_word_off = nullptr, *d_word_ws = nullptr;   // -W only
 	size_t word_ws_bytes = 0;
+	void *d_case_pat = nullptr, *d_case_off = nullptr, *d_case_ws = nullptr;   // -I only
+	size_t case_ws_bytes = 0;
 	// -c only: the grid of file starts of this buffer's stream, the counts per start, of the records in front
 	// of the first start (they belong to cnt_prev_file) and of the whole buffer, and their pinned host twins
 	void *d_cnt_start = nullptr, *d_cnt_rows = nullptr, *d_cnt_lead = nullptr, *d_cnt_total = nullptr, *d_cnt_ws = nullptr;
@@ -204,7 +212,7 @@ struct Worker {
 	long last_state = 0;
 	int seg_file = -1;        // -S: file of the last chunk submitted
 	bool seg_open = false;    // -S -t: that chunk ended inside a line
-	void *d_tail[2] = { nullptr, nullptr };   // -W: the last max_pattern_len bytes of the stream so far, ping-pong
+	void *d_tail[2] = { nullptr, nullptr };   // -W, -I: the last max_pattern_len bytes of the stream so far, ping-pong
 	int tail_cur = 0;
 	size_t tail_len = 0;
 	int cnt_file = -1;        // -c, -n: file of the last chunk prepared
@@ -254,6 +262,12 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 		CK(acm_rt_malloc(&b.d_word_pat, (size + 2) * 4));
 		CK(acm_rt_malloc(&b.d_word_off, (size + 2) * 4));
 		CK(acm_rt_malloc(&b.d_word_ws, b.word_ws_bytes));
+	}
+	if (c.cased) {
+		b.case_ws_bytes = acm_case_workspace_bytes(size);
+		CK(acm_rt_malloc(&b.d_case_pat, (size + 2) * 4));
+		CK(acm_rt_malloc(&b.d_case_off, (size + 2) * 4));
+		CK(acm_rt_malloc(&b.d_case_ws, b.case_ws_bytes));
 	}
 	if (c.lineno) {
 		const size_t cells = c.all_patterns ? size * kAllFactor + 2 : size + 2;
@@ -443,15 +457,16 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 	b.scan_cap = cap;
 	b.end_plane = pat;
 	// final states instead of head patterns where a pass over the records follows: the segment pass
-	// clamps every one to its own text, the word pass keeps whole words, the expansion (-A) lists them
-	const bool states = c.segmented || c.words || c.all_patterns;
+	// clamps every one to its own text, the word pass keeps whole words, the case pass (-I) the exact
+	// patterns where the text has their case, the expansion (-A) lists them
+	const bool states = c.segmented || c.words || c.all_patterns || c.cased;
 	sb.report = states ? ACM_REPORT_STATE : ACM_REPORT_HEAD;
 	if (c.segmented && !b.seg_starts.empty())
 		CK(acm_rt_memcpy_h2d(b.d_seg_start, b.seg_starts.data(), b.seg_starts.size() * 4, s));
 	CK(acm_scan_batch_async(w.dfa, &sb));
 	if (c.segmented) {
 		CK(acm_segment_matches_async(w.dfa, pat, off, cap - 2, (const int32_t *)b.d_seg_start, b.seg_starts.size(),
-		    (long)b.stream_len, (c.all_patterns || c.words) ? ACM_REPORT_STATE : ACM_REPORT_HEAD,
+		    (long)b.stream_len, (c.all_patterns || c.words || c.cased) ? ACM_REPORT_STATE : ACM_REPORT_HEAD,
 		    (int32_t *)b.d_seg_pat, (int32_t *)b.d_seg_off, nullptr, cap, nullptr, b.d_seg_ws, b.seg_ws_bytes, s));
 		pat = (int32_t *)b.d_seg_pat;
 		off = (int32_t *)b.d_seg_off;
@@ -486,6 +501,22 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		pat = wp;
 		off = wo;
 		cap = wcap;
+		if (c.all_patterns)
+			CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
+	} else if (c.cased) {   // the candidates of a mixed automaton made exact; with -A every kept pattern (the expansion's place)
+		int32_t *cp = (int32_t *)(c.all_patterns ? b.d_pat_all : b.d_case_pat);
+		int32_t *co = (int32_t *)(c.all_patterns ? b.d_off_all : b.d_case_off);
+		const size_t ccap = c.all_patterns ? b.all_cap : b.scan_cap;
+		// the tail of the worker's stream so far is this buffer's before: a pattern that began in the buffer
+		// in front is compared whole (-S: the segment pass has left no entry that reaches into another text)
+		CK(acm_case_matches_async(w.dfa, pat, off, cap - 2, b.text, 0, (long)b.stream_len,
+		    w.tail_len ? w.d_tail[w.tail_cur] : nullptr, w.tail_len, c.all_patterns, cp, co, ccap, w.d_tail[w.tail_cur ^ 1],
+		    b.d_case_ws, b.case_ws_bytes, s));
+		w.tail_cur ^= 1;
+		w.tail_len = std::min((size_t)w.sh->max_pattern_len, w.tail_len + b.stream_len);
+		pat = cp;
+		off = co;
+		cap = ccap;
 		if (c.all_patterns)
 			CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
 	} else if (c.all_patterns) {   // every pattern of each final state's match list
@@ -638,7 +669,7 @@ void *worker_main(void *arg)
 	CK(acm_rt_malloc(&w.ws, w.ws_bytes));
 	buffer_alloc(w.buf[0], c, w.stream);
 	buffer_alloc(w.buf[1], c, w.stream);
-	if (c.words)
+	if (c.words || c.cased)
 		for (void *&t : w.d_tail)
 			CK(acm_rt_malloc(&t, (size_t)sh.max_pattern_len + 16));
 	const size_t npat = sh.pat_iid.size();
@@ -739,7 +770,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcn")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -771,6 +802,7 @@ int main(int argc, char **argv)
 		case 'W': c.words = 1; break;
 		case 'c': c.count = 1; break;
 		case 'n': c.lineno = 1; break;
+		case 'I': c.loose_path = optarg; break;
 		default: usage();
 		}
 	}
@@ -792,6 +824,14 @@ int main(int argc, char **argv)
 		printf("ERROR: -W cannot be combined with -F: the byte after a paused input is not known\n");
 		err++;
 	}
+	if (!c.loose_path.empty() && access(c.loose_path.c_str(), R_OK) != 0) {
+		printf("ERROR: File '%s' does not exist\n", c.loose_path.c_str()); err++;
+	}
+	if (!c.loose_path.empty() && (c.words || c.follow)) {   // the word pass takes states, the case pass gives patterns
+		printf("ERROR: -I cannot be combined with -W or -F: the case pass and those are not composed\n");
+		err++;
+	}
+	c.cased = !c.loose_path.empty() && !c.nocase;
 	if (c.lineno && c.text_mode) {
 		printf("ERROR: -n needs binary mode: -t already makes every line a chunk\n");
 		err++;
@@ -852,6 +892,11 @@ int main(int argc, char **argv)
 	acm_automaton *aut = acm_automaton_new();
 	CK(acm_automaton_set_nocase(aut, c.nocase));
 	if (acm_automaton_load_file(aut, c.pat_path.c_str(), c.hex, c.pat_limit) < 0) {
+		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
+		return 1;
+	}
+	if (!c.loose_path.empty() &&
+	    acm_automaton_load_file_ex(aut, c.loose_path.c_str(), c.hex, c.pat_limit, ACM_PATTERN_NOCASE) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}

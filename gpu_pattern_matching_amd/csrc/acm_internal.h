@@ -50,6 +50,7 @@ struct acm_automaton {
 	struct Pattern {
 		std::vector<unsigned char> bytes;
 		int iid;
+		unsigned flags = 0;                    // ACM_PATTERN_* as added (acm_automaton_add_ex)
 	};
 	std::vector<Pattern> patterns;         // bytes folded by compile when nocase: every table is built from these
 	int max_pattern_len = 0;
@@ -58,7 +59,17 @@ struct acm_automaton {
 	// compile folds the pattern bytes and keeps the originals for acm_automaton_pattern; the column
 	// of every lowercase letter repeats its uppercase letter's (byte classes, dense rows), so a walk
 	// over raw text is case-folded by its table lookups alone.
+	//
+	// nocase is the INTERNAL switch: "the tables are built from folded patterns and the kernels fold the
+	// text".  compile derives it from what the caller asked for: want_nocase (acm_automaton_set_nocase), or
+	// per-pattern ACM_PATTERN_NOCASE flags.  All patterns of length >= 1 flagged: the nocase automaton.
+	// Some flagged, some not: a MIXED automaton, built exactly as the nocase automaton of the same patterns
+	// (nocase on, mixed on); its scans report candidates and the case pass (case.hip) keeps the unflagged
+	// (exact) patterns only where the text equals `original`.  The public getter acm_automaton_nocase is
+	// nocase && !mixed.
 	bool nocase = false;
+	bool want_nocase = false;              // acm_automaton_set_nocase, as asked
+	bool mixed = false;                    // compiled, some patterns ignore case and some do not
 	std::vector<std::vector<unsigned char>> original;   // [pattern] bytes as added (nocase only)
 
 	uint32_t num_states = 0;               // highest ref id + 1

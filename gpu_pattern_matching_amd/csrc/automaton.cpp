@@ -77,13 +77,21 @@ extern "C" void acm_automaton_free(acm_automaton *a) { delete a; }
 
 extern "C" int acm_automaton_add(acm_automaton *a, const unsigned char *bytes, int n, int iid)
 {
+	return acm_automaton_add_ex(a, bytes, n, iid, 0);
+}
+
+extern "C" int acm_automaton_add_ex(acm_automaton *a, const unsigned char *bytes, int n, int iid, unsigned flags)
+{
 	if (!a || n < 0 || (n > 0 && !bytes))
 		return acm::fail(ACM_ERR_ARG, "acm_automaton_add: bad arguments");
+	if (flags & ~(unsigned)ACM_PATTERN_NOCASE)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_ex: unknown flag bits 0x%x", flags & ~(unsigned)ACM_PATTERN_NOCASE);
 	if (a->compiled)
 		return acm::fail(ACM_ERR_ARG, "acm_automaton_add: automaton already compiled");
 	acm_automaton::Pattern p;
 	p.bytes.assign(bytes, bytes + n);
 	p.iid = iid;
+	p.flags = flags;
 	a->patterns.push_back(std::move(p));
 	if (n > a->max_pattern_len)
 		a->max_pattern_len = n;
@@ -96,11 +104,20 @@ extern "C" int acm_automaton_set_nocase(acm_automaton *a, int enable)
 		return acm::fail(ACM_ERR_ARG, "acm_automaton_set_nocase: null automaton");
 	if (a->compiled)
 		return acm::fail(ACM_ERR_ARG, "acm_automaton_set_nocase: automaton already compiled");
-	a->nocase = enable != 0;
+	a->nocase = a->want_nocase = enable != 0;
 	return ACM_OK;
 }
 
-extern "C" int acm_automaton_nocase(const acm_automaton *a) { return (a && a->nocase) ? 1 : 0; }
+extern "C" int acm_automaton_nocase(const acm_automaton *a) { return (a && a->nocase && !a->mixed) ? 1 : 0; }
+
+extern "C" int acm_automaton_mixed_case(const acm_automaton *a) { return (a && a->compiled && a->mixed) ? 1 : 0; }
+
+extern "C" int acm_automaton_pattern_flags(const acm_automaton *a, int index)
+{
+	if (!a || index < 0 || index >= (int)a->patterns.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_pattern_flags: index out of range");
+	return (int)a->patterns[index].flags;
+}
 
 // ---- pattern file ------------------------------------------------------------
 
@@ -131,8 +148,15 @@ static bool looks_categorical(const std::string &line)
 
 extern "C" int acm_automaton_load_file(acm_automaton *a, const char *path, int hex, int max_len)
 {
+	return acm_automaton_load_file_ex(a, path, hex, max_len, 0);
+}
+
+extern "C" int acm_automaton_load_file_ex(acm_automaton *a, const char *path, int hex, int max_len, unsigned flags)
+{
 	if (!a || !path)
 		return acm::fail(ACM_ERR_ARG, "acm_automaton_load_file: bad arguments");
+	if (flags & ~(unsigned)ACM_PATTERN_NOCASE)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_load_file_ex: unknown flag bits 0x%x", flags & ~(unsigned)ACM_PATTERN_NOCASE);
 	FILE *fp = fopen(path, "r");
 	if (!fp)
 		return acm::fail(ACM_ERR_IO, "cannot open pattern file '%s': %s", path, strerror(errno));
@@ -192,11 +216,11 @@ extern "C" int acm_automaton_load_file(acm_automaton *a, const char *path, int h
 				rc = acm::fail(ACM_ERR_PARSE, "%s:%d: not a hex digit", path, line_no + 1);
 				break;
 			}
-			rc = acm_automaton_add(a, bytes.data(), (int)bytes.size(), (int)iid);
+			rc = acm_automaton_add_ex(a, bytes.data(), (int)bytes.size(), (int)iid, flags);
 		} else {
 			if (max_len != -1 && pat.size() > (size_t)max_len)
 				pat.resize((size_t)max_len);
-			rc = acm_automaton_add(a, (const unsigned char *)pat.data(), (int)pat.size(), (int)iid);
+			rc = acm_automaton_add_ex(a, (const unsigned char *)pat.data(), (int)pat.size(), (int)iid, flags);
 		}
 		if (rc != ACM_OK)
 			break;
@@ -476,6 +500,14 @@ extern "C" int acm_automaton_compile(acm_automaton *a)
 		return acm::fail(ACM_ERR_LIMIT, "pattern set may need %zu states (limit %u)", total,
 		    acm::kMaxStates);
 	try {
+		if (!a->want_nocase) {   // per-pattern flags: all flagged is the nocase automaton, some is a mixed one
+			size_t flagged = 0, plain = 0;
+			for (auto &p : a->patterns)
+				if (!p.bytes.empty())
+					(p.flags & ACM_PATTERN_NOCASE ? flagged : plain)++;
+			a->nocase = flagged > 0;
+			a->mixed = flagged > 0 && plain > 0;
+		}
 		if (a->nocase && a->original.empty()) {   // (not again after a failed compile)
 			a->original.resize(a->patterns.size());
 			for (size_t i = 0; i < a->patterns.size(); i++) {

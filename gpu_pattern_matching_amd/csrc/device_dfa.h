@@ -9,6 +9,10 @@
 
 #include "acmatch.h"
 
+namespace acm {
+constexpr uint32_t kCaseAny = 0xFFFFFFFFu, kCaseNever = 0xFFFFFFFEu;   // acm_dfa::d_case_ent
+}
+
 struct acm_dfa {
 	int device = 0;
 	int num_cus = 256;
@@ -49,6 +53,11 @@ struct acm_dfa {
 	uint32_t *d_fail_depth = nullptr;    // [states, reference numbering][2] {fail link, trie depth}: segmented scans (segment.hip)
 	uint32_t *d_pat_len = nullptr;       // [patterns] bytes of each pattern: where a list entry starts (word.hip)
 	uint32_t num_patterns = 0;
+	// a mixed automaton only (acm_automaton_mixed_case), for the case pass (case.hip); null otherwise
+	bool mixed = false;
+	uint32_t *d_case_ent = nullptr;      // [patterns][2] {word index of the pattern in d_case_pool, or kCaseAny: ignores case, or
+	                                     // kCaseNever: length 0; length}: one 8-byte load per list entry
+	uint32_t *d_case_pool = nullptr;     // the exact patterns' bytes as added, each padded to whole words, one spare word behind
 	size_t device_bytes = 0;
 	void *arena = nullptr;               // one allocation for the small tables (device_dfa.hip, upload_small)
 	size_t arena_bytes = 0, arena_used = 0;

@@ -237,6 +237,28 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 			plen[i] = (uint32_t)a->patterns[i].bytes.size();
 		d->num_patterns = (uint32_t)plen.size();
 		if (rc == ACM_OK) rc = upload_small(d, &d->d_pat_len, plen.data(), plen.size());
+		// a mixed automaton: what the case pass needs per pattern (case.hip).  Allocations of their own, so
+		// that the arena of a set that is not mixed is used as before.
+		d->mixed = a->mixed;
+		if (rc == ACM_OK && a->mixed) {
+			std::vector<uint32_t> ent(2 * a->patterns.size()), pool;
+			for (size_t i = 0; i < a->patterns.size(); i++) {
+				const std::vector<unsigned char> &b = a->original[i];
+				ent[2 * i + 1] = (uint32_t)b.size();
+				if (b.empty()) {
+					ent[2 * i] = acm::kCaseNever;
+				} else if (a->patterns[i].flags & ACM_PATTERN_NOCASE) {
+					ent[2 * i] = acm::kCaseAny;
+				} else {
+					ent[2 * i] = (uint32_t)pool.size();
+					pool.resize(pool.size() + (b.size() + 3) / 4, 0);
+					memcpy(&pool[ent[2 * i]], b.data(), b.size());
+				}
+			}
+			pool.push_back(0);   // the word behind the last pattern: the compare loads one word ahead
+			rc = upload(&d->d_case_ent, ent.data(), ent.size(), &d->device_bytes);
+			if (rc == ACM_OK) rc = upload(&d->d_case_pool, pool.data(), pool.size(), &d->device_bytes);
+		}
 	} catch (const std::bad_alloc &) {
 		rc = acm::fail(ACM_ERR_NOMEM, "acm_dfa_upload: out of host memory");
 	}
@@ -292,6 +314,8 @@ extern "C" void acm_dfa_release(acm_dfa *d)
 		hipFree(d->d_list_pool);
 		free_small(d, d->d_fail_depth);
 		free_small(d, d->d_pat_len);
+		hipFree(d->d_case_ent);
+		hipFree(d->d_case_pool);
 		free_small(d, d->d_depth);
 		free_small(d, d->d_class);
 		free_small(d, d->d_sv_bloom);

@@ -75,6 +75,45 @@ int acm_automaton_add(acm_automaton *, const unsigned char *bytes, int n,
 int acm_automaton_load_file(acm_automaton *, const char *path, int hex,
     int max_len);
 
+/* Case sensitivity per pattern.  acm_automaton_add_ex is acm_automaton_add plus
+ * flags (acm_automaton_add is add_ex with flags 0): ACM_PATTERN_NOCASE makes
+ * this pattern ignore ASCII case (the fold of acm_automaton_set_nocase below);
+ * a pattern without it is exact.  Unknown flag bits are ACM_ERR_ARG.
+ * acm_automaton_load_file_ex is the parser above with every pattern of the file
+ * added with flags; it may be called after other patterns were added (pattern
+ * indices continue).  acm_automaton_pattern_flags returns the flags as added,
+ * or ACM_ERR_ARG.  What acm_automaton_compile makes of the flags:
+ *   set_nocase(1)             every pattern ignores case, the flags do not
+ *                             matter, the automaton is not mixed: as without
+ *                             the flags, bit for bit
+ *   off, no pattern flagged   nothing changes
+ *   off, every pattern of length >= 1 flagged
+ *                             the automaton set_nocase(1) gives on the same
+ *                             patterns: same tables, self-test digests and
+ *                             reference table, acm_automaton_nocase() = 1, not
+ *                             mixed
+ *   otherwise                 a MIXED automaton.  It is built exactly as the
+ *                             nocase automaton of the same patterns (patterns
+ *                             folded, lowercase columns alias uppercase ones,
+ *                             the bytes as added kept), and every pipeline
+ *                             scans it as it scans that automaton.
+ *                             acm_automaton_nocase() = 0,
+ *                             acm_automaton_mixed_case() = 1 (1 only for a
+ *                             compiled automaton in which at least one pattern
+ *                             ignores case and one does not, else 0), and
+ *                             acm_automaton_pattern returns the bytes as added.
+ * The records of ANY scan of a mixed automaton are CANDIDATES: the nocase
+ * automaton's records, a superset of the wanted ones (an exact pattern is also
+ * reported where the text differs from it in case).  acm_case_matches_async
+ * makes them exact. */
+enum { ACM_PATTERN_NOCASE = 1 };
+int acm_automaton_add_ex(acm_automaton *, const unsigned char *bytes, int n,
+    int iid, unsigned flags);
+int acm_automaton_load_file_ex(acm_automaton *, const char *path, int hex,
+    int max_len, unsigned flags);
+int acm_automaton_pattern_flags(const acm_automaton *, int index);
+int acm_automaton_mixed_case(const acm_automaton *);
+
 /* ASCII case-insensitive matching for every pattern of the automaton.  With
  * it on, fold(b) = b - 0x20 for 'a' <= b <= 'z' and b otherwise (toupper in
  * the C locale; bytes >= 0x80 are never folded), and a scan of text T gives
@@ -82,12 +121,13 @@ int acm_automaton_load_file(acm_automaton *, const char *path, int hex,
  * same records, planes, states and overflow, pattern indices and iids those
  * of the patterns as added.  acm_automaton_pattern still returns the bytes as
  * added.  Off by default.  Only before acm_automaton_compile: afterwards it
- * fails with ACM_ERR_ARG.  Not provided: case sensitivity per pattern within
- * one automaton, and any folding beyond ASCII letters.  The reference-named
+ * fails with ACM_ERR_ARG.  Case sensitivity per pattern: acm_automaton_add_ex
+ * above.  Not provided: any folding beyond ASCII letters.  The reference-named
  * layer (acsm_add_pattern's nocase argument) keeps ignoring the flag as the
  * reference does. */
 int acm_automaton_set_nocase(acm_automaton *, int enable);
-/* 1 if the automaton matches case-insensitively, else 0 */
+/* 1 if every pattern of the automaton matches case-insensitively, else 0 (a
+ * mixed automaton: 0) */
 int acm_automaton_nocase(const acm_automaton *);
 
 /* trie -> fail links -> full DFA, reference state numbering preserved
@@ -197,6 +237,10 @@ size_t acm_scan_workspace_bytes(const acm_dfa *, size_t max_text);
  * d_text must be 16-byte aligned and readable up to n rounded up to 16.
  * Everything is enqueued on 'stream' (a hipStream_t, NULL = default stream);
  * nothing is synchronised.  n <= 2^31 - 17.
+ *
+ * A mixed automaton (acm_automaton_mixed_case): the records of this and of
+ * every other scan entry point are candidates, those of the nocase automaton
+ * of the same patterns; acm_case_matches_async keeps the exact ones.
  */
 int acm_scan_async(const acm_dfa *, const void *d_text, size_t n,
     long init_state, void *d_workspace, size_t workspace_bytes,
@@ -355,6 +399,47 @@ int acm_word_matches_async(const acm_dfa *, const int32_t *d_state_plane,
     const int32_t *d_off_plane, size_t max_records, const void *d_text, long text_origin,
     long text_end, const void *d_before, size_t before_len, int next_byte,
     const int32_t *d_seg_start, size_t segments, const uint8_t *word_set, int all_patterns,
+    int32_t *d_pat_out, int32_t *d_off_out, size_t out_capacity, void *d_tail_out,
+    void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Case sensitivity per pattern: the records of a mixed automaton (acm_automaton_add_ex) made exact.
+ * The scan of a mixed automaton has proved fold(text) == fold(pattern) for every entry of a record's
+ * match list; this pass keeps pattern p of length L >= 1 in the list of a record's state at offset o
+ * iff p ignores case (ACM_PATTERN_NOCASE), or every byte at [o - L + 1, o] equals the pattern's byte
+ * as added.  A byte outside the bytes given (in front of text_origin - before_len, or at or behind
+ * text_end) equals nothing: an exact pattern that reaches there is dropped.  Patterns of length 0
+ * never report; a cell that is no state writes nothing.
+ * Input: the planes of a scan enqueued with report = ACM_REPORT_STATE, or of the segment pass in STATE
+ * form (at most min([0], max_records) records are looked at), offsets in the coordinates the scan
+ * reported.  The text:
+ *   d_text      d_text[i] = the byte at offset text_origin + i, for offsets [text_origin, text_end)
+ *   d_before    the bytes at [text_origin - before_len, text_origin) (a streaming caller's previous
+ *               piece's tail)
+ * No next byte is needed: only bytes under a match are read.  No segment argument is needed either:
+ * after the segment pass every list entry of a clamped state lies inside its own text.
+ * Output, the scan's cell layout and overflow contract ([0] = full count, records, trailer at
+ * min(count + 1, out_capacity - 1)):
+ *   all_patterns == 0  one record per input record that has a kept entry: the first kept entry in
+ *                      match-list order (acm_automaton_state_matches) and the offset, unchanged
+ *   all_patterns != 0  one record per kept entry, list order, offsets ascending
+ *   trailer            the input trailer unchanged: the output can be the next scan's d_init_plane
+ *   d_tail_out         (NULL: not wanted) the last min(max_pattern_len, before_len + text_end -
+ *                      text_origin) bytes of before ++ text: the next piece's d_before.  It must not
+ *                      overlap d_before or d_text.
+ * For an automaton that is not mixed the call is legal and every entry is kept: the all form is
+ * acm_expand_matches_async's output and the head form the HEAD scan's records, bit for bit (entries of
+ * length 0 aside, which the scan reports and this pass, as the word pass, never does).
+ * Chained calls over consecutive pieces of a stream (each piece's d_before the previous piece's tail)
+ * give exactly the records of one call over the whole stream.  No read leaves [0, text_end -
+ * text_origin) of d_text or [0, before_len) of d_before, whatever the planes hold.  The output planes
+ * must not overlap the inputs.  Stream-ordered, no host sync, no allocation; argument errors return
+ * ACM_ERR_ARG before anything is enqueued.  A pass over the records (cost per record and per pattern
+ * byte under it, never per text byte); the scan kernels are not involved.  The workspace query is
+ * monotone and a multiple of 256. */
+size_t acm_case_workspace_bytes(size_t max_records);
+int acm_case_matches_async(const acm_dfa *, const int32_t *d_state_plane,
+    const int32_t *d_off_plane, size_t max_records, const void *d_text, long text_origin,
+    long text_end, const void *d_before, size_t before_len, int all_patterns,
     int32_t *d_pat_out, int32_t *d_off_out, size_t out_capacity, void *d_tail_out,
     void *d_workspace, size_t workspace_bytes, void *stream);
 
