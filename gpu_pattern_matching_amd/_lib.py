@@ -36,6 +36,8 @@ class ShardPlan(C.Structure):
 REPORT_HEAD, REPORT_STATE = 0, 1
 TALLY_ACCUMULATE, TALLY_ALL_PATTERNS = 1, 2
 PATTERN_NOCASE = 1
+POS_FROM_END = 1
+POS_UNBOUNDED = 0x7FFFFFFF
 
 
 class AcmError(RuntimeError):
@@ -60,6 +62,11 @@ NATIVE_API = {
     "acm_automaton_load_file_ex": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, C.c_uint]),
     "acm_automaton_pattern_flags": (C.c_int, [_vp, C.c_int]),
     "acm_automaton_mixed_case": (C.c_int, [_vp]),
+    "acm_automaton_set_position": (C.c_int, [_vp, C.c_int, C.c_int32, C.c_int32, C.c_uint]),
+    "acm_automaton_pattern_position": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_uint)]),
+    "acm_automaton_positioned": (C.c_int, [_vp]),
+    "acm_automaton_load_position_file": (C.c_int, [_vp, C.c_char_p]),
     "acm_automaton_set_nocase": (C.c_int, [_vp, C.c_int]),
     "acm_automaton_nocase": (C.c_int, [_vp]),
     "acm_automaton_compile": (C.c_int, [_vp]),
@@ -103,6 +110,9 @@ NATIVE_API = {
     "acm_case_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "acm_case_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_long, C.c_long, _vp, C.c_size_t, C.c_int,
                                          _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "acm_position_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "acm_position_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.c_long, C.c_long,
+                                             C.c_long, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
     "acm_tally_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_tally_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t,
                                           _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

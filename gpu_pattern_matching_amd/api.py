@@ -128,6 +128,32 @@ class Automaton:
         """compiled, and some patterns ignore case while others do not (acm_automaton_mixed_case)"""
         return bool(self.lib.acm_automaton_mixed_case(self.h))
 
+    def set_position(self, i, lo=0, hi=None, from_end=False):
+        """Where in its text pattern i may start (acm_automaton_set_position): lo <= start - text start <=
+        hi, or with from_end lo <= text end - start <= hi; hi None: no upper bound.  Before or after
+        compile(), but before the Matcher is made: the upload copies the windows."""
+        check(self.lib.acm_automaton_set_position(self.h, i, lo, _lib.POS_UNBOUNDED if hi is None else hi,
+                                                  _lib.POS_FROM_END if from_end else 0), "acm_automaton_set_position")
+
+    def position(self, i):
+        """(lo, hi or None, from_end) of pattern i (acm_automaton_pattern_position)"""
+        lo, hi, fl = C.c_int32(), C.c_int32(), C.c_uint()
+        check(self.lib.acm_automaton_pattern_position(self.h, i, C.byref(lo), C.byref(hi), C.byref(fl)),
+              "acm_automaton_pattern_position")
+        return lo.value, None if hi.value == _lib.POS_UNBOUNDED else hi.value, bool(fl.value & _lib.POS_FROM_END)
+
+    @property
+    def positioned(self):
+        """some pattern has a position constraint (acm_automaton_positioned)"""
+        return bool(self.lib.acm_automaton_positioned(self.h))
+
+    def load_position_file(self, path):
+        """constraints from a file of "<pattern index> <lo> <hi or *> [end]" lines; returns how many"""
+        n = self.lib.acm_automaton_load_position_file(self.h, str(path).encode())
+        if n < 0:
+            check(n, "acm_automaton_load_position_file")
+        return n
+
     def compile(self):
         check(self.lib.acm_automaton_compile(self.h), "acm_automaton_compile")
         return self
@@ -639,6 +665,105 @@ class Matcher:
             p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
             o = off.to_numpy(np.int32, m + 2, stream=self.stream)
             return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1])
+        finally:
+            for b in bufs:
+                b.free()
+
+    def position_async(self, pat_plane, off_plane, max_records, pat_out, off_out, out_capacity, info, report=0,
+                       seg_start=None, segments=0, lead_begin=0, text_end=0, open_end=-1, all_patterns=False,
+                       workspace=None, stream=None):
+        """Enqueue the position pass (acm_position_matches_async) over caller-owned device planes: states
+        (report=REPORT_STATE) or pattern indices (REPORT_HEAD: a HEAD scan, or the all-patterns output of
+        the word, case or expand pass), an entry kept where its pattern's window holds.  info: device
+        int32[4].  workspace: (ptr, nbytes), or None for a temporary one that lives until the stream has
+        passed it (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        tmp = None
+        if workspace is None:
+            nb = self.lib.acm_position_workspace_bytes(max_records)
+            tmp = DeviceArray(max(nb, 16))
+            workspace = (tmp.ptr, nb)
+        try:
+            check(self.lib.acm_position_matches_async(
+                self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, report, _ptr(seg_start), segments, lead_begin,
+                text_end, open_end, 1 if all_patterns else 0, _ptr(pat_out), _ptr(off_out), out_capacity, _ptr(info),
+                _ptr(workspace[0]), workspace[1], st), "acm_position_matches_async")
+        finally:
+            if tmp is not None:
+                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
+                tmp.free()
+
+    def scan_positions(self, text=None, texts=None, all_patterns=False, then=None, lead_begin=0, open_end="end",
+                       init_state=0, before=b"", out_capacity=None):
+        """Matches that obey the patterns' position constraints (Automaton.set_position): a REPORT_STATE
+        scan, the segment pass when texts is given (each text matched alone and its own [T0, Tend)), then
+        the position pass (acm_position_matches_async).  then: None, "case" or "words": that pass runs in
+        its all-patterns form in between and the position pass takes its pattern-form output, so a
+        constraint composes with exact-case or whole-word matching.  lead_begin: where the text in front
+        of the first start began (text given: where it began; may be negative).  open_end: where the last
+        text ends: "end" (with the bytes given), an int >= the bytes given, or None: unknown, end-anchored
+        entries of that text are dropped and counted.  before: the bytes in front of text, for then.
+        Returns (offsets, patterns, last_state, undecided)."""
+        if then not in (None, "case", "words"):
+            raise ValueError("then must be None, 'case' or 'words'")
+        if texts is not None:
+            t, starts = self.pack_segments(texts)
+        else:
+            t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
+                else np.ascontiguousarray(text, dtype=np.uint8)
+            starts = np.zeros(0, dtype=np.int32)
+        end = -1 if open_end is None else int(t.size) if isinstance(open_end, str) else int(open_end)
+        bf = np.frombuffer(bytes(before), dtype=np.uint8)
+        self.reserve(max(t.size, 1))
+        d = DeviceArray.from_numpy(t, stream=self.stream)
+        d_bf = DeviceArray.from_numpy(bf, stream=self.stream) if bf.size else None
+        nseg = int(starts.size)
+        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
+        max_records = self.plane_capacity - 2
+        cap = self.plane_capacity
+        ocap = out_capacity if out_capacity is not None else (8 * cap if all_patterns or then else cap)
+        ws_bytes = self.lib.acm_position_workspace_bytes(max(max_records, 8 * cap))
+        bufs = [DeviceArray(max(ws_bytes, 16)), DeviceArray(ocap * 4), DeviceArray(ocap * 4), DeviceArray(16)]
+        ws, pat, off, info = bufs
+        bufs += [b for b in (d, d_bf, d_st) if b is not None]
+        try:
+            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
+            sp, so, report = self.pat_plane, self.off_plane, _lib.REPORT_STATE
+            if nseg:
+                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
+                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
+                bufs += sb
+                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
+                                   report=_lib.REPORT_STATE, workspace=(sb[0].ptr, seg_ws))
+                sp, so = sb[1], sb[2]
+            if then:
+                icap = 8 * cap
+                nb = (self.lib.acm_case_workspace_bytes if then == "case" else self.lib.acm_word_workspace_bytes)(max_records)
+                tb = [DeviceArray(max(nb, 16)), DeviceArray(icap * 4), DeviceArray(icap * 4)]
+                bufs += tb
+                if then == "case":
+                    self.case_async(sp, so, max_records, d, 0, t.size, tb[1], tb[2], icap, before=d_bf,
+                                    before_len=int(bf.size), all_patterns=True, workspace=(tb[0].ptr, nb))
+                else:
+                    self.word_async(sp, so, max_records, d, 0, t.size, tb[1], tb[2], icap, before=d_bf,
+                                    before_len=int(bf.size), seg_start=d_st, segments=nseg, all_patterns=True,
+                                    workspace=(tb[0].ptr, nb))
+                n = int(tb[1].to_numpy(np.int32, 1, stream=self.stream)[0])
+                if n > icap - 2:
+                    raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_positions", "%d records but planes hold %d"
+                                   % (n, icap - 2))
+                sp, so, report, max_records = tb[1], tb[2], _lib.REPORT_HEAD, icap - 2
+            self.position_async(sp, so, max_records, pat, off, ocap, info, report=report, seg_start=d_st, segments=nseg,
+                                lead_begin=int(lead_begin), text_end=int(t.size), open_end=end, all_patterns=all_patterns,
+                                workspace=(ws.ptr, ws_bytes))
+            m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
+            if m > ocap - 2:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_positions", "%d records but planes hold %d"
+                               % (m, ocap - 2))
+            p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
+            o = off.to_numpy(np.int32, m + 2, stream=self.stream)
+            und = int(info.to_numpy(np.int32, 4, stream=self.stream)[0])
+            return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1]), und
         finally:
             for b in bufs:
                 b.free()

@@ -53,7 +53,7 @@ double now_us()
 	printf("\nUsage:\n"
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
-	       "             [-w cpu_threads] [-R max] [-I file] [-tvxFMAiSWcn]\n"
+	       "             [-w cpu_threads] [-R max] [-I file] [-P file] [-tvxFMAiSWcn]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -80,6 +80,13 @@ double now_us()
 	       "                 exact: every buffer's records go through the case pass on the device before they\n"
 	       "                 are bucketed, printed, counted (-c) or numbered (-n).  With -i it is a second -p\n"
 	       "                 (extension; not with -W or -F)\n"
+	       "  -P file        position constraints, one per line: '<pattern index> <lo> <hi or *> [end]' -- the pattern\n"
+	       "                 may start lo..hi bytes into its text, with 'end' lo..hi bytes in front of its end\n"
+	       "                 ('^': 0 0; '$' for a pattern of L bytes: L L end).  Indices count the patterns of -p, then\n"
+	       "                 those of -I.  Needs -S: the texts are the files (with -t: the lines).  Composes with -A,\n"
+	       "                 -i, -c, -n and with -W or -I.  An end-anchored candidate in a file that goes on in the\n"
+	       "                 next buffer cannot be decided: it is counted and reported as an error at exit\n"
+	       "                 (extension; not with -F)\n"
 	       "  -S             every input unit is its own text: a file, or with -t a line; no match\n"
 	       "                 spans two of them (extension; data appended under -F continues its file\n"
 	       "                 when the worker's previous chunk came from the same file)\n"
@@ -133,10 +140,11 @@ std::vector<std::string> regular_files_in(std::string dir)
 }
 
 struct Config {
-	std::string pat_path, data_path, loose_path;   // loose_path: -I
+	std::string pat_path, data_path, loose_path, pos_path;   // loose_path: -I, pos_path: -P
 	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0,
 	    words = 0, count = 0, lineno = 0;
 	int cased = 0;           // -I without -i: the records go through the case pass
+	int pos = 0;             // -P: the records go through the position pass
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
 	long global_ws = -1, local_ws = -1, chunk = -1;
@@ -175,6 +183,14 @@ struct Buffer {   // one of the two staging buffers of a worker
 	size_t word_ws_bytes = 0;
 	void *d_case_pat = nullptr, *d_case_off = nullptr, *d_case_ws = nullptr;   // -I only
 	size_t case_ws_bytes = 0;
+	// -P only: the position pass's planes, workspace and info (pinned twin: [0] = undecided entries dropped)
+	void *d_pos_pat = nullptr, *d_pos_off = nullptr, *d_pos_ws = nullptr, *d_pos_info = nullptr;
+	int32_t *h_pos_info = nullptr;
+	size_t pos_ws_bytes = 0, pos_cap = 0;
+	long lead_begin = 0;         // -P: where the text that goes on into this buffer began, in its stream's coordinates (<= 0)
+	bool end_known = false;      // -P: the stream's last text ends with the stream (its file, or with -t its line, is finished)
+	bool last_of_input = false;  // -P: nothing of the worker's input follows this buffer
+	int32_t end_start = 0;       // -P: the start behind the last text when end_known (copied from here)
 	// -c only: the grid of file starts of this buffer's stream, the counts per start, of the records in front
 	// of the first start (they belong to cnt_prev_file) and of the whole buffer, and their pinned host twins
 	void *d_cnt_start = nullptr, *d_cnt_rows = nullptr, *d_cnt_lead = nullptr, *d_cnt_total = nullptr, *d_cnt_ws = nullptr;
@@ -212,6 +228,9 @@ struct Worker {
 	long last_state = 0;
 	int seg_file = -1;        // -S: file of the last chunk submitted
 	bool seg_open = false;    // -S -t: that chunk ended inside a line
+	size_t text_bytes = 0;    // -P: bytes of the text in progress that the buffers prepared so far hold
+	bool file_closed = false; // -P: the file of the last chunk filled has been read to its end
+	uint64_t undecided = 0;   // -P: end-anchored entries dropped because their text went on in the next buffer
 	void *d_tail[2] = { nullptr, nullptr };   // -W, -I: the last max_pattern_len bytes of the stream so far, ping-pong
 	int tail_cur = 0;
 	size_t tail_len = 0;
@@ -296,7 +315,17 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 		CK(acm_rt_host_alloc((void **)&b.h_cnt_lead, 64));
 		CK(acm_rt_host_alloc((void **)&b.h_cnt_total, 64));
 	}
-	if (c.all_patterns) {
+	if (c.pos) {
+		b.pos_cap = c.all_patterns ? size * kAllFactor + 2 : size + 2;
+		b.pos_ws_bytes = acm_position_workspace_bytes(size * kAllFactor);
+		CK(acm_rt_malloc(&b.d_pos_pat, b.pos_cap * 4));
+		CK(acm_rt_malloc(&b.d_pos_off, b.pos_cap * 4));
+		CK(acm_rt_malloc(&b.d_pos_ws, b.pos_ws_bytes));
+		CK(acm_rt_malloc(&b.d_pos_info, 16));
+		CK(acm_rt_host_alloc((void **)&b.h_pos_info, 64));
+		b.h_pos_info[0] = 0;
+	}
+	if (c.all_patterns || (c.pos && (c.words || c.cased))) {   // (-P: the word or case pass hands every kept pattern on)
 		b.expand_ws_bytes = acm_expand_workspace_bytes(size);
 		// every pattern of every final state's list: more records than text bytes when patterns nest
 		// (aaa, aaaa, aaaaa over a run of a's); the planes hold kAllFactor per byte, beyond that the
@@ -399,6 +428,11 @@ void prepare(Worker &w, Buffer &b)
 			w.seg_file = b.file_ids[i];
 			w.seg_open = b.h_sizes[i] > 0 && b.h_data[b.h_indices[i] + b.h_sizes[i] - 1] != '\n';
 		}
+		// -P: how much of the text that goes on into this buffer the earlier buffers held, and whether the
+		// last text is known to end here
+		b.lead_begin = -(long)w.text_bytes;
+		w.text_bytes = b.seg_starts.empty() ? w.text_bytes + stream_len : stream_len - (size_t)b.seg_starts.back();
+		b.end_known = w.file_closed || (c.text_mode && chunks > 0 && !w.seg_open);
 	}
 }
 
@@ -459,14 +493,18 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 	// final states instead of head patterns where a pass over the records follows: the segment pass
 	// clamps every one to its own text, the word pass keeps whole words, the case pass (-I) the exact
 	// patterns where the text has their case, the expansion (-A) lists them
-	const bool states = c.segmented || c.words || c.all_patterns || c.cased;
+	const bool states = c.segmented || c.words || c.all_patterns || c.cased;   // (-P needs -S)
 	sb.report = states ? ACM_REPORT_STATE : ACM_REPORT_HEAD;
 	if (c.segmented && !b.seg_starts.empty())
 		CK(acm_rt_memcpy_h2d(b.d_seg_start, b.seg_starts.data(), b.seg_starts.size() * 4, s));
+	if (c.pos && b.end_known) {   // a start at the stream's end, for the position pass alone: the last text is closed
+		b.end_start = (int32_t)b.stream_len;
+		CK(acm_rt_memcpy_h2d((int32_t *)b.d_seg_start + b.seg_starts.size(), &b.end_start, 4, s));
+	}
 	CK(acm_scan_batch_async(w.dfa, &sb));
 	if (c.segmented) {
 		CK(acm_segment_matches_async(w.dfa, pat, off, cap - 2, (const int32_t *)b.d_seg_start, b.seg_starts.size(),
-		    (long)b.stream_len, (c.all_patterns || c.words || c.cased) ? ACM_REPORT_STATE : ACM_REPORT_HEAD,
+		    (long)b.stream_len, (c.all_patterns || c.words || c.cased || c.pos) ? ACM_REPORT_STATE : ACM_REPORT_HEAD,
 		    (int32_t *)b.d_seg_pat, (int32_t *)b.d_seg_off, nullptr, cap, nullptr, b.d_seg_ws, b.seg_ws_bytes, s));
 		pat = (int32_t *)b.d_seg_pat;
 		off = (int32_t *)b.d_seg_off;
@@ -489,43 +527,61 @@ void finish(Worker &w, Buffer &b, int next_byte)
 	int32_t *pat = b.rec_pat, *off = b.rec_off;
 	size_t cap = b.scan_cap;
 	if (c.words) {   // whole words; with -A every word-bounded pattern (the expansion's place)
-		int32_t *wp = (int32_t *)(c.all_patterns ? b.d_pat_all : b.d_word_pat);
-		int32_t *wo = (int32_t *)(c.all_patterns ? b.d_off_all : b.d_word_off);
-		const size_t wcap = c.all_patterns ? b.all_cap : b.scan_cap;
+		const bool every = c.all_patterns || c.pos;   // (-P: the position pass picks the first kept one)
+		int32_t *wp = (int32_t *)(every ? b.d_pat_all : b.d_word_pat);
+		int32_t *wo = (int32_t *)(every ? b.d_off_all : b.d_word_off);
+		const size_t wcap = every ? b.all_cap : b.scan_cap;
 		CK(acm_word_matches_async(w.dfa, pat, off, cap - 2, b.text, 0, (long)b.stream_len,
 		    w.tail_len ? w.d_tail[w.tail_cur] : nullptr, w.tail_len, next_byte,
 		    c.segmented ? (const int32_t *)b.d_seg_start : nullptr, c.segmented ? b.seg_starts.size() : 0, nullptr,
-		    c.all_patterns, wp, wo, wcap, w.d_tail[w.tail_cur ^ 1], b.d_word_ws, b.word_ws_bytes, s));
+		    every, wp, wo, wcap, w.d_tail[w.tail_cur ^ 1], b.d_word_ws, b.word_ws_bytes, s));
 		w.tail_cur ^= 1;
 		w.tail_len = std::min((size_t)w.sh->max_pattern_len, w.tail_len + b.stream_len);
 		pat = wp;
 		off = wo;
 		cap = wcap;
-		if (c.all_patterns)
+		if (every)
 			CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
 	} else if (c.cased) {   // the candidates of a mixed automaton made exact; with -A every kept pattern (the expansion's place)
-		int32_t *cp = (int32_t *)(c.all_patterns ? b.d_pat_all : b.d_case_pat);
-		int32_t *co = (int32_t *)(c.all_patterns ? b.d_off_all : b.d_case_off);
-		const size_t ccap = c.all_patterns ? b.all_cap : b.scan_cap;
+		const bool every = c.all_patterns || c.pos;   // (-P: the position pass picks the first kept one)
+		int32_t *cp = (int32_t *)(every ? b.d_pat_all : b.d_case_pat);
+		int32_t *co = (int32_t *)(every ? b.d_off_all : b.d_case_off);
+		const size_t ccap = every ? b.all_cap : b.scan_cap;
 		// the tail of the worker's stream so far is this buffer's before: a pattern that began in the buffer
 		// in front is compared whole (-S: the segment pass has left no entry that reaches into another text)
 		CK(acm_case_matches_async(w.dfa, pat, off, cap - 2, b.text, 0, (long)b.stream_len,
-		    w.tail_len ? w.d_tail[w.tail_cur] : nullptr, w.tail_len, c.all_patterns, cp, co, ccap, w.d_tail[w.tail_cur ^ 1],
+		    w.tail_len ? w.d_tail[w.tail_cur] : nullptr, w.tail_len, every, cp, co, ccap, w.d_tail[w.tail_cur ^ 1],
 		    b.d_case_ws, b.case_ws_bytes, s));
 		w.tail_cur ^= 1;
 		w.tail_len = std::min((size_t)w.sh->max_pattern_len, w.tail_len + b.stream_len);
 		pat = cp;
 		off = co;
 		cap = ccap;
-		if (c.all_patterns)
+		if (every)
 			CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
-	} else if (c.all_patterns) {   // every pattern of each final state's match list
+	} else if (c.all_patterns && !c.pos) {   // every pattern of each final state's match list
 		CK(acm_expand_matches_async(w.dfa, pat, off, cap - 2, (int32_t *)b.d_pat_all, (int32_t *)b.d_off_all,
 		    b.all_cap, b.d_expand_ws, b.expand_ws_bytes, s));
 		pat = (int32_t *)b.d_pat_all;
 		off = (int32_t *)b.d_off_all;
 		cap = b.all_cap;
 		CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
+	}
+	if (c.pos) {
+		// the windows of the patterns, each in its own text: the files' (-t: lines') starts of this stream, the
+		// text that goes on from the buffer in front, and the end of the last one where it is known.  Behind
+		// the word or case pass the planes hold patterns (every kept one), else the segment pass's states.
+		const bool heads = c.words || c.cased;
+		CK(acm_position_matches_async(w.dfa, pat, off, cap - 2, heads ? ACM_REPORT_HEAD : ACM_REPORT_STATE,
+		    (const int32_t *)b.d_seg_start, b.seg_starts.size() + (b.end_known ? 1 : 0), b.lead_begin, (long)b.stream_len,
+		    b.last_of_input ? (long)b.stream_len : -1L, c.all_patterns, (int32_t *)b.d_pos_pat, (int32_t *)b.d_pos_off,
+		    b.pos_cap, (int32_t *)b.d_pos_info, b.d_pos_ws, b.pos_ws_bytes, s));
+		pat = (int32_t *)b.d_pos_pat;
+		off = (int32_t *)b.d_pos_off;
+		cap = b.pos_cap;
+		CK(acm_rt_memcpy_d2h(b.h_pos_info, b.d_pos_info, 16, s));
+		if (c.all_patterns && !heads)
+			CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
 	}
 	if (c.lineno) {
 		// the lines of this buffer's stream, chained to the buffer in front of it on the device; then the
@@ -585,11 +641,13 @@ void collect(Worker &w, Buffer &b)
 {
 	const Config &c = w.sh->cfg;
 	CK(acm_rt_event_sync(b.done));   // (this buffer's copies; the next buffer's scan may still be running)
-	if (c.all_patterns && b.h_all_count && (size_t)*b.h_all_count > b.all_cap - 2) {
-		fprintf(stderr, "ERROR: -A produced %d records for one buffer, the planes hold %zu; use a smaller -G/-B\n",
-		    *b.h_all_count, b.all_cap - 2);
+	if (b.h_all_count && (size_t)*b.h_all_count > b.all_cap - 2) {
+		fprintf(stderr, "ERROR: %s produced %d records for one buffer, the planes hold %zu; use a smaller -G/-B\n",
+		    c.all_patterns ? "-A" : "-P", *b.h_all_count, b.all_cap - 2);
 		exit(1);
 	}
+	if (c.pos)
+		w.undecided += (uint64_t)b.h_pos_info[0];
 	if (c.count && !w.sh->pat_iid.empty()) {
 		if (b.cnt_starts.empty()) {   // the whole buffer goes on with the file in front of it
 			if (b.cnt_prev_file >= 0)
@@ -712,9 +770,12 @@ void *worker_main(void *arg)
 			got = fill_binary(b, c, sh.fds[cur], cur);
 		w.bytes += got;
 		w.lines += lines;
+		if (got)
+			w.file_closed = false;
 		const bool full = b.chunks >= G || b.bytes + 2 > size;
 		bool file_done = (got == 0) && !full;
 		if (file_done) {   // current file exhausted: next one of this worker
+			w.file_closed = true;
 			if (!c.follow) {
 				if (fp) {
 					fclose(fp);
@@ -737,6 +798,7 @@ void *worker_main(void *arg)
 			// the scan starts in the state the previous buffer ended in: taken from that buffer's planes on
 			// the device, so this one is enqueued BEFORE the host waits for the previous one and walks its results
 			prepare(w, b);
+			b.last_of_input = last;
 			if (in_flight && c.words)   // b's first byte ends the previous buffer's stream
 				finish(w, w.buf[filling ^ 1], first_byte(c, b));
 			submit(w, b, in_flight ? &w.buf[filling ^ 1] : nullptr);   // GPU works on b while we read into the other buffer
@@ -770,7 +832,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -803,6 +865,7 @@ int main(int argc, char **argv)
 		case 'c': c.count = 1; break;
 		case 'n': c.lineno = 1; break;
 		case 'I': c.loose_path = optarg; break;
+		case 'P': c.pos_path = optarg; break;
 		default: usage();
 		}
 	}
@@ -832,6 +895,18 @@ int main(int argc, char **argv)
 		err++;
 	}
 	c.cased = !c.loose_path.empty() && !c.nocase;
+	if (!c.pos_path.empty() && access(c.pos_path.c_str(), R_OK) != 0) {
+		printf("ERROR: File '%s' does not exist\n", c.pos_path.c_str()); err++;
+	}
+	if (!c.pos_path.empty() && !c.segmented) {   // a window counts from the bounds of a text: the texts must be told apart
+		printf("ERROR: -P needs -S: a position counts from the start or the end of a file (with -t: of a line)\n");
+		err++;
+	}
+	if (!c.pos_path.empty() && c.follow) {
+		printf("ERROR: -P cannot be combined with -F: the end of a paused input is not known\n");
+		err++;
+	}
+	c.pos = !c.pos_path.empty();
 	if (c.lineno && c.text_mode) {
 		printf("ERROR: -n needs binary mode: -t already makes every line a chunk\n");
 		err++;
@@ -900,6 +975,10 @@ int main(int argc, char **argv)
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}
+	if (c.pos && acm_automaton_load_position_file(aut, c.pos_path.c_str()) < 0) {
+		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
+		return 1;
+	}
 	CK(acm_automaton_compile(aut));
 	const int states = acm_automaton_num_states(aut);
 	const int np = acm_automaton_num_patterns(aut);
@@ -938,8 +1017,10 @@ int main(int argc, char **argv)
 	pthread_barrier_wait(&sh.ready);
 	const double t0 = now_us();
 	size_t matches = 0, reported = 0, bytes = 0, lines = 0, rounds = 0;
+	uint64_t undecided = 0;
 	for (auto &w : workers) {
 		pthread_join(w.thread, nullptr);
+		undecided += w.undecided;
 		matches += w.matches;
 		reported += w.reported;
 		bytes += w.bytes;
@@ -976,5 +1057,9 @@ int main(int argc, char **argv)
 	printf("-----------------------------------\n\n");
 	for (acm_dfa *dfa : sh.dfas)
 		acm_dfa_release(dfa);
+	if (undecided) {   // no silent loss: the counts and records above are without them
+		printf("ERROR: %lu end-anchored candidates lie in files that span buffers (raise -B/-G)\n", (unsigned long)undecided);
+		return 1;
+	}
 	return 0;
 }

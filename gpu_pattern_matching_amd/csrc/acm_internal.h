@@ -51,6 +51,11 @@ struct acm_automaton {
 		std::vector<unsigned char> bytes;
 		int iid;
 		unsigned flags = 0;                    // ACM_PATTERN_* as added (acm_automaton_add_ex)
+		// where in its text the pattern may start (acm_automaton_set_position); the default is no constraint.
+		// compile never reads these: acm_dfa_upload copies them for the position pass (position.hip)
+		int32_t pos_lo = 0, pos_hi = INT32_MAX;
+		unsigned pos_flags = 0;
+		bool positioned() const { return pos_lo != 0 || pos_hi != INT32_MAX || pos_flags != 0; }
 	};
 	std::vector<Pattern> patterns;         // bytes folded by compile when nocase: every table is built from these
 	int max_pattern_len = 0;

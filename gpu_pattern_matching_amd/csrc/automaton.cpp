@@ -119,6 +119,121 @@ extern "C" int acm_automaton_pattern_flags(const acm_automaton *a, int index)
 	return (int)a->patterns[index].flags;
 }
 
+// ---- position constraints ----------------------------------------------------
+
+extern "C" int acm_automaton_set_position(acm_automaton *a, int index, int32_t lo, int32_t hi, unsigned flags)
+{
+	if (!a || index < 0 || index >= (int)a->patterns.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_set_position: index out of range");
+	if (lo < 0 || hi < 0)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_set_position: negative bound (%d, %d)", lo, hi);
+	if (flags & ~(unsigned)ACM_POS_FROM_END)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_set_position: unknown flag bits 0x%x", flags & ~(unsigned)ACM_POS_FROM_END);
+	acm_automaton::Pattern &p = a->patterns[index];
+	p.pos_lo = lo;
+	p.pos_hi = hi;
+	p.pos_flags = flags;
+	return ACM_OK;
+}
+
+extern "C" int acm_automaton_pattern_position(const acm_automaton *a, int index, int32_t *lo, int32_t *hi, unsigned *flags)
+{
+	if (!a || index < 0 || index >= (int)a->patterns.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_pattern_position: index out of range");
+	const acm_automaton::Pattern &p = a->patterns[index];
+	if (lo) *lo = p.pos_lo;
+	if (hi) *hi = p.pos_hi;
+	if (flags) *flags = p.pos_flags;
+	return ACM_OK;
+}
+
+extern "C" int acm_automaton_positioned(const acm_automaton *a)
+{
+	if (a)
+		for (auto &p : a->patterns)
+			if (p.positioned())
+				return 1;
+	return 0;
+}
+
+// One unsigned decimal field of a position-file line: digits up to a blank or the end, at most INT32_MAX.
+static bool pos_field(const char *&s, int32_t &out)
+{
+	while (*s == ' ' || *s == '\t')
+		s++;
+	if (!isdigit((unsigned char)*s))
+		return false;
+	int64_t v = 0;
+	for (; isdigit((unsigned char)*s); s++) {
+		v = v * 10 + (*s - '0');
+		if (v > INT32_MAX)
+			return false;
+	}
+	if (*s && *s != ' ' && *s != '\t')
+		return false;
+	out = (int32_t)v;
+	return true;
+}
+
+extern "C" int acm_automaton_load_position_file(acm_automaton *a, const char *path)
+{
+	if (!a || !path)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_load_position_file: bad arguments");
+	FILE *fp = fopen(path, "r");
+	if (!fp)
+		return acm::fail(ACM_ERR_IO, "cannot open position file '%s': %s", path, strerror(errno));
+	struct Line {
+		int32_t index, lo, hi;
+		unsigned flags;
+	};
+	std::vector<Line> lines;   // applied only when the whole file has parsed
+	std::vector<char> buf(acm::kMaxPatternLine);
+	int line_no = 0, rc = ACM_OK;
+	while (rc == ACM_OK && fgets(buf.data(), (int)buf.size(), fp)) {
+		line_no++;
+		std::string line(buf.data());
+		while (!line.empty() && (line.back() == '\n' || line.back() == '\r' || line.back() == ' ' || line.back() == '\t'))
+			line.pop_back();
+		const char *s = line.c_str();
+		while (*s == ' ' || *s == '\t')
+			s++;
+		if (!*s || *s == '#')
+			continue;
+		Line l{ 0, 0, INT32_MAX, 0 };
+		bool ok = pos_field(s, l.index) && pos_field(s, l.lo);
+		if (ok) {
+			while (*s == ' ' || *s == '\t')
+				s++;
+			if (*s == '*' && (!s[1] || s[1] == ' ' || s[1] == '\t'))
+				s++;
+			else
+				ok = pos_field(s, l.hi);
+		}
+		if (ok) {
+			while (*s == ' ' || *s == '\t')
+				s++;
+			if (!strcmp(s, "end"))
+				l.flags = ACM_POS_FROM_END;
+			else if (*s)
+				ok = false;
+		}
+		if (!ok)
+			rc = acm::fail(ACM_ERR_PARSE, "%s:%d: not '<pattern index> <lo> <hi or *> [end]'", path, line_no);
+		else if (l.index >= (int)a->patterns.size())
+			rc = acm::fail(ACM_ERR_PARSE, "%s:%d: pattern index %d out of range (%zu patterns)", path, line_no, l.index,
+			    a->patterns.size());
+		else
+			lines.push_back(l);
+	}
+	fclose(fp);
+	if (rc != ACM_OK)
+		return rc;
+	for (const Line &l : lines)
+		if ((rc = acm_automaton_set_position(a, l.index, l.lo, l.hi, l.flags)) != ACM_OK)
+			return rc;
+	return (int)lines.size();
+}
+
 // ---- pattern file ------------------------------------------------------------
 
 static int hex_nibble(unsigned char c)

@@ -58,6 +58,9 @@ struct acm_dfa {
 	uint32_t *d_case_ent = nullptr;      // [patterns][2] {word index of the pattern in d_case_pool, or kCaseAny: ignores case, or
 	                                     // kCaseNever: length 0; length}: one 8-byte load per list entry
 	uint32_t *d_case_pool = nullptr;     // the exact patterns' bytes as added, each padded to whole words, one spare word behind
+	// a positioned automaton only (acm_automaton_positioned at upload), for the position pass (position.hip); null otherwise
+	bool positioned = false;
+	int32_t *d_pos_ent = nullptr;        // [patterns][4] {lo, hi, flags, length}: one 16-byte load per entry
 	size_t device_bytes = 0;
 	void *arena = nullptr;               // one allocation for the small tables (device_dfa.hip, upload_small)
 	size_t arena_bytes = 0, arena_used = 0;

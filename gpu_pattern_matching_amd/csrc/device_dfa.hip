@@ -259,6 +259,20 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 			rc = upload(&d->d_case_ent, ent.data(), ent.size(), &d->device_bytes);
 			if (rc == ACM_OK) rc = upload(&d->d_case_pool, pool.data(), pool.size(), &d->device_bytes);
 		}
+		// a positioned automaton (acm_automaton_positioned): every pattern's window and length, one 16-byte
+		// load per entry of the position pass (position.hip).  An allocation of its own, as above.
+		d->positioned = acm_automaton_positioned(a) != 0;
+		if (rc == ACM_OK && d->positioned) {
+			std::vector<int32_t> ent(4 * a->patterns.size());
+			for (size_t i = 0; i < a->patterns.size(); i++) {
+				const acm_automaton::Pattern &p = a->patterns[i];
+				ent[4 * i] = p.pos_lo;
+				ent[4 * i + 1] = p.pos_hi;
+				ent[4 * i + 2] = (int32_t)p.pos_flags;
+				ent[4 * i + 3] = (int32_t)p.bytes.size();
+			}
+			rc = upload(&d->d_pos_ent, ent.data(), ent.size(), &d->device_bytes);
+		}
 	} catch (const std::bad_alloc &) {
 		rc = acm::fail(ACM_ERR_NOMEM, "acm_dfa_upload: out of host memory");
 	}
@@ -316,6 +330,7 @@ extern "C" void acm_dfa_release(acm_dfa *d)
 		free_small(d, d->d_pat_len);
 		hipFree(d->d_case_ent);
 		hipFree(d->d_case_pool);
+		hipFree(d->d_pos_ent);
 		free_small(d, d->d_depth);
 		free_small(d, d->d_class);
 		free_small(d, d->d_sv_bloom);

@@ -114,6 +114,40 @@ int acm_automaton_load_file_ex(acm_automaton *, const char *path, int hex,
 int acm_automaton_pattern_flags(const acm_automaton *, int index);
 int acm_automaton_mixed_case(const acm_automaton *);
 
+/* Position constraints: where in its text a pattern may match.  Pattern p of length L >= 1 that ends
+ * at offset o starts at a = o - L + 1; its text occupies [T0, Tend).  With the window (lo, hi, flags):
+ *   flags 0            p is kept iff lo <= a - T0 <= hi    (counted from the start of the text)
+ *   ACM_POS_FROM_END   p is kept iff lo <= Tend - a <= hi  (counted back from the end of the text)
+ * hi == ACM_POS_UNBOUNDED: no upper bound.  All arithmetic is in int64.  The default (0,
+ * ACM_POS_UNBOUNDED, 0) is "no constraint"; any other triple is a constraint, and an automaton with one
+ * is POSITIONED (acm_automaton_positioned = 1).  lo > hi is legal and never matches; lo < 0, hi < 0,
+ * unknown flag bits or a bad index are ACM_ERR_ARG.  A pattern of length 0 is never kept.
+ * acm_automaton_pattern_position returns the window as set (any of the three pointers may be NULL).
+ * Windows do not enter acm_automaton_compile: tables, digests, self-tests and acm_dfa_device_bytes of an
+ * automaton without constraints are what they were, and no scan looks at a window.  The records of a
+ * scan are made to obey them by acm_position_matches_async, which reads a copy that acm_dfa_upload
+ * takes: windows may be set before or after acm_automaton_compile, but a window set after
+ * acm_dfa_upload does not reach that acm_dfa.
+ * How the usual source forms map to windows (no parser for them is provided):
+ *   Snort offset, depth     lo = offset, hi = offset + depth - L       flags 0
+ *   ^                       (0, 0, 0)
+ *   $                       (L, L, ACM_POS_FROM_END)
+ *   ClamAV n,ms             (n, n + ms, 0)
+ *   ClamAV EOF-n,ms         (n - ms, n, ACM_POS_FROM_END)
+ * The reference-named layer is unchanged: acsm_add_pattern keeps ignoring its offset and depth
+ * arguments, as the reference's search does.
+ * acm_automaton_load_position_file reads one constraint per line, "<pattern index> <lo> <hi or *> [end]"
+ * (decimal; * = ACM_POS_UNBOUNDED; end = ACM_POS_FROM_END).  A line whose first non-blank byte is '#' and
+ * blank lines are skipped.  A malformed line or an index out of range is ACM_ERR_PARSE and
+ * acm_last_error names the line; nothing is applied then.  Returns the number of constraints applied. */
+enum { ACM_POS_FROM_END = 1 };
+#define ACM_POS_UNBOUNDED INT32_MAX
+int acm_automaton_set_position(acm_automaton *, int index, int32_t lo, int32_t hi, unsigned flags);
+int acm_automaton_pattern_position(const acm_automaton *, int index, int32_t *lo, int32_t *hi,
+    unsigned *flags);
+int acm_automaton_positioned(const acm_automaton *);
+int acm_automaton_load_position_file(acm_automaton *, const char *path);
+
 /* ASCII case-insensitive matching for every pattern of the automaton.  With
  * it on, fold(b) = b - 0x20 for 'a' <= b <= 'z' and b otherwise (toupper in
  * the C locale; bytes >= 0x80 are never folded), and a scan of text T gives
@@ -441,6 +475,54 @@ int acm_case_matches_async(const acm_dfa *, const int32_t *d_state_plane,
     const int32_t *d_off_plane, size_t max_records, const void *d_text, long text_origin,
     long text_end, const void *d_before, size_t before_len, int all_patterns,
     int32_t *d_pat_out, int32_t *d_off_out, size_t out_capacity, void *d_tail_out,
+    void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Position constraints (acm_automaton_set_position) applied to the records of any pass: an entry is
+ * kept iff its pattern's window holds in the text the record belongs to.  No text is read: the predicate
+ * needs the pattern's length, the record's offset and the bounds of its text.
+ * Input: planes in the scan's cell layout; at most min([0], max_records) records are looked at.  report
+ * says what the cells of d_pat_plane are:
+ *   ACM_REPORT_STATE  final states (a STATE scan, the segment pass in STATE form).  The entries of a
+ *                     record are its state's match list (acm_automaton_state_matches).
+ *   ACM_REPORT_HEAD   pattern indices (a HEAD scan, or the all-patterns output of the word pass, the
+ *                     case pass or acm_expand_matches_async).  Each record is one entry; a maximal run
+ *                     of consecutive records with equal offset counts as one offset.  This is how the
+ *                     pass composes with the word and case passes, which take states and give patterns.
+ * Which text a record belongs to: d_seg_start[segments] as in acm_tally_matches_async (non-decreasing,
+ * empty segments and starts at or beyond text_end allowed).  A record at o belongs to the last k with
+ * start[k] <= o, and T0 = start[k].  A record in front of start[0], or any record when segments == 0,
+ * belongs to the lead text: T0 = lead_begin, which may lie far in front of the piece or be negative (a
+ * text that began in an earlier buffer).  Tend is the next start if that start is <= text_end.  Otherwise
+ * the text is open and Tend = open_end: the known end (>= text_end, same coordinates; text_end itself
+ * when the stream ends there), or -1: unknown.  An ACM_POS_FROM_END entry of an open text whose end is
+ * unknown is UNDECIDED: it is dropped and counted.  Nothing is clamped: for per-text matching run the
+ * segment pass first.  An unconstrained entry is always kept, whatever its text is.
+ * Output, the scan's cell layout and overflow contract ([0] = full count, records, trailer -- the input
+ * trailer unchanged -- at min(count + 1, out_capacity - 1)):
+ *   all_patterns != 0  one record per kept entry, in list order (STATE input) or input order (HEAD
+ *                      input), offsets ascending
+ *   all_patterns == 0  the first kept entry per record (STATE input) or per run of equal offsets (HEAD
+ *                      input)
+ *   d_info             int32[4], required, written whole: [0] undecided entries dropped, [1..3] 0.  In
+ *                      the first-entry form only the entries in front of the first kept one of their
+ *                      record or run are looked at, and only those are counted.
+ * For an automaton that is not positioned the call is legal and every entry is kept: STATE input in the
+ * all form is acm_expand_matches_async's output, in the first form the HEAD scan's records, and HEAD
+ * input in the all form is the input, all bit for bit (entries of length 0 aside, which the scan reports
+ * and this pass, as the word and case passes, never does).  A cell that is neither a state nor a pattern
+ * index writes nothing.  No read leaves the input planes, the starts and the library's tables, whatever
+ * the planes hold.  The outputs must not overlap the inputs.  Stream-ordered, no host sync, no
+ * allocation, no host read of device data; argument errors (a NULL plane, output or d_info, out_capacity
+ * < 2, an unknown report, open_end outside {-1} and [text_end, inf), segments without starts, a short
+ * workspace) return ACM_ERR_ARG before anything is enqueued.  Two launches over the records
+ * (csrc/position.hip); cost per record and per list entry, never per text byte (a first-form run of
+ * HEAD input looks back over its own run: bounded by the longest match list for the planes of a pass).
+ * The workspace query is monotone and a multiple of 256. */
+size_t acm_position_workspace_bytes(size_t max_records);
+int acm_position_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
+    const int32_t *d_off_plane, size_t max_records, int report, const int32_t *d_seg_start,
+    size_t segments, long lead_begin, long text_end, long open_end, int all_patterns,
+    int32_t *d_pat_out, int32_t *d_off_out, size_t out_capacity, int32_t *d_info,
     void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* Match tallies: counts of the records of any pass, reduced on the device, so a caller who only counts
