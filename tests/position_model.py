@@ -10,6 +10,7 @@ The model works on entries (pattern, offset, group): a group is a record of a ST
 state's match list, from Automaton.state_matches) or a run of equal offsets of a HEAD plane.  The all form
 keeps every kept entry; the first form the first kept entry of each group, and counts only the undecided
 entries in front of it.  brute_force restates the rule with bytes.find over each text, without an automaton.
+Windows is the rule without an automaton, for entries that come from elsewhere; PositionModel adds the walk.
 """
 import numpy as np
 
@@ -60,9 +61,9 @@ def bounds(offs, starts, lead_begin, text_end, open_end):
     return t0.astype(np.int64), tend.astype(np.int64), known
 
 
-class PositionModel:
-    """pats: bytes, or (bytes, nocase) pairs (then the walk is the nocase automaton's, as the scan of a mixed
-    automaton); windows: {index: (lo, hi or None, from_end)}"""
+class Windows:
+    """the rule alone, for entries that come from elsewhere (an oracle's records): pats: bytes, or (bytes,
+    nocase) pairs; windows: {index: (lo, hi or None, from_end)}"""
 
     def __init__(self, pats, windows):
         self.pats = [bytes(p[0] if isinstance(p, tuple) else p) for p in pats]
@@ -75,20 +76,6 @@ class PositionModel:
             self.lo[i], self.hi[i], self.fe[i] = lo, UNB if hi is None else hi, fe
         self.len = np.array([len(p) for p in self.pats], dtype=np.int64)
         self.free = (self.lo == 0) & (self.hi == UNB) & ~self.fe
-        a = Automaton(nocase=any(self.nocase))
-        for i, p in enumerate(self.pats):
-            a.add(p, i)
-        a.compile()
-        self.a = a
-        self.num_states = a.num_states
-        self.next = np.abs(a.reference_table()[:, 0, :]).astype(np.int64)   # (final transitions are stored negated)
-        lists = [a.state_matches(s) for s in range(a.num_states)]
-        self.list_len = np.array([len(x) for x in lists], dtype=np.int64)
-        self.list = np.full((a.num_states, max(1, int(self.list_len.max()))), -1, dtype=np.int64)
-        for s, x in enumerate(lists):
-            self.list[s, :len(x)] = x
-
-    # ---- the rule
 
     def verdicts(self, p, o, t0, tend, known):
         """DROP / KEEP / UNDECIDED per entry (arrays)"""
@@ -114,19 +101,46 @@ class PositionModel:
         ahead = before - base                                # kept entries in front, this group
         return (v == KEEP) & (ahead == 0), int(((v == UNDECIDED) & (ahead == 0)).sum())
 
+    def entries(self, p, o, all_patterns, starts=(), lead_begin=0, text_end=0, open_end=None):
+        """(patterns int32, offsets int64, undecided) the pass writes for entries in pattern form: a run of
+        equal offsets is a group"""
+        p, o = np.asarray(p, dtype=np.int64), np.asarray(o, dtype=np.int64)
+        group = np.cumsum(np.r_[0, o[1:] != o[:-1]]) if o.size else o
+        t0, tend, known = bounds(o, starts, lead_begin, text_end, open_end)
+        keep, und = self.select(self.verdicts(p, o, t0, tend, known), group, all_patterns)
+        return p[keep].astype(np.int32), o[keep], und
+
+
+class PositionModel(Windows):
+    """pats: bytes, or (bytes, nocase) pairs (then the walk is the nocase automaton's, as the scan of a mixed
+    automaton); windows: {index: (lo, hi or None, from_end)}"""
+
+    def __init__(self, pats, windows):
+        Windows.__init__(self, pats, windows)
+        a = Automaton(nocase=any(self.nocase))
+        for i, p in enumerate(self.pats):
+            a.add(p, i)
+        a.compile()
+        self.a = a
+        self.num_states = a.num_states
+        self.next = np.abs(a.reference_table()[:, 0, :]).astype(np.int64)   # (final transitions are stored negated)
+        lists = [a.state_matches(s) for s in range(a.num_states)]
+        self.list_len = np.array([len(x) for x in lists], dtype=np.int64)
+        self.list = np.full((a.num_states, max(1, int(self.list_len.max()))), -1, dtype=np.int64)
+        for s, x in enumerate(lists):
+            self.list[s, :len(x)] = x
+
     def filter(self, cells, offs, report, all_patterns, starts=(), lead_begin=0, text_end=0, open_end=None):
         """(patterns int32, offsets int64, undecided) the pass writes for the cells, whatever they hold"""
         cells = np.asarray(cells, dtype=np.int64)
         offs = np.asarray(offs, dtype=np.int64)
-        if report == STATE:
-            ok = (cells >= 0) & (cells < self.num_states)
-            n = np.where(ok, self.list_len[np.where(ok, cells, 0)], 0)
-            rec = np.repeat(np.arange(cells.size), n)
-            j = np.arange(rec.size) - np.repeat(np.cumsum(n) - n, n)
-            p, o, group = self.list[cells[rec], j], offs[rec], rec
-        else:
-            p, o = cells, offs
-            group = np.cumsum(np.r_[0, offs[1:] != offs[:-1]]) if offs.size else offs
+        if report != STATE:
+            return self.entries(cells, offs, all_patterns, starts, lead_begin, text_end, open_end)
+        ok = (cells >= 0) & (cells < self.num_states)
+        n = np.where(ok, self.list_len[np.where(ok, cells, 0)], 0)
+        rec = np.repeat(np.arange(cells.size), n)
+        j = np.arange(rec.size) - np.repeat(np.cumsum(n) - n, n)
+        p, o, group = self.list[cells[rec], j], offs[rec], rec
         t0, tend, known = bounds(o, starts, lead_begin, text_end, open_end)
         keep, und = self.select(self.verdicts(p, o, t0, tend, known), group, all_patterns)
         return p[keep].astype(np.int32), o[keep], und

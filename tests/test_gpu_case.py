@@ -1,7 +1,8 @@
 """Case sensitivity per pattern on the device (acm_case_matches_async, Matcher.scan_case): the records of
 a mixed automaton's scan, made exact, compared cell for cell with the model of tests/case_model.py; the
 same set through every scan route; a cross-check against the case-sensitive automaton that does not use
-the model; automata that are not mixed; streaming, segments, overflow, bounds and argument errors."""
+the model; automata that are not mixed; streaming, the state carried out of an overflowed plane, segments,
+overflow, bounds and argument errors."""
 import functools
 
 import numpy as np
@@ -272,6 +273,52 @@ def test_streaming(gpu):
     pairs = set(zip(got[0].tolist(), got[1].tolist()))
     assert (cut + 1, 7) in pairs and (cut + 1, 6) not in pairs     # CDEFABCDE caseless, cdefabcde exact
     assert (cut + 1, 6) in set(zip(whole[0].tolist(), whole[1].tolist()))
+    m.close()
+
+
+def test_carry_from_an_overflowed_plane(gpu):
+    """a stream in four pieces as chained() runs them, the second piece's case output in fewer cells than its
+    records need: its planes are the model's for that capacity, the trailer in the last cell, and the third
+    piece's scan, given those planes and that capacity as d_init_plane, goes on from it"""
+    a = cm.build(FULL)
+    m = Matcher(a, 0, max_text=4096)
+    model = model_of("full")
+    text = bytes(text_of("full", 120, 5))
+    cut = [0, len(text) // 4, len(text) // 2, 3 * len(text) // 4 + 1, len(text)]
+    pieces = [text[cut[i]:cut[i + 1]] for i in range(4)]
+    cap = m.plane_capacity
+    wsb = m.lib.acm_case_workspace_bytes(cap - 2)
+    ws = DeviceArray(max(wsb, 16))
+    for all_patterns in (False, True):
+        exps, state = [], 0
+        for i, piece in enumerate(pieces):
+            exps.append(model.records(piece, all_patterns, init_state=state, before=text[max(0, cut[i] - 33):cut[i]]))
+            state = exps[-1][2]
+        whole = model.records(text, all_patterns)
+        assert state == whole[2] and sum(e[0].size for e in exps) == whole[0].size
+        count = exps[1][0].size
+        assert count > 20
+        for small in (2, 3, count, count + 1, count + 2):     # (the last: the last cell, and no overflow)
+            caps = [8 * cap, small, 8 * cap, 8 * cap]
+            outs = [(poisoned(c + 16), poisoned(c + 16)) for c in caps]
+            tails = [poisoned(16) for _ in pieces]
+            keep = []
+            for i, piece in enumerate(pieces):
+                d = DeviceArray.from_numpy(np.frombuffer(piece, dtype=np.uint8))
+                keep.append(d)
+                m.enqueue(m.make_batch(d, len(piece), m.stream, m.pat_plane, m.off_plane, cap, (m.ws.ptr, m.ws_bytes),
+                                       report=_lib.REPORT_STATE, init_plane=outs[i - 1][0] if i else None,
+                                       init_plane_capacity=caps[i - 1] if i else 0))
+                m.case_async(m.pat_plane, m.off_plane, cap - 2, d, 0, len(piece), outs[i][0], outs[i][1], caps[i],
+                             before=tails[i - 1] if i else None, before_len=min(33, cut[i]), all_patterns=all_patterns,
+                             tail_out=tails[i], workspace=(ws.ptr, wsb))
+            for i in range(4):
+                eo, ep, last = exps[i]
+                got = tuple(x.to_numpy(np.int32, caps[i] + 16) for x in outs[i])
+                check_planes(got, ep, eo, caps[i], last, "piece %d in %d cells, all %d" % (i, caps[i], all_patterns))
+            for x in keep + tails + [y for pair in outs for y in pair]:
+                x.free()
+    ws.free()
     m.close()
 
 

@@ -11,8 +11,8 @@ A. every row of test_gpu_variants.ROWS scans text views -- inside a match of the
    REPORT_STATE and the expansion, and an overflow into 10 cells;
 B. launch groups over adjacent views of one allocation (batch k's bytes past n are batch k + 1's text),
    chained through d_init_plane, with init planes that hold poison in every cell but count and trailer;
-C. the segment and word passes with stale records behind the input trailer, poisoned scratch and
-   outputs, starts and d_before with poison behind them, word bytes around the text;
+C. the segment, word, case and position passes with stale records behind the input trailer, poisoned
+   scratch and outputs, starts and d_before with poison behind them, word bytes around the text;
 D. acm_grep -t whose packed buffer holds a longer earlier round's bytes behind a shorter stream.
 
 Every cell behind a trailer must still hold the poison, and no byte past n may change a record."""
@@ -24,6 +24,7 @@ import pytest
 import fixtures
 import orc
 import poison
+import position_model as pm
 import variants
 import word_model as wm
 from gpu_pattern_matching_amd import DeviceArray, Matcher, _lib
@@ -426,6 +427,166 @@ def test_passes(gpu, monkeypatch, row, nocase):
         for b in keep:
             b.free()
         m.close()
+
+
+def case_kept(pats, hay, lo, end, offs, ids):
+    """bool per (offset, pattern) entry: the pattern ignores case, or the bytes under it -- hay holds the stream
+    offsets [lo, lo + len(hay)), the text ends at end -- equal it as added"""
+    out = np.zeros(len(offs), dtype=bool)
+    for i, (o, p) in enumerate(zip(np.asarray(offs).tolist(), np.asarray(ids).tolist())):
+        pat, nocase = pats[p]
+        a = o - len(pat) + 1
+        out[i] = len(pat) > 0 and (nocase or (a >= lo and o < end and hay[a - lo:o + 1 - lo] == pat))
+    return out
+
+
+def first_per_offset(offs, ids):
+    first = np.concatenate([[True], offs[1:] != offs[:-1]]) if offs.size else np.zeros(0, dtype=bool)
+    return offs[first], ids[first]
+
+
+def mixed_inputs(name):
+    """(nocase model, (pattern, ignores case) pairs, windows, text, denser text, before) of a set with every third
+    pattern ignoring case and windows on three quarters of them.  The text's letters change case now and
+    then; an exact pattern lies across the seam of before and text."""
+    model = wm.WordModel(name, True)          # the candidates are the nocase automaton's
+    pats = [(p, i % 3 == 0) for i, p in enumerate(model.pats)]
+    windows = {i: ((0, 150, False), (8, 200, True), (5, 2, False))[i % 4 - 1] for i in range(len(pats)) if i % 4}
+    text = wm.planted_text(model.pats, PASS_N, 7, max_len=24)
+    letter = ((text | 0x20) >= ord("a")) & ((text | 0x20) <= ord("z"))
+    text[letter & (np.random.default_rng(3).random(text.size) < 0.15)] ^= 0x20
+    across = next(p for p, nocase in pats if not nocase and 4 <= len(p) <= 24)
+    text = np.concatenate([np.frombuffer(across[2:] + b" ", dtype=np.uint8), text])
+    before = b"q7_ " + bytes(text[40:80]) + b" " + across[:2]
+    short = [p for p in model.pats if 0 < len(p) <= 8] or [min((p for p in model.pats if p), key=len)]
+    rng = np.random.default_rng(11)
+    dense = np.frombuffer(b"".join(short[int(rng.integers(len(short)))] for _ in range(text.size // 2))[:text.size],
+                          dtype=np.uint8)   # patterns back to back, as added: many more records and entries
+    return model, pats, windows, text, dense, before
+
+
+@pytest.mark.parametrize("row", list(test_gpu_words.ROWS))
+def test_case_and_position_passes(gpu, monkeypatch, row):
+    """the row's set made mixed and positioned (mixed_inputs), so that the case and position passes have
+    work: both over the STATE planes of a scan that a denser scan used before it, and the position pass also
+    over case-pass output that a denser call left its entries in"""
+    name, mode, env, lds = test_gpu_words.ROWS[row]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    model, pats, windows, text, dense, before = mixed_inputs(name)
+    rule = pm.Windows(pats, windows)
+    a = pm.build(pats, windows)
+    assert a.mixed_case and a.positioned
+    m = Matcher(a, 0, max_text=16)
+    n = text.size
+    init = model.o.scan(wm.FOLD[np.frombuffer(before, np.uint8)])[2]
+    dense_head = model.o.scan(wm.FOLD[dense])
+    cap = dense_head[0].size + 2
+    mr, icap = cap - 2, 8 * cap
+    wsb = m.lib.acm_scan_workspace_bytes(m.dfa, n)
+    cwb, pwb = m.lib.acm_case_workspace_bytes(mr), m.lib.acm_position_workspace_bytes(icap - 2)
+    keep = []
+
+    def buf(nbytes, byte):
+        b = DeviceArray(max(nbytes, 16))
+        b.fill(byte)
+        keep.append(b)
+        return b
+
+    def cells(o, p, shift=ORIGIN):
+        return o.astype(np.int64) + shift, p
+
+    try:
+        assert m.set_mode(mode) == mode
+        assert m.lds_resident() == lds
+        ws = buf(wsb, 0xA5)
+        P, Q = buf(cap * 4, 0), buf(cap * 4, 0)
+        hp, hq = buf(icap * 4, 0), buf(icap * 4, 0)
+        d_dense = DeviceArray.from_numpy(dense)
+        d_text, p_text = framed(text)
+        d_before, p_before = framed(before)
+        keep += [d_dense, d_text, d_before]
+        # the denser scan and its case pass leave their records in P, Q and their entries in hp, hq
+        m.scan_async(d_dense, dense.size, 0, pat_plane=P, off_plane=Q, plane_capacity=cap, workspace=(ws.ptr, wsb),
+                     offset_shift=ORIGIN, report=_lib.REPORT_STATE)
+        m.case_async(P, Q, mr, d_dense, ORIGIN, ORIGIN + dense.size, hp, hq, icap, all_patterns=True,
+                     workspace=(buf(cwb, 0xFF).ptr, cwb))
+        do, dp, _ = model.o.scan_all(wm.FOLD[dense])
+        dk = case_kept(pats, bytes(dense), 0, dense.size, do, dp)
+        dense_entries = int(dk.sum())
+        assert int(read_cells(hp, 1)[0]) == dense_entries <= icap - 2
+        ws.fill(0xFF)
+        m.scan_async(p_text, n, init, pat_plane=P, off_plane=Q, plane_capacity=cap, workspace=(ws.ptr, wsb),
+                     offset_shift=ORIGIN, report=_lib.REPORT_STATE)
+        head = model.o.scan(wm.FOLD[text], init)
+        k = head[0].size
+        stale = read_cells(Q, cap)
+        assert int(stale[0]) == k and dense_head[0].size > k + 100
+        assert np.array_equal(stale[k + 2:cap - 1].astype(np.int64), dense_head[0][k + 1:].astype(np.int64) + ORIGIN), \
+            "the dense scan's records must lie behind the trailer"
+        last = head[2]
+        eo, ep, _ = model.o.scan_all(wm.FOLD[text], init)
+        eo = eo.astype(np.int64)
+        hay = before + bytes(text)
+        tag = row + " "
+
+        # the case pass, all patterns, with before; then the first kept entry per record, without
+        kept = case_kept(pats, hay, -len(before), n, eo, ep)
+        assert 50 < int(kept.sum()) < eo.size and kept[eo < 20].any()
+        cp, cq = buf(icap * 4, EE), buf(icap * 4, EE)
+        m.case_async(P, Q, mr, p_text, ORIGIN, ORIGIN + n, cp, cq, icap, before=p_before, before_len=len(before),
+                     all_patterns=True, workspace=(buf(cwb, 0xA5).ptr, cwb))
+        poison.check_planes(cp, cq, icap, cells(eo[kept], ep[kept]) + (last,), what=tag + "case pass, all, before")
+        alone = case_kept(pats, bytes(text), 0, n, eo, ep)
+        assert int(alone.sum()) < int(kept.sum())          # an entry reached into before
+        fp, fq = buf(cap * 4, EE), buf(cap * 4, EE)
+        m.case_async(P, Q, mr, p_text, ORIGIN, ORIGIN + n, fp, fq, cap, all_patterns=False,
+                     workspace=(buf(cwb, 0xFF).ptr, cwb))
+        poison.check_planes(fp, fq, cap, cells(*first_per_offset(eo[alone], ep[alone])) + (last,),
+                            what=tag + "case pass, first, no before")
+
+        # the position pass over the STATE planes: texts from the starts, the last one's end unknown
+        rng = np.random.default_rng(13)
+        starts = np.sort(rng.choice(n, 300, replace=False)).astype(np.int64)
+        starts = np.concatenate([starts[:150], starts[150:151], starts[150:]])   # one empty text
+        nseg = starts.size
+        st_cells = np.full(nseg + 64, ORIGIN + n // 3, dtype=np.int32)
+        st_cells[:nseg] = starts + ORIGIN
+        d_st = DeviceArray.from_numpy(st_cells, pad_to=0)
+        keep.append(d_st)
+        lead = ORIGIN - len(before)
+        xp, xo, und = rule.entries(ep, eo + ORIGIN, True, starts + ORIGIN, lead, ORIGIN + n, None)
+        assert 50 < xp.size < eo.size and und > 0
+        pp, pq, info = buf(icap * 4, EE), buf(icap * 4, EE), buf(64, EE)
+        m.position_async(P, Q, mr, pp, pq, icap, info, report=_lib.REPORT_STATE, seg_start=d_st, segments=nseg,
+                         lead_begin=lead, text_end=ORIGIN + n, open_end=-1, all_patterns=True,
+                         workspace=(buf(pwb, 0xA5).ptr, pwb))
+        poison.check_planes(pp, pq, icap, (xo, xp, last), what=tag + "position pass over states")
+        assert read_cells(info, 16).tolist() == [und, 0, 0, 0] + [poison.cell(EE)] * 12, tag + "info"
+
+        # the position pass over case-pass output with the denser call's entries behind the trailer
+        m.case_async(P, Q, mr, p_text, ORIGIN, ORIGIN + n, hp, hq, icap, before=p_before, before_len=len(before),
+                     all_patterns=True, workspace=(buf(cwb, 0xA5).ptr, cwb))
+        e = int(kept.sum())
+        assert dense_entries > e + 100
+        got_p, got_q = read_cells(hp, icap), read_cells(hq, icap)
+        assert got_p[0] == e and np.array_equal(got_p[1:1 + e], ep[kept]) and got_p[e + 1] == last
+        assert np.array_equal(got_q[1:1 + e], eo[kept] + ORIGIN)
+        assert np.array_equal(got_q[e + 2:dense_entries + 1], do[dk][e + 1:].astype(np.int64) + ORIGIN), \
+            "the dense call's entries must lie behind the trailer"
+        xp, xo, und = rule.entries(ep[kept], eo[kept] + ORIGIN, False, (), lead, ORIGIN + n, ORIGIN + n)
+        assert 50 < xp.size < e and und == 0
+        pp, pq, info = buf(icap * 4, EE), buf(icap * 4, EE), buf(64, EE)
+        m.position_async(hp, hq, icap - 2, pp, pq, icap, info, report=_lib.REPORT_HEAD, lead_begin=lead,
+                         text_end=ORIGIN + n, open_end=ORIGIN + n, all_patterns=False,
+                         workspace=(buf(pwb, 0xFF).ptr, pwb))
+        poison.check_planes(pp, pq, icap, (xo, xp, last), what=tag + "position pass over case output")
+        assert read_cells(info, 16).tolist() == [0, 0, 0, 0] + [poison.cell(EE)] * 12, tag + "info"
+    finally:
+        for b in keep:
+            b.free()
+        m.close()
+        a.close()
 
 
 # ---------------------------------------------------------------------------------------------- D

@@ -1,5 +1,5 @@
 """The record-pass core (csrc/record_pass.h) through every pass that uses it -- segment, word, tally, line
-select, expand -- at the record counts where tile ownership, ordered ranks and the header / trailer cells
+select, expand, case -- at the record counts where tile ownership, ordered ranks and the header / trailer cells
 can go wrong.  Planes are built by hand in numpy; expected outputs are plain numpy and the models of the
 suite, never the library.
 
@@ -8,10 +8,16 @@ ends at offset 4 i + 3 and holds one of those states or (a quarter of the record
 and is dropped by segment, word and tally: the kept records are an arbitrary subset, known on the host.
 A record's kind is its longest pattern's length; its match list holds that pattern and every shorter one,
 in the oracle's order.
-Starts are multiples of 4, so every record lies 4 bytes or more into its segment and no state is clamped."""
+Starts are multiples of 4, so every record lies 4 bytes or more into its segment and no state is clamped.
+
+The case pass has a mixed automaton of its own over the same idea, {a, bA, cba (ignoring case), Dcba}: kinds
+1..4 with lists of 1..4 entries, the four bytes under a record in a case drawn per byte, so that which of
+a record's exact entries hold -- 0 to 3 cells per record in the all form -- is known on the host only.  The
+text starts two bytes into record 0, whose longer entries reach into `before`."""
 import numpy as np
 import pytest
 
+import case_model as cm
 import line_model
 import orc
 import poison
@@ -321,3 +327,134 @@ def test_expand_header_and_trailer(env, m):
             _lib.check(env.m.lib.acm_expand_matches_async(env.m.dfa, d_sp.ptr, d_op.ptr, mr, pat.ptr, o.ptr, cap, ws.ptr,
                                                           nb, None), "acm_expand_matches_async")
             poison.check_planes(pat, o, cap, exp, what="expand m=%d max_records=%d cap=%d" % (m, mr, cap))
+
+
+# ------------------------------------------------------------------ case
+
+CASE_PATS = [(b"a", False), (b"bA", False), (b"cba", True), (b"Dcba", False)]
+CASE_BYTES = np.frombuffer(b"Dcba", dtype=np.uint8)
+CASE_ORIGIN = 2                              # the text starts here: bytes 0 and 1 of the stream are `before`
+CUT_RECORDS = (1023, 1024)                   # the last record of tile 0, the first of tile 1: three kept entries each
+SLACK = 16                                   # guard cells behind the case pass's output planes
+
+
+class CaseEnv:
+    def __init__(self):
+        self.model = cm.CaseModel(CASE_PATS)
+        a = cm.build(CASE_PATS)
+        assert a.mixed_case
+        self.m = Matcher(a, 0, max_text=4096)
+        self.state = {k: int(self.model.walk(b"dcba"[4 - k:])[2]) for k in (1, 2, 3, 4)}   # kind -> state
+        self.lists = np.full((5, 4), -1, dtype=np.int32)                                    # [kind, j] -> pattern
+        for k in (1, 2, 3, 4):
+            lst = self.model.list_of(self.state[k])
+            assert sorted(lst) == list(range(k))
+            self.lists[k, :k] = lst
+        self.cache = {}
+
+    def planes(self, m):
+        """(kinds, offsets, host state plane, device state plane, device offset plane, stream bytes, device
+        stream, holds[record, pattern]) of m records.  Record 0 and, beyond 1024 records, the records either
+        side of the first tile cut are "Dcba" whole."""
+        if m not in self.cache:
+            rng = np.random.default_rng(3000 + m)
+            kind = rng.integers(1, 5, m)
+            kind[rng.random(m) < 0.25] = 0
+            text = np.where(rng.random((m + 1, 4)) < 0.7, CASE_BYTES, CASE_BYTES ^ 0x20).astype(np.uint8)
+            for i in ((0,) if m else ()) + (CUT_RECORDS if m > 1025 else ()):
+                kind[i], text[i] = 4, CASE_BYTES
+            off = (np.arange(m, dtype=np.int64) * 4 + 3).astype(np.int32)
+            lut = np.array([NO_STATE] + [self.state[k] for k in (1, 2, 3, 4)], dtype=np.int32)
+            sp = np.concatenate([[m], lut[kind], [self.state[1]]]).astype(np.int32)
+            op = np.concatenate([[m], off, [self.state[1]]]).astype(np.int32)
+            t = text[:m]
+            holds = np.stack([t[:, 3] == ord("a"), (t[:, 2] == ord("b")) & (t[:, 3] == ord("A")),
+                              np.ones(m, dtype=bool), (t == CASE_BYTES).all(axis=1)], axis=1)
+            text = text.reshape(-1)
+            self.cache[m] = (kind, off, sp, DeviceArray.from_numpy(sp), DeviceArray.from_numpy(op), text,
+                             DeviceArray.from_numpy(text), holds)
+        return self.cache[m]
+
+
+@pytest.fixture(scope="module")
+def cenv(gpu):
+    e = CaseEnv()
+    yield e
+    for v in e.cache.values():
+        for x in v:
+            if isinstance(x, DeviceArray):
+                x.free()
+    e.m.close()
+
+
+def case_expected(cenv, m, mr, all_patterns):
+    """(offsets, patterns, trailer): every entry of the first min(m, mr) records that holds, or the first of
+    each record, by numpy alone"""
+    kind, off, sp, _, _, _, _, holds = cenv.planes(m)
+    mm = min(m, mr)
+    n = kind[:mm]
+    rec = np.repeat(np.arange(mm), n)
+    start = np.cumsum(n) - n
+    j = np.arange(rec.size) - np.repeat(start, n)
+    p = cenv.lists[kind[rec], j]
+    keep = holds[rec, p]
+    if not all_patterns and rec.size:
+        ahead = np.cumsum(keep) - keep                       # kept entries in front, all records
+        keep &= ahead == np.repeat(ahead[np.minimum(start, rec.size - 1)], n)
+    return off[rec][keep], p[keep], int(sp[1 + mm])
+
+
+def check_case(cenv, m, all_patterns, max_records=None, cap=None):
+    _, _, _, d_sp, d_op, text, d_text, _ = cenv.planes(m)
+    mr = m if max_records is None else max_records
+    eo, ep, last = case_expected(cenv, m, mr, all_patterns)
+    cap = len(eo) + 9 if cap is None else cap
+    pat, o = out_planes(cap + SLACK)
+    tail = DeviceArray(64)
+    tail.fill(P)
+    nb = cenv.m.lib.acm_case_workspace_bytes(mr)
+    ws = poisoned_ws(nb)
+    d_before = DeviceArray.from_numpy(text[:CASE_ORIGIN])
+    cenv.m.case_async(d_sp, d_op, mr, d_text.ptr + CASE_ORIGIN, CASE_ORIGIN, text.size, pat, o, cap, before=d_before,
+                      before_len=CASE_ORIGIN, all_patterns=all_patterns, tail_out=tail, workspace=(ws.ptr, nb))
+    what = "case m=%d max_records=%d cap=%d all=%d" % (m, mr, cap, all_patterns)
+    for got, exp in zip((pat, o), cm.planes(ep, eo, cap, PV, last)):
+        got = got.to_numpy(np.int32, cap + SLACK)
+        assert int(got[0]) == len(eo), "%s: count %d, expected %d" % (what, got[0], len(eo))
+        assert np.array_equal(got[:cap], exp), "%s: plane differs at %s" % (what, np.flatnonzero(got[:cap] != exp)[:5])
+        assert np.all(got[cap:] == PV), what + ": written behind the capacity"
+    tb = tail.to_numpy(np.uint8, 64)
+    assert np.array_equal(tb[:4], text[-4:]) and np.all(tb[4:] == P), what + ": tail"
+    for x in (pat, o, tail, ws, d_before):
+        x.free()
+    return eo, ep, last
+
+
+@pytest.mark.parametrize("m", COUNTS + [BIG])
+def test_case(cenv, m):
+    for all_patterns in (False, True):
+        exp = check_case(cenv, m, all_patterns)
+        if m == BIG:
+            assert len(exp[0]) > m // 2
+            continue
+        # the numpy expectation is the model's
+        _, off, sp, _, _, text, _, _ = cenv.planes(m)
+        mp, mo = cenv.model.filter(sp[1:1 + m], off, text[CASE_ORIGIN:], all_patterns, CASE_ORIGIN,
+                                   bytes(text[:CASE_ORIGIN]))
+        assert np.array_equal(mp, exp[1]) and np.array_equal(mo, exp[0]), "m=%d all=%d" % (m, all_patterns)
+        for mr in max_records_of(m):
+            check_case(cenv, m, all_patterns, max_records=mr)
+        for cap in caps_of(len(exp[0])):
+            check_case(cenv, m, all_patterns, cap=cap)
+
+
+@pytest.mark.parametrize("m", [2049, BIG])
+def test_case_list_across_the_cut(cenv, m):
+    """cap - 2 falls inside the list of the last record of tile 0, then of the first record of tile 1: two
+    blocks' tiles at 2049 records, the two tiles of block 0 at the big count"""
+    eo, ep, _ = case_expected(cenv, m, m, True)
+    for i in CUT_RECORDS:
+        at = int(np.searchsorted(eo, 4 * i + 3))
+        assert eo[at:at + 3].tolist() == [4 * i + 3] * 3 and sorted(ep[at:at + 3].tolist()) == [0, 2, 3]
+        for stored in (at + 1, at + 2):       # one entry of the record in front of the cut, then two
+            check_case(cenv, m, True, cap=stored + 2)

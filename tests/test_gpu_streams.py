@@ -11,7 +11,7 @@ on the scan's own stream before every scan: a scan that silently did not run can
   1. every pipeline on a created stream: plain, shard, REPORT_STATE + expand/segment/word passes with no
      host sync, a three-piece d_init_plane chain, a plane overflow
   2. four streams in flight with one acm_dfa of each kind, a different issue form per stream; buffer reuse
-     protected by stream order alone
+     protected by stream order alone; scan -> segment -> case -> position passes chained on two streams
   3. the event fields: recorded on every path (the empty text too), the wait honoured, events and groups
   4. graph replay, counted through acm_scan_graph_stats (Matcher.graph_stats)
   5. in-line profiling: results unchanged, launches as the header says
@@ -25,9 +25,11 @@ import pytest
 
 import fixtures
 import poison
+import position_model as pm
 import streams
 import variants
 from gpu_pattern_matching_amd import Automaton, Matcher, _lib
+from test_gpu_position import COMP_W, WITH1, comp_texts
 from test_host_segments import oracle_segments
 
 pytestmark = pytest.mark.gpu
@@ -322,6 +324,116 @@ def test_streams_reuse_their_buffers(gpu):
         rig.close()
         for m in ms.values():
             m.close()
+
+
+class PassSet:
+    """the buffers of one scan -> segment -> case -> position chain: a triple for the scan, the segment table,
+    the planes and the workspace of every pass, the position pass's info cells"""
+    INFO = 4 + 16
+
+    def __init__(self, rig, m, room, max_segments):
+        self.rig, self.m = rig, m
+        self.tr = rig.triple(m, np.zeros(room, dtype=np.uint8))
+        cap = self.tr.cap
+        self.mr, self.icap = cap - 2, 8 * cap
+        self.d_st = rig.buf(max_segments * 4, EE)
+        self.seg, self.case, self.pos = rig.planes(cap), rig.planes(self.icap), rig.planes(self.icap)
+        self.info = rig.buf(self.INFO * 4, EE)
+        self.wsb = (m.lib.acm_segment_workspace_bytes(self.mr), m.lib.acm_case_workspace_bytes(self.mr),
+                    m.lib.acm_position_workspace_bytes(self.icap - 2))
+        self.ws = [rig.buf(b) for b in self.wsb]
+
+    def steps(self, s, job):
+        """what one stream enqueues, a step per entry: the text and its table copied in, every output and
+        workspace poisoned, then the four launches -- all on s, nothing synchronised"""
+        tr, m, n, nseg = self.tr, self.m, job.t.size, job.starts.size
+
+        def load():
+            tr.set_text(job.t, s)
+            self.rig.h2d(self.d_st, job.starts, s)
+
+        def spoil():
+            tr.poison(s)
+            for b in self.seg + self.case + self.pos + (self.info,):
+                b.fill(EE, s)
+            for k, b in enumerate(self.ws):
+                b.fill((0xA5, 0xFF)[k % 2], s)
+        return [load, spoil,
+                lambda: m.enqueue(tr.batch(s, report=STATE)),
+                lambda: m.segment_async(tr.pat, tr.off, self.mr, self.d_st, nseg, n, self.seg[0], self.seg[1], tr.cap,
+                                        report=STATE, workspace=(self.ws[0].ptr, self.wsb[0]), stream=s),
+                lambda: m.case_async(self.seg[0], self.seg[1], self.mr, tr.text, 0, n, self.case[0], self.case[1],
+                                     self.icap, all_patterns=True, workspace=(self.ws[1].ptr, self.wsb[1]), stream=s),
+                lambda: m.position_async(self.case[0], self.case[1], self.icap - 2, self.pos[0], self.pos[1], self.icap,
+                                         self.info, report=HEAD, seg_start=self.d_st, segments=nseg, lead_begin=0,
+                                         text_end=n, open_end=n if job.closed else -1, all_patterns=job.all_patterns,
+                                         workspace=(self.ws[2].ptr, self.wsb[2]), stream=s)]
+
+    def check(self, s, job, what):
+        tr = self.tr
+        poison.check_planes(tr.pat, tr.off, tr.cap, job.scan, what=what + " scan", stream=s)
+        poison.check_planes(self.seg[0], self.seg[1], tr.cap, job.seg, what=what + " segment pass", stream=s)
+        poison.check_planes(self.case[0], self.case[1], self.icap, job.case, what=what + " case pass", stream=s)
+        poison.check_planes(self.pos[0], self.pos[1], self.icap, job.pos[:3], what=what + " position pass", stream=s)
+        info = self.info.to_numpy(np.int32, self.INFO, stream=s)
+        assert info[:4].tolist() == [job.pos[3], 0, 0, 0] and (info[4:] == poison.cell(EE)).all(), what + " info"
+
+
+class PassJob:
+    """texts, packed, and what the model says every pass of the chain leaves: (offsets, cells, trailer)"""
+
+    def __init__(self, model, texts, all_patterns, closed):
+        self.t, self.starts = Matcher.pack_segments(texts)
+        self.all_patterns, self.closed = all_patterns, closed
+        states, offs, last = model.walk(self.t)
+        self.scan = (offs, states, last)
+        so, ss, co, cp, base = [], [], [], [], 0
+        for t in texts:
+            states, offs, last = model.walk(t)
+            so.append(offs + base)
+            ss.append(states)
+            for st, o in zip(states.tolist(), offs.tolist()):
+                for p in model.list[st, :model.list_len[st]].tolist():
+                    if model.then_keeps("case", p, o, t):
+                        co.append(o + base)
+                        cp.append(p)
+            base += len(t)
+        self.seg = (np.concatenate(so), np.concatenate(ss), last)
+        self.case = (np.array(co, dtype=np.int64), np.array(cp, dtype=np.int64), last)
+        self.pos = model.records(texts, all_patterns, then="case", open_end="end" if closed else None)
+        assert self.pos[2] == last and (self.pos[3] > 0) == (not closed) and self.scan[0].size > self.seg[0].size > 0      # texts cut matches
+        assert self.case[0].size > self.pos[0].size > 15 and self.case[0].size != self.seg[0].size
+
+
+def test_case_and_position_passes_chained_on_two_streams(gpu):
+    """scan(STATE) -> segment pass (STATE form) -> case pass (all patterns) -> position pass (pattern-form
+    input) on two created streams, a text and a segment table of its own on each, issued step by step in
+    turn with no host sync; then again with the two streams' buffers swapped, the other stream's records
+    still in them: every plane of every pass whole against the models, and the undecided count"""
+    a = pm.build(WITH1, COMP_W)
+    assert a.mixed_case and a.positioned
+    model = pm.PositionModel(WITH1, COMP_W)
+    m = Matcher(a, 0, max_text=16, plane_capacity=2)
+    a.close()
+    rig = streams.Rig()
+    try:
+        texts = comp_texts()
+        jobs = [PassJob(model, texts, True, True),           # the second: the last text's end is not known
+                PassJob(model, texts[::-1][5:] + [b"aBcd.abc", b"", b"Abcd d"], False, False)]
+        assert jobs[0].t.size != jobs[1].t.size and jobs[0].starts.size != jobs[1].starts.size
+        room = max(j.t.size for j in jobs)
+        sets = [PassSet(rig, m, room, max(j.starts.size for j in jobs)) for _ in jobs]
+        ss = [rig.stream(), rig.stream()]
+        for turn, order in enumerate(((0, 1), (1, 0))):
+            plan = [sets[order[k]].steps(ss[k], jobs[k]) for k in range(2)]
+            for step in zip(*plan):
+                for enqueue in step:
+                    enqueue()
+            for k in range(2):
+                sets[order[k]].check(ss[k], jobs[k], "turn %d stream %d" % (turn, k))
+    finally:
+        rig.close()
+        m.close()
 
 
 # ------------------------------------------------------------------------------------------------ 3

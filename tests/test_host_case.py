@@ -1,11 +1,13 @@
 """Case sensitivity per pattern on the host (acm_automaton_add_ex and friends) -- no GPU: the flags, what
-compile makes of them (nocase, mixed or unchanged automata), and the Python model of the case pass
-(tests/case_model.py) against a brute force."""
+compile makes of them (nocase, mixed or unchanged automata), the Python model of the case pass
+(tests/case_model.py) against a brute force, and the slice compares of the compare sweep
+(tests/case_compare.py) against the model."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import case_compare as cc
 import case_model as cm
 from gpu_pattern_matching_amd import AcmError, Automaton, _lib
 
@@ -60,6 +62,58 @@ def test_model_before_and_origin(lib):
     pl = cm.planes([5, 6, 7], [1, 2, 3], 4, -7, 9)
     assert pl[0].tolist() == [3, 5, 6, 9] and pl[1].tolist() == [3, 1, 2, 9]
     assert cm.planes([5], [1], 5, -7, 9)[0].tolist() == [1, 5, 9, -7, -7]
+
+
+def test_compare_sweep_expectations(lib):
+    """what tests/test_gpu_case_compare.py expects of the device, without one: the slice compares of
+    case_compare equal CaseModel.filter on the same planes, texts and befores, in both forms; an unaltered copy
+    keeps every suffix (brute_force); an entry is kept iff no altered byte lies under it"""
+    model = cm.CaseModel(cc.PATS)
+    state_of = {"M": model.walk(cc.M)[2], "M13": model.walk(cc.M13)[2]}
+    lists = {s: model.list_of(s) for s in state_of.values()}
+    assert set(lists[state_of["M"]]) == cc.OF_M and set(lists[state_of["M13"]]) == cc.OF_M13
+    assert len(lists[state_of["M"]]) == len(cc.OF_M) and len(lists[state_of["M13"]]) == len(cc.OF_M13)
+    # the unaltered copies, with no automaton at all
+    for master, name, of in ((cc.M, "M", cc.OF_M), (cc.M13, "M13", cc.OF_M13)):
+        text = b".;" + master + b"-"
+        end = 1 + len(master)
+        at_end = {p for o, p in cm.brute_force(cc.PATS, text) if o == end}
+        assert at_end == of
+        ep, eo = cc.expect(cc.PATS, lists, [(state_of[name], end)], text, 0, len(text), True)
+        assert set(ep.tolist()) == of and ep.tolist() == lists[state_of[name]] and set(eo.tolist()) == {end}
+        assert cc.expect(cc.PATS, lists, [(state_of[name], end)], text, 0, len(text), False)[0].tolist() == ep.tolist()[:1]
+    # text only
+    text, copies = cc.text_only()
+    assert len(copies) == 4 * 2 * 34 and {(o - 32) % 4 for o, _, _ in copies} == {0, 1, 2, 3}
+    sM = state_of["M"]
+    for origin in (0, 1001):
+        records = [(sM, origin + o) for o, _, _ in copies]
+        for all_patterns in (False, True):
+            ep, eo = cc.expect(cc.PATS, lists, records, text, origin, origin + len(text), all_patterns)
+            mp, mo = model.filter([s for s, _ in records], [o for _, o in records], text, all_patterns, origin)
+            assert np.array_equal(ep, mp) and np.array_equal(eo, mo), (origin, all_patterns)
+    kept = {}
+    for p, o in zip(ep.tolist(), (eo - origin).tolist()):
+        kept.setdefault(o, set()).add(p)
+    for o, j, bit in copies:
+        under = {p for p in cc.OF_M if cc.PATS[p][1] or j is None or j < 33 - len(cc.PATS[p][0])}
+        assert kept[o] == under, (o, j, bit)
+    # across the seam
+    seen = set()
+    for seam in cc.seams_13() + cc.seams_33():
+        for origin in (0, 1001):
+            records = seam.records(state_of, origin)
+            for all_patterns in (False, True):
+                ep, eo = seam.expect(lists, state_of, origin, all_patterns)
+                mp, mo = model.filter([s for s, _ in records], [o for _, o in records], seam.text, all_patterns, origin,
+                                      seam.before)
+                assert np.array_equal(ep, mp) and np.array_equal(eo, mo), (seam.name, seam.k, seam.j, seam.mode)
+        first = eo == records[0][1]
+        longest = max(cc.OF_M if seam.name == "M" else cc.OF_M13, key=lambda p: len(cc.PATS[p][0]))
+        assert (longest in ep[first].tolist()) == (seam.j is None and (seam.mode != "fewer" or seam.k == 0))
+        assert int((~first).sum()) == 2 * len(cc.OF_M) + len(cc.OF_M13)       # the plain matches behind the seam
+        seen.add((seam.name, seam.k, seam.j, seam.mode))
+    assert len(seen) == 14 * 14 * 3 - 14 + 34 * 3 - 2
 
 
 def test_flags_round_trip(lib):
