@@ -514,7 +514,10 @@ extern "C" void databuf_copy_device_to_host(struct databuf *db, cl_command_queue
 	hip_or_die(hipMemcpyAsync(db->h_results_comp, db->d_results_comp, 2 * sizeof(int),
 	    hipMemcpyDeviceToHost, s), "read d_results_comp");
 	hip_or_die(hipStreamSynchronize(s), "read d_results");
-	db->last_state = db->h_results[db->chunks * db->max_results];
+	// a round without chunks wrote no bucket trailer (ocl_aho_match skips acm_bucketize): cell 0 still
+	// holds chunk 0's count of an earlier round.  Scanning zero bytes leaves the state alone.
+	if (db->chunks)
+		db->last_state = db->h_results[db->chunks * db->max_results];
 
 	if (db->compact) {
 		size_t m = (size_t)db->h_results_comp[0];

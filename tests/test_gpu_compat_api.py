@@ -192,6 +192,88 @@ def test_text_mode_line_chunks(gpu, tmp_path):
     w.close()
 
 
+@pytest.mark.parametrize("compact", [0, 1])
+def test_round_without_chunks_keeps_the_state(gpu, compact):
+    """databuf_reset, then a round with nothing added, after a round that had matches: no results, no
+    callback, and db->last_state is what the earlier round left -- scanning zero bytes leaves the state
+    alone.  (In bucket mode ocl_aho_match writes no bucket trailer for zero chunks; cell 0 of the bucket
+    plane still holds chunk 0's match count of the round before.)  The round after it completes the
+    pattern that round 1 left open."""
+    w = Worker("tests3", 8, 64)
+    L, db, o = w.L, w.db, w.oracle
+    db.contents.compact = compact
+
+    def walk(init):
+        total, exp, last, buf_pos, pat = expected_bucket_walk(o, db, init)
+        if compact:     # raw offsets, chunk = offset / chunk size (databuf.c:713-742)
+            exp = [(int(db.contents.file_ids[p // 64]), int(q), int(p // 64), int(p)) for p, q in zip(buf_pos, pat)]
+        return total, exp, last
+
+    head = b"test1 test2 test3 test1x tes"
+    assert L.databuf_add_chunk(db, head, len(head), 5, b"\x01") >= 0
+    total, exp, last = walk(0)
+    assert total == 4 and last not in (0, total)       # neither the start state nor chunk 0's count
+    assert w.round() == total and w.records == exp and db.contents.last_state == last
+    L.databuf_reset(db)
+    assert w.round() == 0
+    assert w.records == []
+    assert db.contents.last_state == last
+    L.databuf_reset(db)
+    tail = b"t1x and test2"
+    assert L.databuf_add_chunk(db, tail, len(tail), 6, b"\x01") >= 0
+    total, exp, last2 = walk(last)
+    assert total == 2 and exp[0][3] == 1 + (0 if compact else 1)     # "tes" + "t1": found only with the state carried
+    assert w.round() == total and w.records == exp and db.contents.last_state == last2
+    w.close()
+
+
+def test_text_mode_long_lines(gpu, tmp_path):
+    """-t with lines longer than 256 bytes (more than one trip of the pack kernel's copy loop per chunk):
+    every line starts with a pattern, lines longer than a chunk are cut by fgets, and a pattern planted
+    across such a cut ends on the first byte of the chunk behind it."""
+    B = 512
+    w = Worker("sentiment", 256, B)
+    L, db = w.L, w.db
+    pats = fixtures.patterns_of("sentiment")
+    text = fixtures.text_for({"kind": "words", "n": 40000, "seed": 9}, None).tobytes().replace(b"\n", b" ")
+    rng = np.random.default_rng(9)
+    lines, pos = [], 0
+    while pos < len(text) - 1000:
+        ln = int(rng.integers(300, 900))
+        body = bytearray(pats[len(lines) % 40] + b" " + text[pos:pos + ln])
+        if len(body) > B + 20:      # fgets reads B - 1 bytes: byte B - 1 of the line is the first of the next chunk
+            word = pats[4]
+            body[B - len(word):B] = word
+        lines.append(bytes(body) + b"\n")
+        pos += ln
+    assert min(len(x) for x in lines) > 256 and sum(len(x) > B + 20 for x in lines) > 5
+    path = tmp_path / "long_lines.txt"
+    path.write_bytes(b"".join(lines))
+    libc = C.CDLL(None)
+    libc.fopen.restype = C.c_void_p
+    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    fp = libc.fopen(str(path).encode(), b"r")
+    rb, rl = C.c_size_t(), C.c_size_t()
+    rc = L.databuf_add_fp(db, fp, 3, 1, C.byref(rb), C.byref(rl))
+    libc.fclose(fp)
+    chunks = db.contents.chunks
+    assert rc > 0 and rl.value == len(lines) and chunks > len(lines) + 5
+    assert rb.value == sum(len(x) for x in lines)
+    ind = np.ctypeslib.as_array(db.contents.h_indices, shape=(chunks,)).copy()
+    siz = np.ctypeslib.as_array(db.contents.h_sizes, shape=(chunks,)).copy()
+    assert siz.max() == B - 1 and np.all(ind % 16 == 0) and np.any(ind[1:] > ind[:-1] + siz[:-1])
+    total, exp, last, buf_pos, _ = expected_bucket_walk(w.oracle, db, 0)
+    on_first = set(buf_pos.tolist()) & set(ind.tolist())
+    assert len(on_first) > 5        # records on the first byte of a chunk
+    n = w.round()
+    assert n == total and total > 500
+    assert w.records == exp
+    assert on_first <= {r[3] - 1 for r in w.records}
+    assert db.contents.last_state == last
+    w.close()
+
+
 def test_add_chunk_and_limits(gpu):
     """DATABUF_TEST's insert checks (databuf.c:904-931) + the return codes of databuf.h:91-113."""
     w = Worker("tests3", 100, 80, 129)
