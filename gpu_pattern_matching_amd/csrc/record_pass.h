@@ -1,5 +1,6 @@
-// The record-pass core: what the passes that run behind a scan (segment.hip, word.hip, tally.hip,
-// lines.hip, expand in post.hip) share.  Internal to the library, gfx950 only.  DESIGN.md 6f.
+// The record-pass core: what the passes that run behind a scan (segment.hip, tally.hip, lines.hip, expand
+// in post.hip, and through entry_pass.h word.hip, case.hip and position.hip) share.  Internal to the
+// library, gfx950 only.  DESIGN.md 6f.
 //
 // A pass runs a fixed grid of at most kMaxBlocks blocks of kThreads threads.  Every block owns a
 // contiguous run of tiles (share_of); a tile of records is kPer rows of kThreads, row q holding records
@@ -207,6 +208,18 @@ __device__ __forceinline__ uint32_t starts_le(const Slice &s, const int32_t *sli
     int32_t o)
 {
 	return s.in_lds ? s.k0 + upper_bound_i32(slice, s.len, o) : upper_bound_i32(seg_start, segments, o);
+}
+
+// The text [lo, hi) a record lies in, from ub = the number of starts <= its offset (in [0, segments]):
+// lo is start ub - 1 and hi is start ub; where there is no such start the bound is left as it was.
+// start_at(k): start number k < segments, from wherever the caller keeps it.
+template <class StartAt>
+__device__ __forceinline__ void text_bounds(uint32_t ub, uint32_t segments, StartAt start_at, int64_t &lo, int64_t &hi)
+{
+	if (ub > 0)
+		lo = start_at(ub - 1);
+	if (ub < segments)
+		hi = start_at(ub);
 }
 
 // ---- ordered rank inside a tile ----

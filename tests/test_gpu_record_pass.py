@@ -1,6 +1,6 @@
-"""The record-pass core (csrc/record_pass.h) through every pass that uses it -- segment, word, tally, line
-select, expand, case -- at the record counts where tile ownership, ordered ranks and the header / trailer cells
-can go wrong.  Planes are built by hand in numpy; expected outputs are plain numpy and the models of the
+"""The record-pass core (csrc/record_pass.h, csrc/entry_pass.h) through every pass that uses it -- segment,
+word, tally, line select, expand, case, position -- at the record counts where tile ownership, ordered ranks
+and the header / trailer cells can go wrong.  Planes are built by hand in numpy; expected outputs are plain numpy and the models of the
 suite, never the library.
 
 The automaton is {a, ba, cba}: the state of "cba" lists three patterns, of "ba" two, of "a" one.  Record i
@@ -227,6 +227,52 @@ def test_word_list_across_the_cut(env):
     eo, _, _ = word_expected(env, m, m, True)
     i = int(np.flatnonzero((eo[1:] == eo[:-1]))[-1])   # entries i and i + 1 are one record's
     check_word(env, m, True, cap=i + 1 + 2)
+
+
+# ------------------------------------------------------------------ word, case and position alike
+
+
+@pytest.mark.parametrize("m", [0, 65, 1025, 2049])
+def test_entry_passes_agree(env, m):
+    """The word, case and position (STATE input) passes are one skeleton (csrc/entry_pass.h) around three
+    predicates.  Where no predicate drops anything -- no byte of the text is a word byte, the automaton is
+    neither mixed nor positioned, there are no segments -- the three write the same planes cell for cell: the
+    match lists of the valid records (head: their first entries), on a plane that holds them all and on one
+    that is a cell short."""
+    kind, off, sp, d_sp, d_op, text = env.planes(m)
+    assert ord("#") not in text
+    d_text = DeviceArray.from_numpy(text)
+    for all_patterns in (False, True):
+        eo, ep, _, _ = entries(env, kind, off, all_patterns)
+        exp = (eo, ep, int(sp[1 + m]))
+        for cap in sorted({len(eo) + 2, max(len(eo) + 1, 2)}):
+            got = {}
+            for name in ("word", "case", "position"):
+                pat, o = out_planes(cap)
+                nb = getattr(env.m.lib, "acm_%s_workspace_bytes" % name)(m)
+                ws = poisoned_ws(nb)
+                what = "%s m=%d cap=%d all=%d" % (name, m, cap, all_patterns)
+                if name == "word":
+                    env.m.word_async(d_sp, d_op, m, d_text, 0, text.size, pat, o, cap, word_mask=Matcher.word_mask(b"#"),
+                                     all_patterns=all_patterns, workspace=(ws.ptr, nb))
+                elif name == "case":
+                    env.m.case_async(d_sp, d_op, m, d_text, 0, text.size, pat, o, cap, all_patterns=all_patterns,
+                                     workspace=(ws.ptr, nb))
+                else:
+                    info = DeviceArray(16)
+                    info.fill(P)
+                    env.m.position_async(d_sp, d_op, m, pat, o, cap, info, report=_lib.REPORT_STATE, text_end=text.size,
+                                         open_end=text.size, all_patterns=all_patterns, workspace=(ws.ptr, nb))
+                    assert info.to_numpy(np.int32, 4).tolist() == [0, 0, 0, 0], what
+                    info.free()
+                poison.check_planes(pat, o, cap, exp, what=what)
+                got[name] = (pat.to_numpy(np.int32, cap), o.to_numpy(np.int32, cap))
+                for x in (pat, o, ws):
+                    x.free()
+            for name in ("case", "position"):
+                for a, b in zip(got["word"], got[name]):
+                    assert np.array_equal(a, b), "word and %s differ, m=%d cap=%d all=%d" % (name, m, cap, all_patterns)
+    d_text.free()
 
 
 # ------------------------------------------------------------------ tally
