@@ -38,6 +38,8 @@ TALLY_ACCUMULATE, TALLY_ALL_PATTERNS = 1, 2
 PATTERN_NOCASE = 1
 POS_FROM_END = 1
 POS_UNBOUNDED = 0x7FFFFFFF
+SEQ_MAX_PARTS = 32
+GAP_UNBOUNDED = 0x7FFFFFFF
 
 
 class AcmError(RuntimeError):
@@ -67,6 +69,13 @@ NATIVE_API = {
                                                  C.POINTER(C.c_uint)]),
     "acm_automaton_positioned": (C.c_int, [_vp]),
     "acm_automaton_load_position_file": (C.c_int, [_vp, C.c_char_p]),
+    "acm_automaton_add_sequence": (C.c_int, [_vp, _i32p, _i32p, _i32p, C.c_int, C.c_int]),
+    "acm_automaton_num_sequences": (C.c_int, [_vp]),
+    "acm_automaton_sequence": (C.c_int, [_vp, C.c_int, _i32p, _i32p, C.POINTER(_i32p), C.POINTER(_i32p),
+                                         C.POINTER(_i32p)]),
+    "acm_automaton_pattern_sequence": (C.c_int, [_vp, C.c_int, _i32p, _i32p]),
+    "acm_automaton_add_signature": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_uint]),
+    "acm_automaton_load_signature_file": (C.c_int, [_vp, C.c_char_p, C.c_uint]),
     "acm_automaton_set_nocase": (C.c_int, [_vp, C.c_int]),
     "acm_automaton_nocase": (C.c_int, [_vp]),
     "acm_automaton_compile": (C.c_int, [_vp]),
@@ -113,6 +122,9 @@ NATIVE_API = {
     "acm_position_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "acm_position_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.c_long, C.c_long,
                                              C.c_long, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "acm_sequence_workspace_bytes": (C.c_size_t, [_vp, C.c_size_t]),
+    "acm_sequence_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_long, C.c_long, _vp, _vp,
+                                             C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
     "acm_tally_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_tally_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t,
                                           _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

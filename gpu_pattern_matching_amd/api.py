@@ -154,6 +154,60 @@ class Automaton:
             check(n, "acm_automaton_load_position_file")
         return n
 
+    def add_sequence(self, parts, gaps=(), iid=0):
+        """An ordered multi-part signature (acm_automaton_add_sequence): parts are pattern indices, gaps one
+        (lo, hi) per part but the first, the bytes between that part and the one in front; hi None: no upper
+        bound.  Before or after compile(), but before the Matcher is made.  Returns the sequence index."""
+        parts, gaps = list(parts), list(gaps)
+        if len(gaps) != max(len(parts) - 1, 0):
+            raise ValueError("%d parts need %d gaps, not %d" % (len(parts), max(len(parts) - 1, 0), len(gaps)))
+        p = (C.c_int32 * max(len(parts), 1))(*parts)
+        lo = (C.c_int32 * max(len(gaps), 1))(*[g[0] for g in gaps])
+        hi = (C.c_int32 * max(len(gaps), 1))(*[_lib.GAP_UNBOUNDED if g[1] is None else g[1] for g in gaps])
+        r = self.lib.acm_automaton_add_sequence(self.h, p, lo, hi, len(parts), iid)
+        if r < 0:
+            check(r, "acm_automaton_add_sequence")
+        return r
+
+    def add_signature(self, body, iid=0, nocase=False):
+        """A ClamAV-style hex body (acm_automaton_add_signature): hex byte pairs, ??, *, {n}, {n-m}, {-m}, {n-}.
+        Adds its fixed parts as patterns and registers the sequence; only before compile().  Returns the
+        sequence index."""
+        body = body.encode() if isinstance(body, str) else bytes(body)
+        r = self.lib.acm_automaton_add_signature(self.h, body, iid, _lib.PATTERN_NOCASE if nocase else 0)
+        if r < 0:
+            check(r, "acm_automaton_add_signature")
+        return r
+
+    def load_signature_file(self, path, nocase=False):
+        """signatures from a file, one per line with an optional leading "<iid>:"; returns how many"""
+        n = self.lib.acm_automaton_load_signature_file(self.h, str(path).encode(), _lib.PATTERN_NOCASE if nocase else 0)
+        if n < 0:
+            check(n, "acm_automaton_load_signature_file")
+        return n
+
+    @property
+    def num_sequences(self):
+        return self.lib.acm_automaton_num_sequences(self.h)
+
+    def sequence(self, i):
+        """(parts, gaps, iid) of sequence i (acm_automaton_sequence): gaps a list of (lo, hi or None)"""
+        iid, n = C.c_int32(), C.c_int32()
+        parts, lo, hi = _lib._i32p(), _lib._i32p(), _lib._i32p()
+        check(self.lib.acm_automaton_sequence(self.h, i, C.byref(iid), C.byref(n), C.byref(parts), C.byref(lo),
+                                              C.byref(hi)), "acm_automaton_sequence")
+        k = n.value
+        gaps = [(lo[j], None if hi[j] == _lib.GAP_UNBOUNDED else hi[j]) for j in range(k - 1)]
+        return [parts[j] for j in range(k)], gaps, iid.value
+
+    def pattern_sequence(self, p):
+        """(sequence, level) pattern p is a part of, or None (acm_automaton_pattern_sequence)"""
+        s, lv = C.c_int32(), C.c_int32()
+        r = self.lib.acm_automaton_pattern_sequence(self.h, p, C.byref(s), C.byref(lv))
+        if r < 0:
+            check(r, "acm_automaton_pattern_sequence")
+        return (s.value, lv.value) if r else None
+
     def compile(self):
         check(self.lib.acm_automaton_compile(self.h), "acm_automaton_compile")
         return self
@@ -242,6 +296,7 @@ class Matcher:
         check(self.lib.acm_dfa_upload(automaton.h, device, C.byref(h)), "acm_dfa_upload")
         self.dfa = h.value
         self.num_patterns = automaton.num_patterns
+        self.mixed, self.positioned = automaton.mixed_case, automaton.positioned     # as uploaded (scan_sequences)
         self.max_text = 0
         self.ws = self.pat_plane = self.off_plane = None
         self.reserve(max_text, plane_capacity)
@@ -764,6 +819,110 @@ class Matcher:
             o = off.to_numpy(np.int32, m + 2, stream=self.stream)
             und = int(info.to_numpy(np.int32, 4, stream=self.stream)[0])
             return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1]), und
+        finally:
+            for b in bufs:
+                b.free()
+
+    def sequence_async(self, pat_plane, off_plane, max_records, seq_out, off_out, out_capacity, info, seg_start=None,
+                       segments=0, lead_begin=0, text_end=0, workspace=None, stream=None):
+        """Enqueue the sequence pass (acm_sequence_matches_async) over caller-owned device planes of pattern
+        indices, one record per occurrence (the all-patterns output of the expand, word, case or position
+        pass): one record (sequence index, end offset) per match of a sequence (Automaton.add_sequence).
+        info: device int32[4].  The pass orders max_records cells: size it to the planes.  workspace: (ptr,
+        nbytes), or None for a temporary one that lives until the stream has passed it (the call then
+        synchronises)."""
+        st = stream if stream is not None else self.stream
+        tmp = None
+        if workspace is None:
+            nb = self.lib.acm_sequence_workspace_bytes(self.dfa, max_records)
+            tmp = DeviceArray(max(nb, 16))
+            workspace = (tmp.ptr, nb)
+        try:
+            check(self.lib.acm_sequence_matches_async(
+                self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, _ptr(seg_start), segments, lead_begin, text_end,
+                _ptr(seq_out), _ptr(off_out), out_capacity, _ptr(info), _ptr(workspace[0]), workspace[1], st),
+                "acm_sequence_matches_async")
+        finally:
+            if tmp is not None:
+                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
+                tmp.free()
+
+    def scan_sequences(self, text=None, texts=None, lead_begin=0, init_state=0, before=b"", out_capacity=None):
+        """Matches of the automaton's sequences (Automaton.add_sequence, add_signature): a REPORT_STATE scan,
+        the segment pass when texts is given (each text matched alone), every pattern of every record (the
+        case pass when the automaton is mixed, else acm_expand_matches_async), the position pass in its all
+        form when the automaton is positioned (a window on the first part anchors the signature), then the
+        sequence pass (acm_sequence_matches_async).  text: host bytes; or None with texts: a list of bytes-like
+        objects or a (uint8 array, int32 starts) pair.  lead_begin: where the text in front of the first
+        start began.  before: the bytes in front of text, for the case pass.  Returns (offsets, sequences,
+        last_state, info): a record per match, the sequence index and the offset it ends at; info: [records
+        that are a part, alive records over all levels, 0, 0].  A sequence whose parts lie in different calls
+        is not joined: scan whole texts."""
+        if texts is not None:
+            t, starts = self.pack_segments(texts)
+        else:
+            t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
+                else np.ascontiguousarray(text, dtype=np.uint8)
+            starts = np.zeros(0, dtype=np.int32)
+        bf = np.frombuffer(bytes(before), dtype=np.uint8)
+        self.reserve(max(t.size, 1))
+        d = DeviceArray.from_numpy(t, stream=self.stream)
+        d_bf = DeviceArray.from_numpy(bf, stream=self.stream) if bf.size else None
+        nseg = int(starts.size)
+        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
+        max_records = self.plane_capacity - 2
+        cap = self.plane_capacity
+        icap = 8 * cap
+        bufs = [b for b in (d, d_bf, d_st) if b is not None]
+
+        def count_of(plane, room):
+            n = int(plane.to_numpy(np.int32, 1, stream=self.stream)[0])
+            if n > room - 2:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_sequences", "%d records but planes hold %d" % (n, room - 2))
+            return n
+        try:
+            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
+            sp, so = self.pat_plane, self.off_plane
+            if nseg:
+                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
+                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
+                bufs += sb
+                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
+                                   report=_lib.REPORT_STATE, workspace=(sb[0].ptr, seg_ws))
+                sp, so = sb[1], sb[2]
+            mixed = self.mixed
+            nb = (self.lib.acm_case_workspace_bytes if mixed else self.lib.acm_expand_workspace_bytes)(max_records)
+            tb = [DeviceArray(max(nb, 16)), DeviceArray(icap * 4), DeviceArray(icap * 4)]
+            bufs += tb
+            if mixed:
+                self.case_async(sp, so, max_records, d, 0, t.size, tb[1], tb[2], icap, before=d_bf,
+                                before_len=int(bf.size), all_patterns=True, workspace=(tb[0].ptr, nb))
+            else:
+                check(self.lib.acm_expand_matches_async(self.dfa, _ptr(sp), _ptr(so), max_records, tb[1].ptr, tb[2].ptr,
+                                                        icap, tb[0].ptr, nb, self.stream), "acm_expand_matches_async")
+            n = count_of(tb[1], icap)
+            sp, so = tb[1], tb[2]
+            info = DeviceArray(16)
+            bufs.append(info)
+            if self.positioned:
+                nb = self.lib.acm_position_workspace_bytes(n)
+                pb = [DeviceArray(max(nb, 16)), DeviceArray((n + 2) * 4), DeviceArray((n + 2) * 4)]
+                bufs += pb
+                self.position_async(sp, so, n, pb[1], pb[2], n + 2, info, report=_lib.REPORT_HEAD, seg_start=d_st,
+                                    segments=nseg, lead_begin=int(lead_begin), text_end=int(t.size), open_end=int(t.size),
+                                    all_patterns=True, workspace=(pb[0].ptr, nb))
+                n = count_of(pb[1], n + 2)
+                sp, so = pb[1], pb[2]
+            ocap = out_capacity if out_capacity is not None else n + 2
+            nb = self.lib.acm_sequence_workspace_bytes(self.dfa, n)
+            qb = [DeviceArray(max(nb, 16)), DeviceArray(ocap * 4), DeviceArray(ocap * 4)]
+            bufs += qb
+            self.sequence_async(sp, so, n, qb[1], qb[2], ocap, info, seg_start=d_st, segments=nseg,
+                                lead_begin=int(lead_begin), text_end=int(t.size), workspace=(qb[0].ptr, nb))
+            m = count_of(qb[1], ocap)
+            q = qb[1].to_numpy(np.int32, m + 2, stream=self.stream)
+            o = qb[2].to_numpy(np.int32, m + 2, stream=self.stream)
+            return o[1:1 + m].astype(np.uint32), q[1:1 + m].copy(), int(q[m + 1]), info.to_numpy(np.int32, 4, stream=self.stream)
         finally:
             for b in bufs:
                 b.free()

@@ -87,6 +87,15 @@ double now_us()
 	       "                 -i, -c, -n and with -W or -I.  An end-anchored candidate in a file that goes on in the\n"
 	       "                 next buffer cannot be decided: it is counted and reported as an error at exit\n"
 	       "                 (extension; not with -F)\n"
+	       "  -Q file        multi-part signatures, one per line: a ClamAV-style hex body (hex byte pairs, ??, *, {n},\n"
+	       "                 {n-m}, {-m}, {n-}) with an optional leading '<decimal id>:'.  Instead of -p or beside it (the\n"
+	       "                 patterns of -p and -I come first).  The matches printed and counted are then those of the\n"
+	       "                 signatures, joined on the device: the -v line names the signature's id and the offset its\n"
+	       "                 last part ends at.  A signature lies in one buffer and, with -S, in one file.  The pass\n"
+	       "                 orders one cell per byte of a buffer, at most 4 Mi (36 bytes of device memory each, per\n"
+	       "                 buffer): a buffer with more pattern records than that is an error.  Composes with\n"
+	       "                 -i, -I, -S and -P (the indices of the parts follow those of -p and -I)\n"
+	       "                 (extension; not with -c, -n, -W or -A)\n"
 	       "  -S             every input unit is its own text: a file, or with -t a line; no match\n"
 	       "                 spans two of them (extension; data appended under -F continues its file\n"
 	       "                 when the worker's previous chunk came from the same file)\n"
@@ -140,11 +149,12 @@ std::vector<std::string> regular_files_in(std::string dir)
 }
 
 struct Config {
-	std::string pat_path, data_path, loose_path, pos_path;   // loose_path: -I, pos_path: -P
+	std::string pat_path, data_path, loose_path, pos_path, seq_path;   // loose_path: -I, pos_path: -P, seq_path: -Q
 	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0,
 	    words = 0, count = 0, lineno = 0;
 	int cased = 0;           // -I without -i: the records go through the case pass
 	int pos = 0;             // -P: the records go through the position pass
+	int seq = 0;             // -Q: every pattern of the records goes through the sequence pass; its records are reported
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
 	long global_ws = -1, local_ws = -1, chunk = -1;
@@ -157,12 +167,16 @@ struct Shared {
 	std::vector<int> fds;
 	std::vector<std::string> pat_bytes;   // for the -v line
 	std::vector<int> pat_iid;
+	std::vector<int> seq_iid;             // -Q: the id of every sequence, for the -v line
 	int max_pattern_len = 0;
 	pthread_mutex_t print_lock = PTHREAD_MUTEX_INITIALIZER;
 	pthread_barrier_t ready;   // workers have their buffers; the clock starts (the reference
 	                           // also allocates in ocl_worker_ctx_init, before start_time)
 };
 
+// -Q: the pattern records of one buffer the sequence pass takes.  The pass keys and orders that many cells for
+// every buffer, however few records it holds, in 36 bytes of workspace each: a buffer with more is an error
+constexpr size_t kSeqMaxRecords = (size_t)4 << 20;
 constexpr size_t kAllFactor = 4;   // -A: records the expanded planes hold per text byte
 
 struct Buffer {   // one of the two staging buffers of a worker
@@ -187,7 +201,10 @@ struct Buffer {   // one of the two staging buffers of a worker
 	void *d_pos_pat = nullptr, *d_pos_off = nullptr, *d_pos_ws = nullptr, *d_pos_info = nullptr;
 	int32_t *h_pos_info = nullptr;
 	size_t pos_ws_bytes = 0, pos_cap = 0;
-	long lead_begin = 0;         // -P: where the text that goes on into this buffer began, in its stream's coordinates (<= 0)
+	// -Q only: the sequence pass's planes, workspace and info; seq_max: the pattern-form records it takes
+	void *d_seq_pat = nullptr, *d_seq_off = nullptr, *d_seq_ws = nullptr, *d_seq_info = nullptr;
+	size_t seq_ws_bytes = 0, seq_max = 0;
+	long lead_begin = 0;         // -P, -Q: where the text that goes on into this buffer began, in its stream's coordinates (<= 0)
 	bool end_known = false;      // -P: the stream's last text ends with the stream (its file, or with -t its line, is finished)
 	bool last_of_input = false;  // -P: nothing of the worker's input follows this buffer
 	int32_t end_start = 0;       // -P: the start behind the last text when end_known (copied from here)
@@ -316,7 +333,7 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 		CK(acm_rt_host_alloc((void **)&b.h_cnt_total, 64));
 	}
 	if (c.pos) {
-		b.pos_cap = c.all_patterns ? size * kAllFactor + 2 : size + 2;
+		b.pos_cap = (c.all_patterns || c.seq) ? size * kAllFactor + 2 : size + 2;
 		b.pos_ws_bytes = acm_position_workspace_bytes(size * kAllFactor);
 		CK(acm_rt_malloc(&b.d_pos_pat, b.pos_cap * 4));
 		CK(acm_rt_malloc(&b.d_pos_off, b.pos_cap * 4));
@@ -325,7 +342,7 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 		CK(acm_rt_host_alloc((void **)&b.h_pos_info, 64));
 		b.h_pos_info[0] = 0;
 	}
-	if (c.all_patterns || (c.pos && (c.words || c.cased))) {   // (-P: the word or case pass hands every kept pattern on)
+	if (c.all_patterns || c.seq || (c.pos && (c.words || c.cased))) {   // (-P: the word or case pass hands every kept pattern on; -Q takes every pattern)
 		b.expand_ws_bytes = acm_expand_workspace_bytes(size);
 		// every pattern of every final state's list: more records than text bytes when patterns nest
 		// (aaa, aaaa, aaaaa over a run of a's); the planes hold kAllFactor per byte, beyond that the
@@ -493,7 +510,7 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 	// final states instead of head patterns where a pass over the records follows: the segment pass
 	// clamps every one to its own text, the word pass keeps whole words, the case pass (-I) the exact
 	// patterns where the text has their case, the expansion (-A) lists them
-	const bool states = c.segmented || c.words || c.all_patterns || c.cased;   // (-P needs -S)
+	const bool states = c.segmented || c.words || c.all_patterns || c.cased || c.seq;   // (-P needs -S)
 	sb.report = states ? ACM_REPORT_STATE : ACM_REPORT_HEAD;
 	if (c.segmented && !b.seg_starts.empty())
 		CK(acm_rt_memcpy_h2d(b.d_seg_start, b.seg_starts.data(), b.seg_starts.size() * 4, s));
@@ -504,7 +521,7 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 	CK(acm_scan_batch_async(w.dfa, &sb));
 	if (c.segmented) {
 		CK(acm_segment_matches_async(w.dfa, pat, off, cap - 2, (const int32_t *)b.d_seg_start, b.seg_starts.size(),
-		    (long)b.stream_len, (c.all_patterns || c.words || c.cased || c.pos) ? ACM_REPORT_STATE : ACM_REPORT_HEAD,
+		    (long)b.stream_len, (c.all_patterns || c.words || c.cased || c.pos || c.seq) ? ACM_REPORT_STATE : ACM_REPORT_HEAD,
 		    (int32_t *)b.d_seg_pat, (int32_t *)b.d_seg_off, nullptr, cap, nullptr, b.d_seg_ws, b.seg_ws_bytes, s));
 		pat = (int32_t *)b.d_seg_pat;
 		off = (int32_t *)b.d_seg_off;
@@ -543,7 +560,7 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		if (every)
 			CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
 	} else if (c.cased) {   // the candidates of a mixed automaton made exact; with -A every kept pattern (the expansion's place)
-		const bool every = c.all_patterns || c.pos;   // (-P: the position pass picks the first kept one)
+		const bool every = c.all_patterns || c.pos || c.seq;   // (-P: the position pass picks the first kept one)
 		int32_t *cp = (int32_t *)(every ? b.d_pat_all : b.d_case_pat);
 		int32_t *co = (int32_t *)(every ? b.d_off_all : b.d_case_off);
 		const size_t ccap = every ? b.all_cap : b.scan_cap;
@@ -559,7 +576,7 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		cap = ccap;
 		if (every)
 			CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
-	} else if (c.all_patterns && !c.pos) {   // every pattern of each final state's match list
+	} else if ((c.all_patterns || c.seq) && !c.pos) {   // every pattern of each final state's match list
 		CK(acm_expand_matches_async(w.dfa, pat, off, cap - 2, (int32_t *)b.d_pat_all, (int32_t *)b.d_off_all,
 		    b.all_cap, b.d_expand_ws, b.expand_ws_bytes, s));
 		pat = (int32_t *)b.d_pat_all;
@@ -574,14 +591,24 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		const bool heads = c.words || c.cased;
 		CK(acm_position_matches_async(w.dfa, pat, off, cap - 2, heads ? ACM_REPORT_HEAD : ACM_REPORT_STATE,
 		    (const int32_t *)b.d_seg_start, b.seg_starts.size() + (b.end_known ? 1 : 0), b.lead_begin, (long)b.stream_len,
-		    b.last_of_input ? (long)b.stream_len : -1L, c.all_patterns, (int32_t *)b.d_pos_pat, (int32_t *)b.d_pos_off,
+		    b.last_of_input ? (long)b.stream_len : -1L, c.all_patterns || c.seq, (int32_t *)b.d_pos_pat, (int32_t *)b.d_pos_off,
 		    b.pos_cap, (int32_t *)b.d_pos_info, b.d_pos_ws, b.pos_ws_bytes, s));
 		pat = (int32_t *)b.d_pos_pat;
 		off = (int32_t *)b.d_pos_off;
 		cap = b.pos_cap;
 		CK(acm_rt_memcpy_d2h(b.h_pos_info, b.d_pos_info, 16, s));
-		if (c.all_patterns && !heads)
+		if ((c.all_patterns || c.seq) && !heads)
 			CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
+	}
+	if (c.seq) {
+		// the signatures: the parts' records (every pattern, whatever pass wrote them) joined on the device.
+		// Without -S the stream is one text that began long ago: only a chain inside this buffer is found.
+		CK(acm_sequence_matches_async(w.dfa, pat, off, b.seq_max, c.segmented ? (const int32_t *)b.d_seg_start : nullptr,
+		    c.segmented ? b.seg_starts.size() : 0, c.segmented ? b.lead_begin : -(1L << 40), (long)b.stream_len,
+		    (int32_t *)b.d_seq_pat, (int32_t *)b.d_seq_off, b.seq_max + 2, (int32_t *)b.d_seq_info, b.d_seq_ws, b.seq_ws_bytes, s));
+		pat = (int32_t *)b.d_seq_pat;
+		off = (int32_t *)b.d_seq_off;
+		cap = b.seq_max + 2;
 	}
 	if (c.lineno) {
 		// the lines of this buffer's stream, chained to the buffer in front of it on the device; then the
@@ -643,7 +670,12 @@ void collect(Worker &w, Buffer &b)
 	CK(acm_rt_event_sync(b.done));   // (this buffer's copies; the next buffer's scan may still be running)
 	if (b.h_all_count && (size_t)*b.h_all_count > b.all_cap - 2) {
 		fprintf(stderr, "ERROR: %s produced %d records for one buffer, the planes hold %zu; use a smaller -G/-B\n",
-		    c.all_patterns ? "-A" : "-P", *b.h_all_count, b.all_cap - 2);
+		    c.seq ? "-Q" : c.all_patterns ? "-A" : "-P", *b.h_all_count, b.all_cap - 2);
+		exit(1);
+	}
+	if (c.seq && (size_t)*b.h_all_count > b.seq_max) {
+		fprintf(stderr, "ERROR: -Q: %d pattern records in one buffer, the sequence pass takes %zu; use a smaller -G/-B\n",
+		    *b.h_all_count, b.seq_max);
 		exit(1);
 	}
 	if (c.pos)
@@ -677,7 +709,10 @@ void collect(Worker &w, Buffer &b)
 			if (!c.verbose)
 				continue;
 			pthread_mutex_lock(&w.sh->print_lock);
-			if (c.lineno) {
+			if (c.seq) {
+				printf("Sequence %d found in file '%s' at offset %d [relative: %d]\n", w.sh->seq_iid[p_idx],
+				    w.sh->files[b.file_ids[i]].c_str(), off, off - b.h_indices[i]);
+			} else if (c.lineno) {
 				// newlines in front of the record less those in front of its file's start; a file that began
 				// in an earlier buffer adds what those buffers counted for it
 				const uint64_t d_rec = (uint64_t)b.h_results3[(size_t)(j + 1) * chunks + i];
@@ -694,7 +729,7 @@ void collect(Worker &w, Buffer &b)
 				fwrite(b.h_data + b.h_indices[i], 1, (size_t)b.h_sizes[i], stdout);
 			} else {             // some context around the match, up to a newline
 				printf(" ... ");
-				const int plen = (int)w.sh->pat_bytes[p_idx].size();
+				const int plen = c.seq ? 0 : (int)w.sh->pat_bytes[p_idx].size();
 				const int lo = std::max(0, off - plen - 10);
 				for (int k = lo; k < off + 10 && (size_t)k < b.bytes; k++) {
 					if (b.h_data[k] == '\n')
@@ -727,6 +762,15 @@ void *worker_main(void *arg)
 	CK(acm_rt_malloc(&w.ws, w.ws_bytes));
 	buffer_alloc(w.buf[0], c, w.stream);
 	buffer_alloc(w.buf[1], c, w.stream);
+	if (c.seq)
+		for (Buffer &b : w.buf) {   // (the workspace depends on the uploaded set)
+			b.seq_max = std::min((size_t)c.global_ws * c.chunk, kSeqMaxRecords);
+			b.seq_ws_bytes = acm_sequence_workspace_bytes(w.dfa, b.seq_max);
+			CK(acm_rt_malloc(&b.d_seq_pat, (b.seq_max + 2) * 4));
+			CK(acm_rt_malloc(&b.d_seq_off, (b.seq_max + 2) * 4));
+			CK(acm_rt_malloc(&b.d_seq_ws, b.seq_ws_bytes));
+			CK(acm_rt_malloc(&b.d_seq_info, 16));
+		}
 	if (c.words || c.cased)
 		for (void *&t : w.d_tail)
 			CK(acm_rt_malloc(&t, (size_t)sh.max_pattern_len + 16));
@@ -832,7 +876,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -866,12 +910,14 @@ int main(int argc, char **argv)
 		case 'n': c.lineno = 1; break;
 		case 'I': c.loose_path = optarg; break;
 		case 'P': c.pos_path = optarg; break;
+		case 'Q': c.seq_path = optarg; break;
 		default: usage();
 		}
 	}
 	int err = 0;   // check_args, ocl_aho_grep.c:210-266
-	if (c.pat_path.empty()) { printf("ERROR: No pattern file\n"); err++; }
-	else if (access(c.pat_path.c_str(), R_OK) != 0) {
+	c.seq = !c.seq_path.empty();
+	if (c.pat_path.empty() && !c.seq) { printf("ERROR: No pattern file\n"); err++; }
+	else if (!c.pat_path.empty() && access(c.pat_path.c_str(), R_OK) != 0) {
 		printf("ERROR: File '%s' does not exist\n", c.pat_path.c_str()); err++;
 	}
 	if (c.data_path.empty()) { printf("ERROR: No data file\n"); err++; }
@@ -907,6 +953,13 @@ int main(int argc, char **argv)
 		err++;
 	}
 	c.pos = !c.pos_path.empty();
+	if (c.seq && access(c.seq_path.c_str(), R_OK) != 0) {
+		printf("ERROR: File '%s' does not exist\n", c.seq_path.c_str()); err++;
+	}
+	if (c.seq && (c.count || c.lineno || c.words || c.all_patterns)) {   // the records are sequence matches, not patterns
+		printf("ERROR: -Q cannot be combined with -c, -n, -W or -A: the records of -Q are signature matches\n");
+		err++;
+	}
 	if (c.lineno && c.text_mode) {
 		printf("ERROR: -n needs binary mode: -t already makes every line a chunk\n");
 		err++;
@@ -966,7 +1019,7 @@ int main(int argc, char **argv)
 	// one automaton, one copy per device, shared by the workers of that device
 	acm_automaton *aut = acm_automaton_new();
 	CK(acm_automaton_set_nocase(aut, c.nocase));
-	if (acm_automaton_load_file(aut, c.pat_path.c_str(), c.hex, c.pat_limit) < 0) {
+	if (!c.pat_path.empty() && acm_automaton_load_file(aut, c.pat_path.c_str(), c.hex, c.pat_limit) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}
@@ -974,6 +1027,15 @@ int main(int argc, char **argv)
 	    acm_automaton_load_file_ex(aut, c.loose_path.c_str(), c.hex, c.pat_limit, ACM_PATTERN_NOCASE) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
+	}
+	if (c.seq && acm_automaton_load_signature_file(aut, c.seq_path.c_str(), 0) < 0) {
+		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
+		return 1;
+	}
+	for (int i = 0; i < acm_automaton_num_sequences(aut); i++) {
+		int iid = 0;
+		acm_automaton_sequence(aut, i, &iid, nullptr, nullptr, nullptr, nullptr);
+		sh.seq_iid.push_back(iid);
 	}
 	if (c.pos && acm_automaton_load_position_file(aut, c.pos_path.c_str()) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());

@@ -56,7 +56,16 @@ struct acm_automaton {
 		int32_t pos_lo = 0, pos_hi = INT32_MAX;
 		unsigned pos_flags = 0;
 		bool positioned() const { return pos_lo != 0 || pos_hi != INT32_MAX || pos_flags != 0; }
+		// the sequence this pattern is a part of (acm_automaton_add_sequence) and its level there, or -1
+		int32_t seq = -1, seq_level = 0;
 	};
+	// ordered multi-part signatures (acm_automaton_add_sequence).  compile never reads these:
+	// acm_dfa_upload copies them for the sequence pass (sequence.hip)
+	struct Sequence {
+		int iid;
+		std::vector<int32_t> parts, gap_lo, gap_hi;   // gaps: parts.size() - 1 cells, gap j - 1 in front of part j
+	};
+	std::vector<Sequence> sequences;
 	std::vector<Pattern> patterns;         // bytes folded by compile when nocase: every table is built from these
 	int max_pattern_len = 0;
 	bool compiled = false;

@@ -234,8 +234,6 @@ extern "C" int acm_automaton_load_position_file(acm_automaton *a, const char *pa
 	return (int)lines.size();
 }
 
-// ---- pattern file ------------------------------------------------------------
-
 static int hex_nibble(unsigned char c)
 {
 	if (c >= '0' && c <= '9') return c - '0';
@@ -243,6 +241,273 @@ static int hex_nibble(unsigned char c)
 	if (c >= 'A' && c <= 'F') return c - 'A' + 10;
 	return -1;
 }
+
+// ---- sequences -----------------------------------------------------------------
+
+extern "C" int acm_automaton_add_sequence(acm_automaton *a, const int32_t *parts, const int32_t *gap_lo, const int32_t *gap_hi,
+    int nparts, int iid)
+{
+	if (!a || !parts || nparts < 1)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_sequence: bad arguments");
+	if (nparts > ACM_SEQ_MAX_PARTS)
+		return acm::fail(ACM_ERR_LIMIT, "acm_automaton_add_sequence: %d parts, at most %d", nparts, ACM_SEQ_MAX_PARTS);
+	if (nparts > 1 && (!gap_lo || !gap_hi))
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_sequence: %d parts without gaps", nparts);
+	if (a->sequences.size() >= (size_t)INT32_MAX)
+		return acm::fail(ACM_ERR_LIMIT, "acm_automaton_add_sequence: too many sequences");
+	for (int j = 0; j < nparts; j++) {
+		const int32_t p = parts[j];
+		if (p < 0 || p >= (int)a->patterns.size())
+			return acm::fail(ACM_ERR_ARG, "acm_automaton_add_sequence: part %d: pattern index %d out of range", j, p);
+		if (a->patterns[p].seq >= 0)
+			return acm::fail(ACM_ERR_ARG, "acm_automaton_add_sequence: part %d: pattern %d is a part of sequence %d", j, p,
+			    a->patterns[p].seq);
+		if (a->patterns[p].bytes.empty())
+			return acm::fail(ACM_ERR_ARG, "acm_automaton_add_sequence: part %d: pattern %d has length 0", j, p);
+		for (int i = 0; i < j; i++)
+			if (parts[i] == p)
+				return acm::fail(ACM_ERR_ARG, "acm_automaton_add_sequence: pattern %d is part %d and part %d", p, i, j);
+		if (j > 0 && (gap_lo[j - 1] < 0 || gap_hi[j - 1] < 0))
+			return acm::fail(ACM_ERR_ARG, "acm_automaton_add_sequence: gap %d: negative bound (%d, %d)", j, gap_lo[j - 1],
+			    gap_hi[j - 1]);
+	}
+	acm_automaton::Sequence s;
+	s.iid = iid;
+	s.parts.assign(parts, parts + nparts);
+	if (nparts > 1) {
+		s.gap_lo.assign(gap_lo, gap_lo + nparts - 1);
+		s.gap_hi.assign(gap_hi, gap_hi + nparts - 1);
+	}
+	const int index = (int)a->sequences.size();
+	a->sequences.push_back(std::move(s));
+	for (int j = 0; j < nparts; j++) {
+		a->patterns[parts[j]].seq = index;
+		a->patterns[parts[j]].seq_level = j;
+	}
+	return index;
+}
+
+extern "C" int acm_automaton_num_sequences(const acm_automaton *a) { return a ? (int)a->sequences.size() : 0; }
+
+extern "C" int acm_automaton_sequence(const acm_automaton *a, int index, int *iid, int *nparts, const int32_t **parts,
+    const int32_t **gap_lo, const int32_t **gap_hi)
+{
+	if (!a || index < 0 || index >= (int)a->sequences.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_sequence: index out of range");
+	const acm_automaton::Sequence &s = a->sequences[index];
+	if (iid) *iid = s.iid;
+	if (nparts) *nparts = (int)s.parts.size();
+	if (parts) *parts = s.parts.data();
+	if (gap_lo) *gap_lo = s.gap_lo.data();
+	if (gap_hi) *gap_hi = s.gap_hi.data();
+	return ACM_OK;
+}
+
+extern "C" int acm_automaton_pattern_sequence(const acm_automaton *a, int pattern, int *sequence, int *level)
+{
+	if (!a || pattern < 0 || pattern >= (int)a->patterns.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_pattern_sequence: index out of range");
+	const acm_automaton::Pattern &p = a->patterns[pattern];
+	if (p.seq < 0)
+		return 0;
+	if (sequence) *sequence = p.seq;
+	if (level) *level = p.seq_level;
+	return 1;
+}
+
+namespace {
+
+// a signature body, parsed: the fixed parts and the gap in front of every part but the first
+struct Signature {
+	std::vector<std::vector<unsigned char>> parts;
+	std::vector<int32_t> gap_lo, gap_hi;
+	int iid = 0;
+	bool has_iid = false;
+};
+
+// Parses body (hex byte pairs, ??, *, {n}, {n-m}, {-m}, {n-}).  Returns 0, or the column (from 1) of the
+// first byte that is wrong, with why.
+int parse_signature(const char *s, Signature &sig, const char *&why)
+{
+	sig.parts.clear();
+	sig.gap_lo.clear();
+	sig.gap_hi.clear();
+	std::vector<unsigned char> part;
+	int64_t lo = 0, hi = 0;   // the gap being summed (hi: -1 unbounded)
+	bool in_gap = false;
+	size_t i = 0;
+	auto number = [&](int64_t &v) {   // digits at i; false where there is none or the value is too large
+		if (!isdigit((unsigned char)s[i]))
+			return false;
+		for (v = 0; isdigit((unsigned char)s[i]); i++)
+			if ((v = v * 10 + (s[i] - '0')) >= INT32_MAX)
+				return false;
+		return true;
+	};
+	auto add_gap = [&](int64_t l, int64_t h) {
+		if (!in_gap) {
+			sig.parts.push_back(part);
+			part.clear();
+			lo = hi = 0;
+			in_gap = true;
+		}
+		lo += l;
+		hi = (hi < 0 || h < 0) ? -1 : hi + h;
+		return lo < INT32_MAX && hi < INT32_MAX;
+	};
+	while (s[i]) {
+		const size_t at = i;
+		const unsigned char c = (unsigned char)s[i];
+		int64_t l = 0, h = 0;
+		if (hex_nibble(c) >= 0) {
+			if (hex_nibble((unsigned char)s[i + 1]) < 0) {
+				why = s[i + 1] == '?' ? "nibble wildcards are not supported" : "odd hex digit";
+				return (int)at + 1;
+			}
+			if (in_gap) {
+				sig.gap_lo.push_back((int32_t)lo);
+				sig.gap_hi.push_back(hi < 0 ? INT32_MAX : (int32_t)hi);
+				in_gap = false;
+			}
+			part.push_back((unsigned char)(hex_nibble(c) << 4 | hex_nibble((unsigned char)s[i + 1])));
+			i += 2;
+			continue;
+		}
+		if (c == '?') {
+			if (s[i + 1] != '?') {
+				why = "nibble wildcards are not supported";
+				return (int)at + 1;
+			}
+			l = h = 1;
+			i += 2;
+		} else if (c == '*') {
+			h = -1;
+			i++;
+		} else if (c == '{') {
+			i++;
+			bool ok;
+			if (s[i] == '-') {   // {-m}
+				i++;
+				ok = number(h);
+			} else {
+				ok = number(l);
+				if (ok && s[i] == '-') {   // {n-} or {n-m}
+					i++;
+					if (s[i] == '}')
+						h = -1;
+					else
+						ok = number(h);
+				} else {
+					h = l;   // {n}
+				}
+			}
+			if (!ok || s[i] != '}') {
+				why = "not {n}, {n-m}, {-m} or {n-}";
+				return (int)at + 1;
+			}
+			i++;
+		} else {
+			why = (c == '(' || c == '|' || c == ')') ? "alternatives are not supported"
+			      : c == '!'                         ? "negation is not supported"
+			                                         : "not a hex digit, ??, * or {..}";
+			return (int)at + 1;
+		}
+		if (part.empty() && !in_gap) {
+			why = "a gap in front of the first part";
+			return (int)at + 1;
+		}
+		if (!add_gap(l, h)) {
+			why = "gap too large";
+			return (int)at + 1;
+		}
+	}
+	if (in_gap || part.empty()) {
+		why = in_gap ? "a gap behind the last part" : "empty signature";
+		return (int)i + 1;
+	}
+	sig.parts.push_back(part);
+	if (sig.parts.size() > (size_t)ACM_SEQ_MAX_PARTS) {
+		why = "too many parts";
+		return (int)i + 1;
+	}
+	return 0;
+}
+
+// adds the parts and the sequence of a parsed signature: cannot fail but for memory
+int apply_signature(acm_automaton *a, const Signature &sig, int iid, unsigned flags)
+{
+	std::vector<int32_t> parts;
+	for (const auto &p : sig.parts) {
+		parts.push_back((int32_t)a->patterns.size());
+		if (int rc = acm_automaton_add_ex(a, p.data(), (int)p.size(), iid, flags))
+			return rc;
+	}
+	return acm_automaton_add_sequence(a, parts.data(), sig.gap_lo.data(), sig.gap_hi.data(), (int)parts.size(), iid);
+}
+
+}  // namespace
+
+extern "C" int acm_automaton_add_signature(acm_automaton *a, const char *body, int iid, unsigned flags)
+{
+	if (!a || !body)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_signature: bad arguments");
+	if (flags & ~(unsigned)ACM_PATTERN_NOCASE)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_signature: unknown flag bits 0x%x", flags & ~(unsigned)ACM_PATTERN_NOCASE);
+	if (a->compiled)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_signature: automaton already compiled");
+	Signature sig;
+	const char *why = "";
+	if (const int col = parse_signature(body, sig, why))
+		return acm::fail(ACM_ERR_PARSE, "signature: column %d: %s", col, why);
+	return apply_signature(a, sig, iid, flags);
+}
+
+extern "C" int acm_automaton_load_signature_file(acm_automaton *a, const char *path, unsigned flags)
+{
+	if (!a || !path)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_load_signature_file: bad arguments");
+	if (flags & ~(unsigned)ACM_PATTERN_NOCASE)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_load_signature_file: unknown flag bits 0x%x",
+		    flags & ~(unsigned)ACM_PATTERN_NOCASE);
+	if (a->compiled)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_load_signature_file: automaton already compiled");
+	std::ifstream in(path);
+	if (!in)
+		return acm::fail(ACM_ERR_IO, "cannot open signature file '%s': %s", path, strerror(errno));
+	std::vector<Signature> sigs;   // applied only when the whole file has parsed
+	std::string line;
+	for (int line_no = 1; std::getline(in, line); line_no++) {
+		while (!line.empty() && (line.back() == '\n' || line.back() == '\r' || line.back() == ' ' || line.back() == '\t'))
+			line.pop_back();
+		size_t b = line.find_first_not_of(" \t");
+		if (b == std::string::npos || line[b] == '#')
+			continue;
+		Signature sig;
+		size_t k = b;
+		int64_t iid = 0;
+		while (k < line.size() && isdigit((unsigned char)line[k]) && iid <= INT32_MAX)
+			iid = iid * 10 + (line[k++] - '0');
+		if (k > b && k < line.size() && line[k] == ':') {
+			if (iid > INT32_MAX)
+				return acm::fail(ACM_ERR_PARSE, "%s:%d: iid too large", path, line_no);
+			sig.iid = (int)iid;
+			sig.has_iid = true;
+			b = k + 1;
+		}
+		const char *why = "";
+		if (const int col = parse_signature(line.c_str() + b, sig, why))
+			return acm::fail(ACM_ERR_PARSE, "%s:%d: column %d: %s", path, line_no, (int)b + col, why);
+		sigs.push_back(std::move(sig));
+	}
+	for (const Signature &sig : sigs) {
+		const int rc = apply_signature(a, sig, sig.has_iid ? sig.iid : (int)a->sequences.size(), flags);
+		if (rc < 0)
+			return rc;
+	}
+	return (int)sigs.size();
+}
+
+// ---- pattern file ------------------------------------------------------------
 
 // "[+-]?digits" followed by a blank => the file is "ID pattern" per line.
 // The reference decides this on line 0 only (ocl_worker.c:79-102); its scan

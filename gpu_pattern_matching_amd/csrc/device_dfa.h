@@ -61,6 +61,13 @@ struct acm_dfa {
 	// a positioned automaton only (acm_automaton_positioned at upload), for the position pass (position.hip); null otherwise
 	bool positioned = false;
 	int32_t *d_pos_ent = nullptr;        // [patterns][4] {lo, hi, flags, length}: one 16-byte load per entry
+	// an automaton with sequences only (acm_automaton_add_sequence before upload), for the sequence pass
+	// (sequence.hip); null otherwise.  A SLOT is a part of a sequence; slots are numbered level-major (every
+	// level-0 part, then every level-1 part, ...), so that records ordered by slot lie level by level.
+	int32_t *d_seq_ent = nullptr;        // [patterns][4] {slot or -1, lo, hi of the gap in front, length}
+	int32_t *d_seq_slot = nullptr;       // [slots][2] {slot of the part in front or -1, sequence index or -1: not the last part}
+	uint32_t seq_slots = 0, seq_levels = 0;
+	uint32_t seq_level_base[ACM_SEQ_MAX_PARTS + 1] = { 0 };   // slots [base[j], base[j + 1]) are level j
 	size_t device_bytes = 0;
 	void *arena = nullptr;               // one allocation for the small tables (device_dfa.hip, upload_small)
 	size_t arena_bytes = 0, arena_used = 0;

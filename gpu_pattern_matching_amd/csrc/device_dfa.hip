@@ -273,6 +273,44 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 			}
 			rc = upload(&d->d_pos_ent, ent.data(), ent.size(), &d->device_bytes);
 		}
+		// an automaton with sequences (acm_automaton_add_sequence): every part is a slot, numbered level by
+		// level; per pattern its slot, the gap in front of it and its length, per slot the part in front and,
+		// for a last part, the sequence (sequence.hip).  Allocations of their own, as above.
+		if (rc == ACM_OK && !a->sequences.empty()) {
+			std::vector<int32_t> ent(4 * a->patterns.size()), slot;
+			std::vector<int32_t> slot_of(a->patterns.size(), -1);
+			for (size_t i = 0; i < a->patterns.size(); i++) {
+				ent[4 * i] = -1;
+				ent[4 * i + 1] = ent[4 * i + 2] = 0;
+				ent[4 * i + 3] = (int32_t)a->patterns[i].bytes.size();
+			}
+			uint32_t levels = 0;
+			for (const auto &s : a->sequences)
+				levels = std::max<uint32_t>(levels, (uint32_t)s.parts.size());
+			for (uint32_t j = 0; j < levels; j++) {
+				d->seq_level_base[j] = (uint32_t)(slot.size() / 2);
+				for (size_t q = 0; q < a->sequences.size(); q++) {
+					const auto &s = a->sequences[q];
+					if (j >= s.parts.size())
+						continue;
+					const int32_t p = s.parts[j], me = (int32_t)(slot.size() / 2);
+					slot_of[p] = me;
+					ent[4 * (size_t)p] = me;
+					if (j > 0) {
+						ent[4 * (size_t)p + 1] = s.gap_lo[j - 1];
+						ent[4 * (size_t)p + 2] = s.gap_hi[j - 1];
+					}
+					slot.push_back(j > 0 ? slot_of[s.parts[j - 1]] : -1);
+					slot.push_back(j + 1 == s.parts.size() ? (int32_t)q : -1);
+				}
+			}
+			d->seq_levels = levels;
+			d->seq_slots = (uint32_t)(slot.size() / 2);
+			for (uint32_t j = levels; j <= ACM_SEQ_MAX_PARTS; j++)
+				d->seq_level_base[j] = d->seq_slots;
+			rc = upload(&d->d_seq_ent, ent.data(), ent.size(), &d->device_bytes);
+			if (rc == ACM_OK) rc = upload(&d->d_seq_slot, slot.data(), slot.size(), &d->device_bytes);
+		}
 	} catch (const std::bad_alloc &) {
 		rc = acm::fail(ACM_ERR_NOMEM, "acm_dfa_upload: out of host memory");
 	}
@@ -331,6 +369,8 @@ extern "C" void acm_dfa_release(acm_dfa *d)
 		hipFree(d->d_case_ent);
 		hipFree(d->d_case_pool);
 		hipFree(d->d_pos_ent);
+		hipFree(d->d_seq_ent);
+		hipFree(d->d_seq_slot);
 		free_small(d, d->d_depth);
 		free_small(d, d->d_class);
 		free_small(d, d->d_sv_bloom);

@@ -148,6 +148,66 @@ int acm_automaton_pattern_position(const acm_automaton *, int index, int32_t *lo
 int acm_automaton_positioned(const acm_automaton *);
 int acm_automaton_load_position_file(acm_automaton *, const char *path);
 
+/* Ordered multi-part signatures: the relation BETWEEN patterns.  A SEQUENCE is k parts, 1 <= k <=
+ * ACM_SEQ_MAX_PARTS: pattern indices p_0 .. p_{k-1}, k - 1 gaps (lo_j, hi_j), j = 1 .. k-1, and a user id
+ * iid.  A gap has lo >= 0 and hi >= 0, or hi == ACM_GAP_UNBOUNDED; lo > hi is legal and never matches (as
+ * a position window).
+ * An occurrence of pattern p (length L >= 1) that ends at offset e starts at a = e - L + 1 and lies in the
+ * text [T0, Tend) its offset belongs to (found as the position pass finds it; Tend is not needed).  A
+ * sequence MATCHES ENDING AT o iff there are occurrences of its parts with ends e_0 < ... < e_{k-1} = o
+ * such that
+ *   a_0 >= T0, and
+ *   for j >= 1:  lo_j <= a_j - e_{j-1} - 1 <= hi_j  and  e_{j-1} >= T0 of part j's text.
+ * The gap is the number of bytes strictly between two parts, so parts never overlap, and no chain crosses
+ * a text start.  Level by level: a level-0 record is ALIVE iff a >= T0; a level-j record is alive iff some
+ * alive level-(j-1) record of the same sequence ends in [max(a - 1 - hi, T0), a - 1 - lo] (no lower bound
+ * but T0 when hi is unbounded).  All arithmetic is in int64.
+ * How the usual source forms map to gaps:
+ *   ClamAV {n-m}  (n, m)      {n}  (n, n)      {-m}  (0, m)      {n-}  (n, unbounded)      *  (0, unbounded)
+ *   ClamAV ??     (1, 1); adjacent gap tokens add, a sum with an unbounded term is unbounded
+ *   Snort distance d          lo = d  (d >= 0)
+ *   Snort within w            hi = w - L_j
+ * A pattern index may be a part of at most one sequence, at one level; to use the same bytes twice, add
+ * the pattern twice (the automaton keeps duplicates and the all-patterns forms report every list entry).
+ * A 1-part sequence has no gaps: plain patterns and multi-part signatures come out under one id space.
+ * Sequences do not enter acm_automaton_compile: tables, digests, self-tests and acm_dfa_device_bytes of an
+ * automaton without sequences are what they were, and no scan looks at a sequence.  They may be added
+ * before or after compile; acm_dfa_upload takes a copy, so one added later does not reach that acm_dfa.
+ * acm_sequence_matches_async joins the records of a scan on the device.
+ *   acm_automaton_add_sequence       returns the sequence index.  gap_lo / gap_hi have nparts - 1 cells
+ *                                    (ignored when nparts == 1).  ACM_ERR_ARG: a bad index, a part already
+ *                                    used (also twice in this call), a part of length 0, a negative bound,
+ *                                    nparts < 1; ACM_ERR_LIMIT above ACM_SEQ_MAX_PARTS.  On an error
+ *                                    nothing is applied.
+ *   acm_automaton_sequence           sequence i: iid, nparts and borrowed pointers (any may be NULL)
+ *   acm_automaton_pattern_sequence   1 and (sequence, level) if the pattern is a part, else 0
+ *   acm_automaton_add_signature      parses a ClamAV-style hex body -- hex byte pairs, ??, *, {n}, {n-m},
+ *                                    {-m}, {n-} -- adds each fixed part with acm_automaton_add_ex(..., iid,
+ *                                    flags) and registers the sequence; returns the sequence index.  The
+ *                                    body begins and ends with a fixed part.  Anything else (a nibble
+ *                                    wildcard a?, alternatives (..|..), !, an odd hex digit, an empty part,
+ *                                    a gap sum of INT32_MAX or more) is ACM_ERR_PARSE and acm_last_error
+ *                                    names the column (from 1).  The body is parsed completely before
+ *                                    anything is added.  Only before compile: it adds patterns.
+ *   acm_automaton_load_signature_file  one signature per line, with an optional leading "<decimal iid>:",
+ *                                    otherwise the iid is the sequence index; lines whose first non-blank
+ *                                    byte is '#' and blank lines are skipped.  A bad line is ACM_ERR_PARSE
+ *                                    naming the line, and nothing of the file is applied.  Returns the
+ *                                    number of sequences added.  A pure hex line is a 1-part sequence.
+ * Not provided: sequences whose parts lie in different calls (a stream cut inside a signature is not
+ * joined: scan whole texts), negative distances or overlapping parts, nibble wildcards and alternatives,
+ * where a match begins.  The reference-named layer is unchanged. */
+#define ACM_SEQ_MAX_PARTS 32
+#define ACM_GAP_UNBOUNDED INT32_MAX
+int acm_automaton_add_sequence(acm_automaton *, const int32_t *parts, const int32_t *gap_lo,
+    const int32_t *gap_hi, int nparts, int iid);
+int acm_automaton_num_sequences(const acm_automaton *);
+int acm_automaton_sequence(const acm_automaton *, int index, int *iid, int *nparts,
+    const int32_t **parts, const int32_t **gap_lo, const int32_t **gap_hi);
+int acm_automaton_pattern_sequence(const acm_automaton *, int pattern, int *sequence, int *level);
+int acm_automaton_add_signature(acm_automaton *, const char *body, int iid, unsigned flags);
+int acm_automaton_load_signature_file(acm_automaton *, const char *path, unsigned flags);
+
 /* ASCII case-insensitive matching for every pattern of the automaton.  With
  * it on, fold(b) = b - 0x20 for 'a' <= b <= 'z' and b otherwise (toupper in
  * the C locale; bytes >= 0x80 are never folded), and a scan of text T gives
@@ -524,6 +584,34 @@ int acm_position_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
     size_t segments, long lead_begin, long text_end, long open_end, int all_patterns,
     int32_t *d_pat_out, int32_t *d_off_out, size_t out_capacity, int32_t *d_info,
     void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Sequences (acm_automaton_add_sequence) joined on the device: the records of the parts in, one record
+ * per sequence match out.  No text is read.
+ * Input: planes in the scan's cell layout whose cells are pattern indices, one record per occurrence: the
+ * all-patterns output of acm_expand_matches_async or of the word, case or position pass (a HEAD scan's
+ * planes also work: its one pattern per offset).  Offsets non-decreasing.  At most min([0], max_records)
+ * records are looked at.  A cell that is no pattern index, or a pattern that is no part, takes part in
+ * nothing.  Texts: d_seg_start[segments], lead_begin and text_end as in acm_position_matches_async.
+ * Output, the scan's cell layout and overflow contract ([0] = full count, records, trailer -- the input
+ * trailer unchanged -- at min(count + 1, out_capacity - 1)): one record per alive record of a sequence's
+ * last part, in input order: d_seq_out the sequence index, d_off_out the offset o the match ends at.
+ *   d_info   int32[4], required, written whole: [0] input records that are a part of some sequence, [1]
+ *            alive records over all levels, [2..3] 0
+ * For an uploaded set without sequences the call is legal and writes count 0.  Results are the same on
+ * every run (integers; no order decided by atomics).  No read leaves the inputs, the starts and the
+ * library's tables and no write leaves the outputs and the workspace, whatever the planes hold.  The
+ * outputs must not overlap the inputs.  Stream-ordered, no host sync, no allocation, no host read of device
+ * data; argument errors (a NULL plane, output or d_info, out_capacity < 2, segments without starts, a
+ * short workspace) return ACM_ERR_ARG before anything is enqueued.  The records are keyed by part, ordered
+ * by a stable radix sort over max_records cells (cost per max_records, not per record: size it to the
+ * planes), and the levels are joined one after the other (csrc/sequence.hip): the launch count depends on
+ * the uploaded set (its parts and levels) alone, never on the data.  The workspace query is monotone in
+ * max_records and a multiple of 256. */
+size_t acm_sequence_workspace_bytes(const acm_dfa *, size_t max_records);
+int acm_sequence_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
+    const int32_t *d_off_plane, size_t max_records, const int32_t *d_seg_start, size_t segments,
+    long lead_begin, long text_end, int32_t *d_seq_out, int32_t *d_off_out, size_t out_capacity,
+    int32_t *d_info, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* Match tallies: counts of the records of any pass, reduced on the device, so a caller who only counts
  * (a classifier, grep -c, "which signatures hit which file") copies back the counts, not the records.
