@@ -40,6 +40,8 @@ POS_FROM_END = 1
 POS_UNBOUNDED = 0x7FFFFFFF
 SEQ_MAX_PARTS = 32
 GAP_UNBOUNDED = 0x7FFFFFFF
+WILDCARD_MAX_POSITIONS = 4096
+SIG_EXTENDED = 1
 
 
 class AcmError(RuntimeError):
@@ -76,6 +78,12 @@ NATIVE_API = {
     "acm_automaton_pattern_sequence": (C.c_int, [_vp, C.c_int, _i32p, _i32p]),
     "acm_automaton_add_signature": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_uint]),
     "acm_automaton_load_signature_file": (C.c_int, [_vp, C.c_char_p, C.c_uint]),
+    "acm_automaton_add_wildcard": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, C.c_uint]),
+    "acm_automaton_pattern_wildcard": (C.c_int, [_vp, C.c_int, _i32p, _i32p, C.POINTER(_vp), C.POINTER(_vp)]),
+    "acm_automaton_wildcards": (C.c_int, [_vp]),
+    "acm_automaton_wildcard_reach": (C.c_int, [_vp, _i32p, _i32p]),
+    "acm_automaton_add_signature_ex": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_uint, C.c_uint]),
+    "acm_automaton_load_signature_file_ex": (C.c_int, [_vp, C.c_char_p, C.c_uint, C.c_uint]),
     "acm_automaton_set_nocase": (C.c_int, [_vp, C.c_int]),
     "acm_automaton_nocase": (C.c_int, [_vp]),
     "acm_automaton_compile": (C.c_int, [_vp]),
@@ -122,6 +130,10 @@ NATIVE_API = {
     "acm_position_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "acm_position_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.c_long, C.c_long,
                                              C.c_long, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "acm_wildcard_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "acm_wildcard_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_long, C.c_long, _vp, C.c_size_t,
+                                             _vp, C.c_size_t, C.c_long, C.c_long, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp,
+                                             C.c_size_t, _vp]),
     "acm_sequence_workspace_bytes": (C.c_size_t, [_vp, C.c_size_t]),
     "acm_sequence_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_long, C.c_long, _vp, _vp,
                                              C.c_size_t, _vp, _vp, C.c_size_t, _vp]),

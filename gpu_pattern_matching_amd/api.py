@@ -169,22 +169,89 @@ class Automaton:
             check(r, "acm_automaton_add_sequence")
         return r
 
-    def add_signature(self, body, iid=0, nocase=False):
+    def add_signature(self, body, iid=0, nocase=False, extended=False):
         """A ClamAV-style hex body (acm_automaton_add_signature): hex byte pairs, ??, *, {n}, {n-m}, {-m}, {n-}.
-        Adds its fixed parts as patterns and registers the sequence; only before compile().  Returns the
-        sequence index."""
+        Adds its fixed parts as patterns and registers the sequence; only before compile().  extended
+        (acm_automaton_add_signature_ex, ACM_SIG_EXTENDED): also a?, ?a, (aa|bb), !(aa|bb), ?? a position; the
+        parts are wildcard patterns (add_wildcard).  Returns the sequence index."""
         body = body.encode() if isinstance(body, str) else bytes(body)
-        r = self.lib.acm_automaton_add_signature(self.h, body, iid, _lib.PATTERN_NOCASE if nocase else 0)
+        fl = _lib.PATTERN_NOCASE if nocase else 0
+        if extended:
+            r = self.lib.acm_automaton_add_signature_ex(self.h, body, iid, fl, _lib.SIG_EXTENDED)
+        else:
+            r = self.lib.acm_automaton_add_signature(self.h, body, iid, fl)
         if r < 0:
             check(r, "acm_automaton_add_signature")
         return r
 
-    def load_signature_file(self, path, nocase=False):
-        """signatures from a file, one per line with an optional leading "<iid>:"; returns how many"""
-        n = self.lib.acm_automaton_load_signature_file(self.h, str(path).encode(), _lib.PATTERN_NOCASE if nocase else 0)
+    def load_signature_file(self, path, nocase=False, extended=False):
+        """signatures from a file, one per line with an optional leading "<iid>:"; returns how many.  extended:
+        the extended body syntax (acm_automaton_load_signature_file_ex)"""
+        fl = _lib.PATTERN_NOCASE if nocase else 0
+        if extended:
+            n = self.lib.acm_automaton_load_signature_file_ex(self.h, str(path).encode(), fl, _lib.SIG_EXTENDED)
+        else:
+            n = self.lib.acm_automaton_load_signature_file(self.h, str(path).encode(), fl)
         if n < 0:
             check(n, "acm_automaton_load_signature_file")
         return n
+
+    @staticmethod
+    def byte_set(position):
+        """the 32 bytes of set of one position: an int, bytes or an iterable of ints"""
+        if isinstance(position, int):
+            position = (position,)
+        out = bytearray(32)
+        for b in position:
+            b = int(b)
+            if not 0 <= b <= 255:
+                raise ValueError("byte value %d" % b)
+            out[b >> 3] |= 1 << (b & 7)
+        return bytes(out)
+
+    def add_wildcard(self, positions, iid=0, nocase=False):
+        """A wildcard pattern (acm_automaton_add_wildcard): every position a set of byte values, given as an int,
+        bytes or an iterable of ints.  The longest run of one-byte positions, its anchor, enters the automaton
+        (nocase applies to it alone); the positions around it are checked by Matcher.scan_wildcards.  Only before
+        compile().  Returns the pattern index."""
+        sets = b"".join(self.byte_set(p) for p in positions)
+        r = self.lib.acm_automaton_add_wildcard(self.h, sets, len(sets) // 32, iid, _lib.PATTERN_NOCASE if nocase else 0)
+        if r < 0:
+            check(r, "acm_automaton_add_wildcard")
+        return r
+
+    def wildcard(self, i):
+        """(pre, post) of pattern i (acm_automaton_pattern_wildcard): the context positions in front of and behind
+        its anchor, each a frozenset of byte values; two empty lists for a plain pattern"""
+        pre, post, ps, qs = C.c_int32(), C.c_int32(), C.c_void_p(), C.c_void_p()
+        r = self.lib.acm_automaton_pattern_wildcard(self.h, i, C.byref(pre), C.byref(post), C.byref(ps), C.byref(qs))
+        if r < 0:
+            check(r, "acm_automaton_pattern_wildcard")
+
+        def sets(ptr, n):
+            raw = C.string_at(ptr.value, 32 * n) if n else b""
+            return [frozenset(b for b in range(256) if raw[32 * k + (b >> 3)] >> (b & 7) & 1) for k in range(n)]
+        return sets(ps, pre.value), sets(qs, post.value)
+
+    def wildcard_lengths(self, i):
+        """(pre, post) of pattern i as counts"""
+        pre, post = C.c_int32(), C.c_int32()
+        r = self.lib.acm_automaton_pattern_wildcard(self.h, i, C.byref(pre), C.byref(post), None, None)
+        if r < 0:
+            check(r, "acm_automaton_pattern_wildcard")
+        return pre.value, post.value
+
+    @property
+    def has_wildcards(self):
+        """some pattern has a context (acm_automaton_wildcards)"""
+        return bool(self.lib.acm_automaton_wildcards(self.h))
+
+    @property
+    def wildcard_reach(self):
+        """(back, ahead) over the patterns with a context: the largest pre + anchor length, the largest post"""
+        b, f = C.c_int32(), C.c_int32()
+        check(self.lib.acm_automaton_wildcard_reach(self.h, C.byref(b), C.byref(f)), "acm_automaton_wildcard_reach")
+        return b.value, f.value
 
     @property
     def num_sequences(self):
@@ -297,6 +364,10 @@ class Matcher:
         self.dfa = h.value
         self.num_patterns = automaton.num_patterns
         self.mixed, self.positioned = automaton.mixed_case, automaton.positioned     # as uploaded (scan_sequences)
+        self.wild = automaton.has_wildcards
+        # post context of every sequence's last part: a match ends that far behind the offset the sequence pass reports
+        self.seq_post = np.array([automaton.wildcard_lengths(automaton.sequence(q)[0][-1])[1]
+                                  for q in range(automaton.num_sequences)] if self.wild else [], dtype=np.int64)
         self.max_text = 0
         self.ws = self.pat_plane = self.off_plane = None
         self.reserve(max_text, plane_capacity)
@@ -823,6 +894,109 @@ class Matcher:
             for b in bufs:
                 b.free()
 
+    def wildcard_async(self, pat_plane, off_plane, max_records, d_text, text_origin, text_end, pat_out, off_out,
+                       out_capacity, info, report=0, before=None, before_len=0, seg_start=None, segments=0, lead_begin=0,
+                       open_end=-1, all_patterns=True, workspace=None, stream=None):
+        """Enqueue the wildcard pass (acm_wildcard_matches_async) over caller-owned device planes: states
+        (report=REPORT_STATE) or pattern indices (REPORT_HEAD, all_patterns only), an entry kept where the bytes
+        around its anchor lie in its pattern's context sets (Automaton.add_wildcard).  info: device int32[4].
+        workspace: (ptr, nbytes), or None for a temporary one that lives until the stream has passed it (the
+        call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        tmp = None
+        if workspace is None:
+            nb = self.lib.acm_wildcard_workspace_bytes(max_records)
+            tmp = DeviceArray(max(nb, 16))
+            workspace = (tmp.ptr, nb)
+        try:
+            check(self.lib.acm_wildcard_matches_async(
+                self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, report, _ptr(d_text), text_origin, text_end,
+                _ptr(before), before_len, _ptr(seg_start), segments, lead_begin, open_end, 1 if all_patterns else 0,
+                _ptr(pat_out), _ptr(off_out), out_capacity, _ptr(info), _ptr(workspace[0]), workspace[1], st),
+                "acm_wildcard_matches_async")
+        finally:
+            if tmp is not None:
+                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
+                tmp.free()
+
+    def scan_wildcards(self, text=None, texts=None, all_patterns=False, before=b"", init_state=0, out_capacity=None):
+        """Matches of an automaton with wildcard patterns (Automaton.add_wildcard): a REPORT_STATE scan, the
+        segment pass when texts is given (each text matched alone), then the wildcard pass
+        (acm_wildcard_matches_async).  A mixed automaton: the case pass in its all form runs in between and the
+        wildcard pass takes its pattern-form output (then, without all_patterns, the position pass picks the
+        first entry of every offset).  text: host bytes; or None with texts: a list of bytes-like objects or a
+        (uint8 array, int32 starts) pair.  before: the bytes in front of text, part of the same text.  The
+        text ends with the bytes given.  Returns (offsets, patterns, last_state, info): the offsets are the
+        ANCHORS' ends (a match ends Automaton.wildcard_lengths(p)[1] bytes behind), info[0] the undecided
+        entries."""
+        if texts is not None:
+            t, starts = self.pack_segments(texts)
+        else:
+            t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
+                else np.ascontiguousarray(text, dtype=np.uint8)
+            starts = np.zeros(0, dtype=np.int32)
+        bf = np.frombuffer(bytes(before), dtype=np.uint8)
+        self.reserve(max(t.size, 1))
+        d = DeviceArray.from_numpy(t, stream=self.stream)
+        d_bf = DeviceArray.from_numpy(bf, stream=self.stream) if bf.size else None
+        nseg = int(starts.size)
+        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
+        max_records = self.plane_capacity - 2
+        cap = self.plane_capacity
+        ocap = out_capacity if out_capacity is not None else (8 * cap if all_patterns or self.mixed else cap)
+        info = DeviceArray(16)
+        bufs = [info] + [b for b in (d, d_bf, d_st) if b is not None]
+
+        def count_of(plane, room):
+            n = int(plane.to_numpy(np.int32, 1, stream=self.stream)[0])
+            if n > room - 2:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_wildcards", "%d records but planes hold %d" % (n, room - 2))
+            return n
+        where = dict(before=d_bf, before_len=int(bf.size), seg_start=d_st, segments=nseg, lead_begin=-int(bf.size),
+                     open_end=int(t.size))
+        try:
+            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
+            sp, so, report = self.pat_plane, self.off_plane, _lib.REPORT_STATE
+            if nseg:
+                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
+                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
+                bufs += sb
+                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
+                                   report=_lib.REPORT_STATE, workspace=(sb[0].ptr, seg_ws))
+                sp, so = sb[1], sb[2]
+            if self.mixed:
+                icap = 8 * cap
+                nb = self.lib.acm_case_workspace_bytes(max_records)
+                tb = [DeviceArray(max(nb, 16)), DeviceArray(icap * 4), DeviceArray(icap * 4)]
+                bufs += tb
+                self.case_async(sp, so, max_records, d, 0, t.size, tb[1], tb[2], icap, before=d_bf,
+                                before_len=int(bf.size), all_patterns=True, workspace=(tb[0].ptr, nb))
+                max_records = count_of(tb[1], icap)
+                sp, so, report = tb[1], tb[2], _lib.REPORT_HEAD
+            nb = self.lib.acm_wildcard_workspace_bytes(max_records)
+            wb = [DeviceArray(max(nb, 16)), DeviceArray(ocap * 4), DeviceArray(ocap * 4)]
+            bufs += wb
+            self.wildcard_async(sp, so, max_records, d, 0, t.size, wb[1], wb[2], ocap, info, report=report,
+                                all_patterns=all_patterns or report == _lib.REPORT_HEAD, workspace=(wb[0].ptr, nb), **where)
+            m = count_of(wb[1], ocap)
+            pat, off = wb[1], wb[2]
+            und = info.to_numpy(np.int32, 4, stream=self.stream)
+            if report == _lib.REPORT_HEAD and not all_patterns:
+                nb = self.lib.acm_position_workspace_bytes(m)
+                pb = [DeviceArray(max(nb, 16)), DeviceArray((m + 2) * 4), DeviceArray((m + 2) * 4), DeviceArray(16)]
+                bufs += pb
+                self.position_async(pat, off, m, pb[1], pb[2], m + 2, pb[3], report=_lib.REPORT_HEAD, seg_start=d_st,
+                                    segments=nseg, lead_begin=-int(bf.size), text_end=int(t.size), open_end=int(t.size),
+                                    all_patterns=False, workspace=(pb[0].ptr, nb))
+                m = count_of(pb[1], m + 2)
+                pat, off = pb[1], pb[2]
+            p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
+            o = off.to_numpy(np.int32, m + 2, stream=self.stream)
+            return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1]), und
+        finally:
+            for b in bufs:
+                b.free()
+
     def sequence_async(self, pat_plane, off_plane, max_records, seq_out, off_out, out_capacity, info, seg_start=None,
                        segments=0, lead_begin=0, text_end=0, workspace=None, stream=None):
         """Enqueue the sequence pass (acm_sequence_matches_async) over caller-owned device planes of pattern
@@ -850,7 +1024,9 @@ class Matcher:
     def scan_sequences(self, text=None, texts=None, lead_begin=0, init_state=0, before=b"", out_capacity=None):
         """Matches of the automaton's sequences (Automaton.add_sequence, add_signature): a REPORT_STATE scan,
         the segment pass when texts is given (each text matched alone), every pattern of every record (the
-        case pass when the automaton is mixed, else acm_expand_matches_async), the position pass in its all
+        case pass when the automaton is mixed, else acm_expand_matches_async), the wildcard pass when the
+        automaton has wildcard contexts (the offsets returned are then the matches' ends: the last part's post
+        context is added on the host), the position pass in its all
         form when the automaton is positioned (a window on the first part anchors the signature), then the
         sequence pass (acm_sequence_matches_async).  text: host bytes; or None with texts: a list of bytes-like
         objects or a (uint8 array, int32 starts) pair.  lead_begin: where the text in front of the first
@@ -904,6 +1080,16 @@ class Matcher:
             sp, so = tb[1], tb[2]
             info = DeviceArray(16)
             bufs.append(info)
+            if self.wild:
+                nb = self.lib.acm_wildcard_workspace_bytes(n)
+                wb = [DeviceArray(max(nb, 16)), DeviceArray((n + 2) * 4), DeviceArray((n + 2) * 4)]
+                bufs += wb
+                self.wildcard_async(sp, so, n, d, 0, t.size, wb[1], wb[2], n + 2, info, report=_lib.REPORT_HEAD,
+                                    before=d_bf, before_len=int(bf.size), seg_start=d_st, segments=nseg,
+                                    lead_begin=int(lead_begin), open_end=int(t.size), all_patterns=True,
+                                    workspace=(wb[0].ptr, nb))
+                n = count_of(wb[1], n + 2)
+                sp, so = wb[1], wb[2]
             if self.positioned:
                 nb = self.lib.acm_position_workspace_bytes(n)
                 pb = [DeviceArray(max(nb, 16)), DeviceArray((n + 2) * 4), DeviceArray((n + 2) * 4)]
@@ -922,7 +1108,10 @@ class Matcher:
             m = count_of(qb[1], ocap)
             q = qb[1].to_numpy(np.int32, m + 2, stream=self.stream)
             o = qb[2].to_numpy(np.int32, m + 2, stream=self.stream)
-            return o[1:1 + m].astype(np.uint32), q[1:1 + m].copy(), int(q[m + 1]), info.to_numpy(np.int32, 4, stream=self.stream)
+            ends = o[1:1 + m].astype(np.uint32)
+            if self.wild:   # the pass reports the end of the last part's anchor: the match ends post bytes behind it
+                ends = (ends.astype(np.int64) + self.seq_post[q[1:1 + m]]).astype(np.uint32)
+            return ends, q[1:1 + m].copy(), int(q[m + 1]), info.to_numpy(np.int32, 4, stream=self.stream)
         finally:
             for b in bufs:
                 b.free()

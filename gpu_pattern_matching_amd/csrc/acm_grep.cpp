@@ -96,6 +96,14 @@ double now_us()
 	       "                 buffer): a buffer with more pattern records than that is an error.  Composes with\n"
 	       "                 -i, -I, -S and -P (the indices of the parts follow those of -p and -I)\n"
 	       "                 (extension; not with -c, -n, -W or -A)\n"
+	       "  -E             the signatures of -Q in the extended syntax: beside hex byte pairs a position may be a\n"
+	       "                 nibble wildcard (a?, ?a), any byte (??, a position here, not a gap of one), one of some bytes\n"
+	       "                 ((aa|bb|cc)) or none of them (!(aa|bb)); only * and {..} separate parts, and every part\n"
+	       "                 needs an exact byte.  The longest run of exact bytes of a part is matched by the automaton,\n"
+	       "                 the positions around it are checked on the device where it matched.  A candidate whose\n"
+	       "                 positions reach over a buffer border is not decided: such candidates are counted and\n"
+	       "                 reported on stderr at exit.  Composes with -i, -I, -S and -P (a window counts from a part's\n"
+	       "                 first position) (extension; needs -Q, not with -W)\n"
 	       "  -S             every input unit is its own text: a file, or with -t a line; no match\n"
 	       "                 spans two of them (extension; data appended under -F continues its file\n"
 	       "                 when the worker's previous chunk came from the same file)\n"
@@ -155,6 +163,8 @@ struct Config {
 	int cased = 0;           // -I without -i: the records go through the case pass
 	int pos = 0;             // -P: the records go through the position pass
 	int seq = 0;             // -Q: every pattern of the records goes through the sequence pass; its records are reported
+	int ext = 0;             // -E: the signatures of -Q are read in the extended syntax
+	int wild = 0;            // -E and some part has a context: the parts' records go through the wildcard pass
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
 	long global_ws = -1, local_ws = -1, chunk = -1;
@@ -168,6 +178,7 @@ struct Shared {
 	std::vector<std::string> pat_bytes;   // for the -v line
 	std::vector<int> pat_iid;
 	std::vector<int> seq_iid;             // -Q: the id of every sequence, for the -v line
+	std::vector<int> seq_post;            // -E: the post context of every sequence's last part: a match ends that far behind its record
 	int max_pattern_len = 0;
 	pthread_mutex_t print_lock = PTHREAD_MUTEX_INITIALIZER;
 	pthread_barrier_t ready;   // workers have their buffers; the clock starts (the reference
@@ -204,6 +215,10 @@ struct Buffer {   // one of the two staging buffers of a worker
 	// -Q only: the sequence pass's planes, workspace and info; seq_max: the pattern-form records it takes
 	void *d_seq_pat = nullptr, *d_seq_off = nullptr, *d_seq_ws = nullptr, *d_seq_info = nullptr;
 	size_t seq_ws_bytes = 0, seq_max = 0;
+	// -E only: the wildcard pass's planes, workspace and info (pinned twin: [0] = undecided entries, [4] = records written)
+	void *d_wild_pat = nullptr, *d_wild_off = nullptr, *d_wild_ws = nullptr, *d_wild_info = nullptr;
+	int32_t *h_wild_info = nullptr;
+	size_t wild_ws_bytes = 0;
 	long lead_begin = 0;         // -P, -Q: where the text that goes on into this buffer began, in its stream's coordinates (<= 0)
 	bool end_known = false;      // -P: the stream's last text ends with the stream (its file, or with -t its line, is finished)
 	bool last_of_input = false;  // -P: nothing of the worker's input follows this buffer
@@ -248,6 +263,7 @@ struct Worker {
 	size_t text_bytes = 0;    // -P: bytes of the text in progress that the buffers prepared so far hold
 	bool file_closed = false; // -P: the file of the last chunk filled has been read to its end
 	uint64_t undecided = 0;   // -P: end-anchored entries dropped because their text went on in the next buffer
+	uint64_t wild_undecided = 0;   // -E: candidates whose positions reach over a buffer border
 	void *d_tail[2] = { nullptr, nullptr };   // -W, -I: the last max_pattern_len bytes of the stream so far, ping-pong
 	int tail_cur = 0;
 	size_t tail_len = 0;
@@ -514,7 +530,7 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 	sb.report = states ? ACM_REPORT_STATE : ACM_REPORT_HEAD;
 	if (c.segmented && !b.seg_starts.empty())
 		CK(acm_rt_memcpy_h2d(b.d_seg_start, b.seg_starts.data(), b.seg_starts.size() * 4, s));
-	if (c.pos && b.end_known) {   // a start at the stream's end, for the position pass alone: the last text is closed
+	if ((c.pos || c.wild) && c.segmented && b.end_known) {   // a start at the stream's end, for the position and wildcard passes alone: the last text is closed
 		b.end_start = (int32_t)b.stream_len;
 		CK(acm_rt_memcpy_h2d((int32_t *)b.d_seg_start + b.seg_starts.size(), &b.end_start, 4, s));
 	}
@@ -584,11 +600,30 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		cap = b.all_cap;
 		CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
 	}
+	bool wild_ran = false;
+	if (c.wild) {
+		// the positions around every anchor, each in its own text (as the position pass below finds it).  Behind
+		// the case pass or the expansion the planes hold patterns, else the segment pass's states.  No bytes of
+		// the buffer in front are given: a candidate that reaches there is undecided and counted.
+		const bool heads = c.cased || !c.pos;
+		const size_t nseg = c.segmented ? b.seg_starts.size() + (b.end_known ? 1 : 0) : 0;
+		CK(acm_wildcard_matches_async(w.dfa, pat, off, cap - 2, heads ? ACM_REPORT_HEAD : ACM_REPORT_STATE, b.text, 0,
+		    (long)b.stream_len, nullptr, 0, nseg ? (const int32_t *)b.d_seg_start : nullptr, nseg,
+		    c.segmented ? b.lead_begin : -(1L << 40), b.last_of_input ? (long)b.stream_len : -1L, 1, (int32_t *)b.d_wild_pat,
+		    (int32_t *)b.d_wild_off, b.all_cap, (int32_t *)b.d_wild_info, b.d_wild_ws, b.wild_ws_bytes, s));
+		pat = (int32_t *)b.d_wild_pat;
+		off = (int32_t *)b.d_wild_off;
+		cap = b.all_cap;
+		CK(acm_rt_memcpy_d2h(b.h_wild_info, b.d_wild_info, 16, s));
+		if (!heads)   // (no pass in front has counted every pattern)
+			CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
+		wild_ran = true;
+	}
 	if (c.pos) {
 		// the windows of the patterns, each in its own text: the files' (-t: lines') starts of this stream, the
 		// text that goes on from the buffer in front, and the end of the last one where it is known.  Behind
 		// the word or case pass the planes hold patterns (every kept one), else the segment pass's states.
-		const bool heads = c.words || c.cased;
+		const bool heads = c.words || c.cased || wild_ran;
 		CK(acm_position_matches_async(w.dfa, pat, off, cap - 2, heads ? ACM_REPORT_HEAD : ACM_REPORT_STATE,
 		    (const int32_t *)b.d_seg_start, b.seg_starts.size() + (b.end_known ? 1 : 0), b.lead_begin, (long)b.stream_len,
 		    b.last_of_input ? (long)b.stream_len : -1L, c.all_patterns || c.seq, (int32_t *)b.d_pos_pat, (int32_t *)b.d_pos_off,
@@ -680,6 +715,8 @@ void collect(Worker &w, Buffer &b)
 	}
 	if (c.pos)
 		w.undecided += (uint64_t)b.h_pos_info[0];
+	if (c.wild)
+		w.wild_undecided += (uint64_t)b.h_wild_info[0];
 	if (c.count && !w.sh->pat_iid.empty()) {
 		if (b.cnt_starts.empty()) {   // the whole buffer goes on with the file in front of it
 			if (b.cnt_prev_file >= 0)
@@ -704,7 +741,9 @@ void collect(Worker &w, Buffer &b)
 		w.matches += (size_t)n;
 		for (int j = 0; j < n && j < R - 1; j++) {
 			const int p_idx = b.h_results[(size_t)(j + 1) * chunks + i];
-			const int off = b.h_results2[(size_t)(j + 1) * chunks + i] + 1;  // end + 1 (databuf.c:771)
+			int off = b.h_results2[(size_t)(j + 1) * chunks + i] + 1;  // end + 1 (databuf.c:771)
+			if (c.wild)   // the record is the end of the last part's anchor: the match ends its post context behind
+				off += w.sh->seq_post[p_idx];
 			w.reported++;
 			if (!c.verbose)
 				continue;
@@ -770,6 +809,15 @@ void *worker_main(void *arg)
 			CK(acm_rt_malloc(&b.d_seq_off, (b.seq_max + 2) * 4));
 			CK(acm_rt_malloc(&b.d_seq_ws, b.seq_ws_bytes));
 			CK(acm_rt_malloc(&b.d_seq_info, 16));
+			if (c.wild) {
+				b.wild_ws_bytes = acm_wildcard_workspace_bytes(b.all_cap);
+				CK(acm_rt_malloc(&b.d_wild_pat, b.all_cap * 4));
+				CK(acm_rt_malloc(&b.d_wild_off, b.all_cap * 4));
+				CK(acm_rt_malloc(&b.d_wild_ws, b.wild_ws_bytes));
+				CK(acm_rt_malloc(&b.d_wild_info, 16));
+				CK(acm_rt_host_alloc((void **)&b.h_wild_info, 64));
+				b.h_wild_info[0] = 0;
+			}
 		}
 	if (c.words || c.cased)
 		for (void *&t : w.d_tail)
@@ -876,7 +924,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:E")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -911,6 +959,7 @@ int main(int argc, char **argv)
 		case 'I': c.loose_path = optarg; break;
 		case 'P': c.pos_path = optarg; break;
 		case 'Q': c.seq_path = optarg; break;
+		case 'E': c.ext = 1; break;
 		default: usage();
 		}
 	}
@@ -958,6 +1007,14 @@ int main(int argc, char **argv)
 	}
 	if (c.seq && (c.count || c.lineno || c.words || c.all_patterns)) {   // the records are sequence matches, not patterns
 		printf("ERROR: -Q cannot be combined with -c, -n, -W or -A: the records of -Q are signature matches\n");
+		err++;
+	}
+	if (c.ext && !c.seq) {
+		printf("ERROR: -E needs -Q: it is the syntax of the signature file\n");
+		err++;
+	}
+	if (c.ext && c.words) {
+		printf("ERROR: -E cannot be combined with -W: the word pass looks at the bytes next to a part's exact run\n");
 		err++;
 	}
 	if (c.lineno && c.text_mode) {
@@ -1028,14 +1085,19 @@ int main(int argc, char **argv)
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}
-	if (c.seq && acm_automaton_load_signature_file(aut, c.seq_path.c_str(), 0) < 0) {
+	if (c.seq && acm_automaton_load_signature_file_ex(aut, c.seq_path.c_str(), 0, c.ext ? ACM_SIG_EXTENDED : 0) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}
+	c.wild = c.ext && acm_automaton_wildcards(aut);
 	for (int i = 0; i < acm_automaton_num_sequences(aut); i++) {
-		int iid = 0;
-		acm_automaton_sequence(aut, i, &iid, nullptr, nullptr, nullptr, nullptr);
+		int iid = 0, nparts = 0, post = 0;
+		const int32_t *parts = nullptr;
+		acm_automaton_sequence(aut, i, &iid, &nparts, &parts, nullptr, nullptr);
 		sh.seq_iid.push_back(iid);
+		if (nparts > 0)
+			acm_automaton_pattern_wildcard(aut, parts[nparts - 1], nullptr, &post, nullptr, nullptr);
+		sh.seq_post.push_back(post);
 	}
 	if (c.pos && acm_automaton_load_position_file(aut, c.pos_path.c_str()) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
@@ -1079,10 +1141,11 @@ int main(int argc, char **argv)
 	pthread_barrier_wait(&sh.ready);
 	const double t0 = now_us();
 	size_t matches = 0, reported = 0, bytes = 0, lines = 0, rounds = 0;
-	uint64_t undecided = 0;
+	uint64_t undecided = 0, wild_undecided = 0;
 	for (auto &w : workers) {
 		pthread_join(w.thread, nullptr);
 		undecided += w.undecided;
+		wild_undecided += w.wild_undecided;
 		matches += w.matches;
 		reported += w.reported;
 		bytes += w.bytes;
@@ -1119,6 +1182,9 @@ int main(int argc, char **argv)
 	printf("-----------------------------------\n\n");
 	for (acm_dfa *dfa : sh.dfas)
 		acm_dfa_release(dfa);
+	if (wild_undecided)   // no silent loss: a signature cut by a buffer border is not found, and here that is known
+		fprintf(stderr, "NOTE: %lu wildcard candidates reach over a buffer border and were not decided (raise -B/-G)\n",
+		    (unsigned long)wild_undecided);
 	if (undecided) {   // no silent loss: the counts and records above are without them
 		printf("ERROR: %lu end-anchored candidates lie in files that span buffers (raise -B/-G)\n", (unsigned long)undecided);
 		return 1;

@@ -2,6 +2,7 @@
 // Nothing here is part of the ABI (see include/acmatch.h for that).
 #pragma once
 
+#include <array>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -58,7 +59,16 @@ struct acm_automaton {
 		bool positioned() const { return pos_lo != 0 || pos_hi != INT32_MAX || pos_flags != 0; }
 		// the sequence this pattern is a part of (acm_automaton_add_sequence) and its level there, or -1
 		int32_t seq = -1, seq_level = 0;
+		// a wildcard pattern (acm_automaton_add_wildcard): bytes is its anchor, and the positions in front of
+		// and behind the anchor are its context: wild_sets holds their pre + post sets of 32 bytes, wild_cells
+		// one cell each (an exact byte, or 0x100 | index into acm_automaton::wild_classes).  compile never
+		// reads these: acm_dfa_upload copies them for the wildcard pass (wildcard.hip)
+		int32_t wild_pre = 0, wild_post = 0;
+		std::vector<uint8_t> wild_sets;
+		std::vector<uint16_t> wild_cells;
 	};
+	// the distinct context sets of two or more bytes, interned: at most 256
+	std::vector<std::array<uint8_t, 32>> wild_classes;
 	// ordered multi-part signatures (acm_automaton_add_sequence).  compile never reads these:
 	// acm_dfa_upload copies them for the sequence pass (sequence.hip)
 	struct Sequence {

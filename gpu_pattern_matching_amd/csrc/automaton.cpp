@@ -317,12 +317,69 @@ extern "C" int acm_automaton_pattern_sequence(const acm_automaton *a, int patter
 
 namespace {
 
-// a signature body, parsed: the fixed parts and the gap in front of every part but the first
+// a signature body, parsed: the parts and the gap in front of every part but the first.  Syntax 0: a part is
+// its bytes.  ACM_SIG_EXTENDED: a part is its positions, 32 bytes of set each (acm_automaton_add_wildcard).
 struct Signature {
 	std::vector<std::vector<unsigned char>> parts;
 	std::vector<int32_t> gap_lo, gap_hi;
 	int iid = 0;
 	bool has_iid = false;
+	bool extended = false;
+};
+
+// digits at s[i]; false where there is none or the value is too large
+bool sig_number(const char *s, size_t &i, int64_t &v)
+{
+	if (!isdigit((unsigned char)s[i]))
+		return false;
+	for (v = 0; isdigit((unsigned char)s[i]); i++)
+		if ((v = v * 10 + (s[i] - '0')) >= INT32_MAX)
+			return false;
+	return true;
+}
+
+// {n}, {n-m}, {-m} or {n-} at s[i] == '{': the gap (l, h), h -1 unbounded; i moves behind it
+bool sig_braces(const char *s, size_t &i, int64_t &l, int64_t &h)
+{
+	i++;
+	bool ok;
+	if (s[i] == '-') {   // {-m}
+		i++;
+		ok = sig_number(s, i, h);
+	} else {
+		ok = sig_number(s, i, l);
+		if (ok && s[i] == '-') {   // {n-} or {n-m}
+			i++;
+			if (s[i] == '}')
+				h = -1;
+			else
+				ok = sig_number(s, i, h);
+		} else {
+			h = l;   // {n}
+		}
+	}
+	if (!ok || s[i] != '}')
+		return false;
+	i++;
+	return true;
+}
+
+// the gap being summed between two parts
+struct GapSum {
+	int64_t lo = 0, hi = 0;   // hi: -1 unbounded
+	bool open = false;
+	bool add(int64_t l, int64_t h)
+	{
+		lo += l;
+		hi = (hi < 0 || h < 0) ? -1 : hi + h;
+		return lo < INT32_MAX && hi < INT32_MAX;
+	}
+	void close(Signature &sig)
+	{
+		sig.gap_lo.push_back((int32_t)lo);
+		sig.gap_hi.push_back(hi < 0 ? INT32_MAX : (int32_t)hi);
+		open = false;
+	}
 };
 
 // Parses body (hex byte pairs, ??, *, {n}, {n-m}, {-m}, {n-}).  Returns 0, or the column (from 1) of the
@@ -333,28 +390,8 @@ int parse_signature(const char *s, Signature &sig, const char *&why)
 	sig.gap_lo.clear();
 	sig.gap_hi.clear();
 	std::vector<unsigned char> part;
-	int64_t lo = 0, hi = 0;   // the gap being summed (hi: -1 unbounded)
-	bool in_gap = false;
+	GapSum gap;
 	size_t i = 0;
-	auto number = [&](int64_t &v) {   // digits at i; false where there is none or the value is too large
-		if (!isdigit((unsigned char)s[i]))
-			return false;
-		for (v = 0; isdigit((unsigned char)s[i]); i++)
-			if ((v = v * 10 + (s[i] - '0')) >= INT32_MAX)
-				return false;
-		return true;
-	};
-	auto add_gap = [&](int64_t l, int64_t h) {
-		if (!in_gap) {
-			sig.parts.push_back(part);
-			part.clear();
-			lo = hi = 0;
-			in_gap = true;
-		}
-		lo += l;
-		hi = (hi < 0 || h < 0) ? -1 : hi + h;
-		return lo < INT32_MAX && hi < INT32_MAX;
-	};
 	while (s[i]) {
 		const size_t at = i;
 		const unsigned char c = (unsigned char)s[i];
@@ -364,11 +401,8 @@ int parse_signature(const char *s, Signature &sig, const char *&why)
 				why = s[i + 1] == '?' ? "nibble wildcards are not supported" : "odd hex digit";
 				return (int)at + 1;
 			}
-			if (in_gap) {
-				sig.gap_lo.push_back((int32_t)lo);
-				sig.gap_hi.push_back(hi < 0 ? INT32_MAX : (int32_t)hi);
-				in_gap = false;
-			}
+			if (gap.open)
+				gap.close(sig);
 			part.push_back((unsigned char)(hex_nibble(c) << 4 | hex_nibble((unsigned char)s[i + 1])));
 			i += 2;
 			continue;
@@ -384,45 +418,32 @@ int parse_signature(const char *s, Signature &sig, const char *&why)
 			h = -1;
 			i++;
 		} else if (c == '{') {
-			i++;
-			bool ok;
-			if (s[i] == '-') {   // {-m}
-				i++;
-				ok = number(h);
-			} else {
-				ok = number(l);
-				if (ok && s[i] == '-') {   // {n-} or {n-m}
-					i++;
-					if (s[i] == '}')
-						h = -1;
-					else
-						ok = number(h);
-				} else {
-					h = l;   // {n}
-				}
-			}
-			if (!ok || s[i] != '}') {
+			if (!sig_braces(s, i, l, h)) {
 				why = "not {n}, {n-m}, {-m} or {n-}";
 				return (int)at + 1;
 			}
-			i++;
 		} else {
 			why = (c == '(' || c == '|' || c == ')') ? "alternatives are not supported"
 			      : c == '!'                         ? "negation is not supported"
 			                                         : "not a hex digit, ??, * or {..}";
 			return (int)at + 1;
 		}
-		if (part.empty() && !in_gap) {
+		if (part.empty() && !gap.open) {
 			why = "a gap in front of the first part";
 			return (int)at + 1;
 		}
-		if (!add_gap(l, h)) {
+		if (!gap.open) {
+			sig.parts.push_back(part);
+			part.clear();
+			gap = GapSum{ 0, 0, true };
+		}
+		if (!gap.add(l, h)) {
 			why = "gap too large";
 			return (int)at + 1;
 		}
 	}
-	if (in_gap || part.empty()) {
-		why = in_gap ? "a gap behind the last part" : "empty signature";
+	if (gap.open || part.empty()) {
+		why = gap.open ? "a gap behind the last part" : "empty signature";
 		return (int)i + 1;
 	}
 	sig.parts.push_back(part);
@@ -433,44 +454,242 @@ int parse_signature(const char *s, Signature &sig, const char *&why)
 	return 0;
 }
 
-// adds the parts and the sequence of a parsed signature: cannot fail but for memory
+inline void set_add(unsigned char *set, unsigned b) { set[b >> 3] |= (unsigned char)(1u << (b & 7)); }
+
+int set_count(const unsigned char *set)
+{
+	int n = 0;
+	for (int k = 0; k < 32; k++)
+		n += __builtin_popcount(set[k]);
+	return n;
+}
+
+// The extended syntax (ACM_SIG_EXTENDED): a position is HH, H?, ?H, ??, (HH|HH|...) or !(HH|...); * and {..}
+// separate parts.  A part is its positions' sets.  Returns 0, or the column (from 1) of the first byte that is
+// wrong, with why; a part without an exact byte is reported at the column it begins at.
+int parse_signature_ex(const char *s, Signature &sig, const char *&why)
+{
+	sig.parts.clear();
+	sig.gap_lo.clear();
+	sig.gap_hi.clear();
+	sig.extended = true;
+	std::vector<unsigned char> part;   // 32 bytes per position
+	size_t part_at = 0;                // where the part began
+	bool exact = false, last_any = false;
+	GapSum gap;
+	size_t i = 0;
+	auto hex_pair = [&](size_t k) {   // the byte at s[k], s[k + 1], or -1
+		const int a = hex_nibble((unsigned char)s[k]);
+		const int b = a < 0 ? -1 : hex_nibble((unsigned char)s[k + 1]);
+		return b < 0 ? -1 : (a << 4 | b);
+	};
+	while (s[i]) {
+		const size_t at = i;
+		const unsigned char c = (unsigned char)s[i];
+		unsigned char set[32] = { 0 };
+		bool position = true;
+		int64_t l = 0, h = 0;
+		if (hex_nibble(c) >= 0) {
+			const int lo = hex_nibble((unsigned char)s[i + 1]);
+			if (lo >= 0) {
+				set_add(set, (unsigned)(hex_nibble(c) << 4 | lo));
+			} else if (s[i + 1] == '?') {
+				for (unsigned x = 0; x < 16; x++)
+					set_add(set, (unsigned)hex_nibble(c) << 4 | x);
+			} else {
+				why = "odd hex digit";
+				return (int)at + 1;
+			}
+			i += 2;
+		} else if (c == '?') {
+			const int lo = hex_nibble((unsigned char)s[i + 1]);
+			if (s[i + 1] == '?') {
+				memset(set, 0xFF, 32);
+			} else if (lo >= 0) {
+				for (unsigned x = 0; x < 16; x++)
+					set_add(set, x << 4 | (unsigned)lo);
+			} else {
+				why = "not ?? or ?H";
+				return (int)at + 1;
+			}
+			i += 2;
+		} else if (c == '(' || c == '!') {
+			if (c == '!' && s[i + 1] != '(') {
+				why = "a ! that no ( follows";
+				return (int)at + 1;
+			}
+			i += c == '!' ? 2 : 1;
+			for (;;) {
+				const int b = hex_pair(i);
+				if (b < 0) {
+					why = "not a hex byte in an alternative";
+					return (int)i + 1;
+				}
+				set_add(set, (unsigned)b);
+				i += 2;
+				if (s[i] == ')')
+					break;
+				if (s[i] != '|') {
+					why = hex_nibble((unsigned char)s[i]) >= 0 ? "alternatives of more than one byte are not supported"
+					                                           : "not | or ) in an alternative";
+					return (int)i + 1;
+				}
+				i++;
+			}
+			i++;
+			if (c == '!')
+				for (int k = 0; k < 32; k++)
+					set[k] = (unsigned char)~set[k];
+			if (set_count(set) == 0) {
+				why = "a position that no byte matches";
+				return (int)at + 1;
+			}
+		} else if (c == '*') {
+			position = false;
+			h = -1;
+			i++;
+		} else if (c == '{') {
+			position = false;
+			if (!sig_braces(s, i, l, h)) {
+				why = "not {n}, {n-m}, {-m} or {n-}";
+				return (int)at + 1;
+			}
+		} else {
+			why = "not a position, * or {..}";
+			return (int)at + 1;
+		}
+		if (position) {
+			const int n = set_count(set);
+			if (sig.parts.empty() && part.empty() && n == 256) {
+				why = "?? in front of the first position";
+				return (int)at + 1;
+			}
+			if (part.size() / 32 >= (size_t)ACM_WILDCARD_MAX_POSITIONS) {
+				why = "a part of too many positions";
+				return (int)at + 1;
+			}
+			if (gap.open)
+				gap.close(sig);
+			if (part.empty()) {
+				part_at = at;
+				exact = false;
+			}
+			part.insert(part.end(), set, set + 32);
+			exact = exact || n == 1;
+			last_any = n == 256;
+			continue;
+		}
+		if (part.empty() && !gap.open) {
+			why = "a gap in front of the first part";
+			return (int)at + 1;
+		}
+		if (!gap.open) {
+			if (!exact) {
+				why = "a part without an exact byte";
+				return (int)part_at + 1;
+			}
+			sig.parts.push_back(part);
+			part.clear();
+			gap = GapSum{ 0, 0, true };
+		}
+		if (!gap.add(l, h)) {
+			why = "gap too large";
+			return (int)at + 1;
+		}
+	}
+	if (gap.open || part.empty()) {
+		why = gap.open ? "a gap behind the last part" : "empty signature";
+		return (int)i + 1;
+	}
+	if (last_any) {
+		why = "?? behind the last position";
+		return (int)i + 1;
+	}
+	if (!exact) {
+		why = "a part without an exact byte";
+		return (int)part_at + 1;
+	}
+	sig.parts.push_back(part);
+	if (sig.parts.size() > (size_t)ACM_SEQ_MAX_PARTS) {
+		why = "too many parts";
+		return (int)i + 1;
+	}
+	return 0;
+}
+
+// the context sets of two or more bytes among the n positions of sets that the automaton has not interned and
+// fresh does not hold yet are added to fresh; false when the automaton would then hold more than 256
+bool wild_room(const acm_automaton *a, const unsigned char *sets, int n, std::vector<std::array<uint8_t, 32>> &fresh)
+{
+	for (int i = 0; i < n; i++) {
+		if (set_count(sets + 32 * (size_t)i) < 2)
+			continue;
+		std::array<uint8_t, 32> c;
+		memcpy(c.data(), sets + 32 * (size_t)i, 32);
+		if (std::find(a->wild_classes.begin(), a->wild_classes.end(), c) == a->wild_classes.end() &&
+		    std::find(fresh.begin(), fresh.end(), c) == fresh.end())
+			fresh.push_back(c);
+	}
+	return a->wild_classes.size() + fresh.size() <= 256;
+}
+
+// adds the parts and the sequence of a parsed signature: cannot fail but for memory, once signatures_fit
 int apply_signature(acm_automaton *a, const Signature &sig, int iid, unsigned flags)
 {
 	std::vector<int32_t> parts;
 	for (const auto &p : sig.parts) {
 		parts.push_back((int32_t)a->patterns.size());
-		if (int rc = acm_automaton_add_ex(a, p.data(), (int)p.size(), iid, flags))
+		const int rc = sig.extended ? acm_automaton_add_wildcard(a, p.data(), (int)(p.size() / 32), iid, flags)
+		                            : acm_automaton_add_ex(a, p.data(), (int)p.size(), iid, flags);
+		if (rc < 0)
 			return rc;
 	}
 	return acm_automaton_add_sequence(a, parts.data(), sig.gap_lo.data(), sig.gap_hi.data(), (int)parts.size(), iid);
 }
 
-}  // namespace
-
-extern "C" int acm_automaton_add_signature(acm_automaton *a, const char *body, int iid, unsigned flags)
+// do the context sets of all these signatures fit the automaton's 256?  (Exact: a set of two or more bytes
+// never lies in an anchor.)  Asked before anything is added, so that a refused load applies nothing.
+bool signatures_fit(const acm_automaton *a, const Signature *sigs, size_t n)
 {
-	if (!a || !body)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_signature: bad arguments");
+	std::vector<std::array<uint8_t, 32>> fresh;
+	for (size_t k = 0; k < n; k++)
+		if (sigs[k].extended)
+			for (const auto &p : sigs[k].parts)
+				if (!wild_room(a, p.data(), (int)(p.size() / 32), fresh))
+					return false;
+	return true;
+}
+
+int sig_args(const char *fn, acm_automaton *a, const void *arg, unsigned flags, unsigned syntax)
+{
+	if (!a || !arg)
+		return acm::fail(ACM_ERR_ARG, "%s: bad arguments", fn);
 	if (flags & ~(unsigned)ACM_PATTERN_NOCASE)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_signature: unknown flag bits 0x%x", flags & ~(unsigned)ACM_PATTERN_NOCASE);
+		return acm::fail(ACM_ERR_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~(unsigned)ACM_PATTERN_NOCASE);
+	if (syntax & ~(unsigned)ACM_SIG_EXTENDED)
+		return acm::fail(ACM_ERR_ARG, "%s: unknown syntax bits 0x%x", fn, syntax & ~(unsigned)ACM_SIG_EXTENDED);
 	if (a->compiled)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_signature: automaton already compiled");
+		return acm::fail(ACM_ERR_ARG, "%s: automaton already compiled", fn);
+	return ACM_OK;
+}
+
+int add_signature(const char *fn, acm_automaton *a, const char *body, int iid, unsigned flags, unsigned syntax)
+{
+	if (int rc = sig_args(fn, a, body, flags, syntax))
+		return rc;
 	Signature sig;
 	const char *why = "";
-	if (const int col = parse_signature(body, sig, why))
+	if (const int col = (syntax & ACM_SIG_EXTENDED) ? parse_signature_ex(body, sig, why) : parse_signature(body, sig, why))
 		return acm::fail(ACM_ERR_PARSE, "signature: column %d: %s", col, why);
+	if (!signatures_fit(a, &sig, 1))
+		return acm::fail(ACM_ERR_LIMIT, "%s: more than 256 distinct context sets", fn);
 	return apply_signature(a, sig, iid, flags);
 }
 
-extern "C" int acm_automaton_load_signature_file(acm_automaton *a, const char *path, unsigned flags)
+int load_signature_file(const char *fn, acm_automaton *a, const char *path, unsigned flags, unsigned syntax)
 {
-	if (!a || !path)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_load_signature_file: bad arguments");
-	if (flags & ~(unsigned)ACM_PATTERN_NOCASE)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_load_signature_file: unknown flag bits 0x%x",
-		    flags & ~(unsigned)ACM_PATTERN_NOCASE);
-	if (a->compiled)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_load_signature_file: automaton already compiled");
+	if (int rc = sig_args(fn, a, path, flags, syntax))
+		return rc;
 	std::ifstream in(path);
 	if (!in)
 		return acm::fail(ACM_ERR_IO, "cannot open signature file '%s': %s", path, strerror(errno));
@@ -495,16 +714,142 @@ extern "C" int acm_automaton_load_signature_file(acm_automaton *a, const char *p
 			b = k + 1;
 		}
 		const char *why = "";
-		if (const int col = parse_signature(line.c_str() + b, sig, why))
+		const char *body = line.c_str() + b;
+		if (const int col = (syntax & ACM_SIG_EXTENDED) ? parse_signature_ex(body, sig, why) : parse_signature(body, sig, why))
 			return acm::fail(ACM_ERR_PARSE, "%s:%d: column %d: %s", path, line_no, (int)b + col, why);
 		sigs.push_back(std::move(sig));
 	}
+	if (!signatures_fit(a, sigs.data(), sigs.size()))
+		return acm::fail(ACM_ERR_LIMIT, "%s: '%s' needs more than 256 distinct context sets", fn, path);
 	for (const Signature &sig : sigs) {
 		const int rc = apply_signature(a, sig, sig.has_iid ? sig.iid : (int)a->sequences.size(), flags);
 		if (rc < 0)
 			return rc;
 	}
 	return (int)sigs.size();
+}
+
+}  // namespace
+
+extern "C" int acm_automaton_add_signature(acm_automaton *a, const char *body, int iid, unsigned flags)
+{
+	return add_signature("acm_automaton_add_signature", a, body, iid, flags, 0);
+}
+
+extern "C" int acm_automaton_add_signature_ex(acm_automaton *a, const char *body, int iid, unsigned flags, unsigned syntax)
+{
+	return add_signature("acm_automaton_add_signature_ex", a, body, iid, flags, syntax);
+}
+
+extern "C" int acm_automaton_load_signature_file(acm_automaton *a, const char *path, unsigned flags)
+{
+	return load_signature_file("acm_automaton_load_signature_file", a, path, flags, 0);
+}
+
+extern "C" int acm_automaton_load_signature_file_ex(acm_automaton *a, const char *path, unsigned flags, unsigned syntax)
+{
+	return load_signature_file("acm_automaton_load_signature_file_ex", a, path, flags, syntax);
+}
+
+// ---- wildcard patterns -----------------------------------------------------------
+
+extern "C" int acm_automaton_add_wildcard(acm_automaton *a, const uint8_t *sets, int n, int iid, unsigned flags)
+{
+	if (!a || !sets || n < 1)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_wildcard: bad arguments");
+	if (flags & ~(unsigned)ACM_PATTERN_NOCASE)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_wildcard: unknown flag bits 0x%x", flags & ~(unsigned)ACM_PATTERN_NOCASE);
+	if (a->compiled)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_wildcard: automaton already compiled");
+	if (n > ACM_WILDCARD_MAX_POSITIONS)
+		return acm::fail(ACM_ERR_LIMIT, "acm_automaton_add_wildcard: %d positions, at most %d", n, ACM_WILDCARD_MAX_POSITIONS);
+	// the anchor: the longest run of one-byte sets, the leftmost among equal runs
+	int at = 0, len = 0, run = 0;
+	for (int i = 0; i < n; i++) {
+		const int c = set_count(sets + 32 * (size_t)i);
+		if (c == 0)
+			return acm::fail(ACM_ERR_ARG, "acm_automaton_add_wildcard: position %d: empty set", i);
+		run = c == 1 ? run + 1 : 0;
+		if (run > len) {
+			len = run;
+			at = i + 1 - run;
+		}
+	}
+	if (len == 0)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_wildcard: no position with a one-byte set");
+	const int pre = at, post = n - at - len;
+	std::vector<std::array<uint8_t, 32>> fresh;
+	if (!wild_room(a, sets, pre, fresh) || !wild_room(a, sets + 32 * (size_t)(at + len), post, fresh))
+		return acm::fail(ACM_ERR_LIMIT, "acm_automaton_add_wildcard: more than 256 distinct context sets");
+	auto only_byte = [&](int i) {
+		const uint8_t *s = sets + 32 * (size_t)i;
+		for (int b = 0; b < 256; b++)
+			if (s[b >> 3] >> (b & 7) & 1)
+				return b;
+		return 0;
+	};
+	std::vector<unsigned char> anchor(len);
+	for (int i = 0; i < len; i++)
+		anchor[i] = (unsigned char)only_byte(at + i);
+	const int index = (int)a->patterns.size();
+	if (int rc = acm_automaton_add_ex(a, anchor.data(), len, iid, flags))
+		return rc;
+	a->wild_classes.insert(a->wild_classes.end(), fresh.begin(), fresh.end());
+	acm_automaton::Pattern &p = a->patterns[index];
+	p.wild_pre = pre;
+	p.wild_post = post;
+	for (int i = 0; i < n; i++) {
+		if (i >= at && i < at + len)
+			continue;
+		const uint8_t *s = sets + 32 * (size_t)i;
+		p.wild_sets.insert(p.wild_sets.end(), s, s + 32);
+		if (set_count(s) == 1) {
+			p.wild_cells.push_back((uint16_t)only_byte(i));
+		} else {
+			std::array<uint8_t, 32> c;
+			memcpy(c.data(), s, 32);
+			const size_t k = std::find(a->wild_classes.begin(), a->wild_classes.end(), c) - a->wild_classes.begin();
+			p.wild_cells.push_back((uint16_t)(0x100 | k));
+		}
+	}
+	return index;
+}
+
+extern "C" int acm_automaton_pattern_wildcard(const acm_automaton *a, int index, int *pre, int *post, const uint8_t **pre_sets,
+    const uint8_t **post_sets)
+{
+	if (!a || index < 0 || index >= (int)a->patterns.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_pattern_wildcard: index out of range");
+	const acm_automaton::Pattern &p = a->patterns[index];
+	if (pre) *pre = p.wild_pre;
+	if (post) *post = p.wild_post;
+	if (pre_sets) *pre_sets = p.wild_sets.data();
+	if (post_sets) *post_sets = p.wild_sets.data() + 32 * (size_t)p.wild_pre;
+	return (p.wild_pre || p.wild_post) ? 1 : 0;
+}
+
+extern "C" int acm_automaton_wildcards(const acm_automaton *a)
+{
+	if (a)
+		for (auto &p : a->patterns)
+			if (p.wild_pre || p.wild_post)
+				return 1;
+	return 0;
+}
+
+extern "C" int acm_automaton_wildcard_reach(const acm_automaton *a, int *back, int *ahead)
+{
+	if (!a)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_wildcard_reach: null automaton");
+	int b = 0, f = 0;
+	for (auto &p : a->patterns)
+		if (p.wild_pre || p.wild_post) {
+			b = std::max(b, p.wild_pre + (int)p.bytes.size());
+			f = std::max(f, p.wild_post);
+		}
+	if (back) *back = b;
+	if (ahead) *ahead = f;
+	return ACM_OK;
 }
 
 // ---- pattern file ------------------------------------------------------------

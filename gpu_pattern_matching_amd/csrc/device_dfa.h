@@ -68,6 +68,13 @@ struct acm_dfa {
 	int32_t *d_seq_slot = nullptr;       // [slots][2] {slot of the part in front or -1, sequence index or -1: not the last part}
 	uint32_t seq_slots = 0, seq_levels = 0;
 	uint32_t seq_level_base[ACM_SEQ_MAX_PARTS + 1] = { 0 };   // slots [base[j], base[j + 1]) are level j
+	// an automaton with wildcard contexts only (acm_automaton_wildcards at upload), for the wildcard pass
+	// (wildcard.hip); null otherwise.  The position and sequence tables above then hold the folded lengths.
+	bool wild = false;
+	int32_t *d_wild_ent = nullptr;       // [patterns][4] {cell index of the context in d_wild_pool, pre, post, length}
+	uint16_t *d_wild_pool = nullptr;     // per context position an exact byte, or 0x100 | class; a pattern's cells start on a word
+	uint32_t *d_wild_sets = nullptr;     // [wild_classes][8] the interned sets, bit b & 31 of word b / 32
+	uint32_t wild_classes = 0;
 	size_t device_bytes = 0;
 	void *arena = nullptr;               // one allocation for the small tables (device_dfa.hip, upload_small)
 	size_t arena_bytes = 0, arena_used = 0;

@@ -269,7 +269,8 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 				ent[4 * i] = p.pos_lo;
 				ent[4 * i + 1] = p.pos_hi;
 				ent[4 * i + 2] = (int32_t)p.pos_flags;
-				ent[4 * i + 3] = (int32_t)p.bytes.size();
+				// (a wildcard pattern's window counts from its first position: acmatch.h)
+				ent[4 * i + 3] = p.bytes.empty() ? 0 : (int32_t)p.bytes.size() + p.wild_pre;
 			}
 			rc = upload(&d->d_pos_ent, ent.data(), ent.size(), &d->device_bytes);
 		}
@@ -296,9 +297,13 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 					const int32_t p = s.parts[j], me = (int32_t)(slot.size() / 2);
 					slot_of[p] = me;
 					ent[4 * (size_t)p] = me;
+					// a wildcard part: the join works on full spans while the records keep the anchors' ends, so
+					// the length reaches from the part's first position over the post context of the part in front
+					ent[4 * (size_t)p + 3] += a->patterns[p].wild_pre;
 					if (j > 0) {
 						ent[4 * (size_t)p + 1] = s.gap_lo[j - 1];
 						ent[4 * (size_t)p + 2] = s.gap_hi[j - 1];
+						ent[4 * (size_t)p + 3] += a->patterns[s.parts[j - 1]].wild_post;
 					}
 					slot.push_back(j > 0 ? slot_of[s.parts[j - 1]] : -1);
 					slot.push_back(j + 1 == s.parts.size() ? (int32_t)q : -1);
@@ -310,6 +315,32 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 				d->seq_level_base[j] = d->seq_slots;
 			rc = upload(&d->d_seq_ent, ent.data(), ent.size(), &d->device_bytes);
 			if (rc == ACM_OK) rc = upload(&d->d_seq_slot, slot.data(), slot.size(), &d->device_bytes);
+		}
+		// an automaton with wildcard contexts (acm_automaton_wildcards): per pattern where its context cells lie,
+		// the cells, and the interned sets as words (wildcard.hip).  Allocations of their own, as above.
+		d->wild = acm_automaton_wildcards(a) != 0;
+		if (rc == ACM_OK && d->wild) {
+			std::vector<int32_t> ent(4 * a->patterns.size());
+			std::vector<uint16_t> pool;
+			for (size_t i = 0; i < a->patterns.size(); i++) {
+				const acm_automaton::Pattern &p = a->patterns[i];
+				ent[4 * i] = (int32_t)pool.size();
+				ent[4 * i + 1] = p.wild_pre;
+				ent[4 * i + 2] = p.wild_post;
+				ent[4 * i + 3] = (int32_t)p.bytes.size();
+				pool.insert(pool.end(), p.wild_cells.begin(), p.wild_cells.end());
+				if (pool.size() & 1)
+					pool.push_back(0);
+			}
+			pool.resize(pool.size() + 2, 0);
+			std::vector<uint32_t> sets(8 * std::max<size_t>(a->wild_classes.size(), 1), 0);
+			for (size_t c = 0; c < a->wild_classes.size(); c++)
+				for (int k = 0; k < 32; k++)
+					sets[8 * c + k / 4] |= (uint32_t)a->wild_classes[c][k] << (8 * (k % 4));
+			d->wild_classes = (uint32_t)a->wild_classes.size();
+			rc = upload(&d->d_wild_ent, ent.data(), ent.size(), &d->device_bytes);
+			if (rc == ACM_OK) rc = upload(&d->d_wild_pool, pool.data(), pool.size(), &d->device_bytes);
+			if (rc == ACM_OK) rc = upload(&d->d_wild_sets, sets.data(), sets.size(), &d->device_bytes);
 		}
 	} catch (const std::bad_alloc &) {
 		rc = acm::fail(ACM_ERR_NOMEM, "acm_dfa_upload: out of host memory");
@@ -371,6 +402,9 @@ extern "C" void acm_dfa_release(acm_dfa *d)
 		hipFree(d->d_pos_ent);
 		hipFree(d->d_seq_ent);
 		hipFree(d->d_seq_slot);
+		hipFree(d->d_wild_ent);
+		hipFree(d->d_wild_pool);
+		hipFree(d->d_wild_sets);
 		free_small(d, d->d_depth);
 		free_small(d, d->d_class);
 		free_small(d, d->d_sv_bloom);

@@ -195,8 +195,9 @@ int acm_automaton_load_position_file(acm_automaton *, const char *path);
  *                                    naming the line, and nothing of the file is applied.  Returns the
  *                                    number of sequences added.  A pure hex line is a 1-part sequence.
  * Not provided: sequences whose parts lie in different calls (a stream cut inside a signature is not
- * joined: scan whole texts), negative distances or overlapping parts, nibble wildcards and alternatives,
- * where a match begins.  The reference-named layer is unchanged. */
+ * joined: scan whole texts), negative distances or overlapping parts, alternatives of more than one byte,
+ * where a match begins.  Nibble wildcards and one-byte alternatives: the extended syntax below.  The
+ * reference-named layer is unchanged. */
 #define ACM_SEQ_MAX_PARTS 32
 #define ACM_GAP_UNBOUNDED INT32_MAX
 int acm_automaton_add_sequence(acm_automaton *, const int32_t *parts, const int32_t *gap_lo,
@@ -207,6 +208,65 @@ int acm_automaton_sequence(const acm_automaton *, int index, int *iid, int *npar
 int acm_automaton_pattern_sequence(const acm_automaton *, int pattern, int *sequence, int *level);
 int acm_automaton_add_signature(acm_automaton *, const char *body, int iid, unsigned flags);
 int acm_automaton_load_signature_file(acm_automaton *, const char *path, unsigned flags);
+
+/* Wildcard patterns: literal + confirm.  A WILDCARD PATTERN is n positions, 1 <= n <=
+ * ACM_WILDCARD_MAX_POSITIONS, each a set of byte values: 32 bytes, bit b & 7 of byte b / 8 set = byte b is
+ * in the set (the layout of acm_word_matches_async's word_set).  It matches where every position holds a
+ * byte of its set.
+ * The ANCHOR is the longest run of positions whose set holds exactly one byte, the leftmost among equal
+ * runs.  Only its L bytes enter the automaton, added with acm_automaton_add_ex(..., iid, flags);
+ * acm_automaton_add_wildcard returns that pattern's index.  The pre positions in front of the anchor are the
+ * pattern's PRE context, the post positions behind it its POST context; acm_wildcard_matches_async checks
+ * them where the anchor matched.  ACM_PATTERN_NOCASE applies to the anchor only: context sets are compared
+ * with raw text bytes (a case-blind context position is the set {A, a}).  A pattern whose positions are all
+ * one-byte sets is a plain pattern (pre = post = 0), and an automaton without any context is bit for bit
+ * what it is without this interface: tables, digests, self-tests and acm_dfa_device_bytes.
+ * Context sets of two or more bytes are interned per automaton: at most 256 distinct ones (a one-byte set in
+ * a context does not count).  Contexts do not enter acm_automaton_compile; acm_dfa_upload takes a copy.
+ *   acm_automaton_add_wildcard      ACM_ERR_ARG: no position with a one-byte set, an empty set, n < 1, unknown
+ *                                   flags, a compiled automaton (it adds a pattern); ACM_ERR_LIMIT: n above
+ *                                   the maximum, or a 257th distinct set.  On an error nothing is applied.
+ *   acm_automaton_pattern_wildcard  1 if pattern `index` has a context, else 0 (negative: a bad index); pre and
+ *                                   post, and borrowed pointers to their pre * 32 and post * 32 bytes of sets
+ *                                   (any pointer may be NULL)
+ *   acm_automaton_wildcards         1 if some pattern has a context
+ *   acm_automaton_wildcard_reach    over the patterns that have a context: back = the largest pre + L (bytes
+ *                                   from a pattern's first position to its anchor's end), ahead = the largest
+ *                                   post.  What a streaming caller keeps of the piece in front, and how far
+ *                                   behind an anchor a match can end.  Both 0 without contexts.
+ * How the other per-pattern rules see a wildcard pattern (folded into their tables at upload):
+ *   position windows   count from the pattern's FIRST POSITION (a = o - L - pre + 1), for both window kinds
+ *   sequences          gaps count between the parts' full spans: from the last position of the part in front
+ *                      to the first position of this part.  Exact for records that went through
+ *                      acm_wildcard_matches_async with the same starts.  The sequence pass keeps reporting
+ *                      the end of the last part's ANCHOR; the match ends post bytes behind it (the caller
+ *                      adds that after the fetch: acm_automaton_pattern_wildcard of the last part)
+ *   whole words        NOT composed: the word pass looks at the bytes next to the anchor
+ * Extended body syntax: acm_automaton_add_signature_ex and acm_automaton_load_signature_file_ex are the two
+ * entry points above with a syntax argument.  syntax 0 is exactly those (a?, (..|..) and ! stay
+ * ACM_ERR_PARSE); unknown syntax bits are ACM_ERR_ARG.  With ACM_SIG_EXTENDED a body is POSITIONS and gaps:
+ *   HH            an exact byte                H? or ?H      the 16 bytes with that nibble
+ *   ??            any byte (a position here, not a gap of one)
+ *   (HH|HH|...)   the listed bytes (one entry: an exact byte)        !(HH|...)   every other byte
+ * and only * and {...} separate parts.  Every part needs an exact byte and is added with
+ * acm_automaton_add_wildcard.  The body begins and ends with a position that is not ??.  Alternatives of more
+ * than one byte ((aabb|ccdd)), a ! that no ( follows, a part of more than ACM_WILDCARD_MAX_POSITIONS
+ * positions and everything syntax 0 rejects in gap tokens are ACM_ERR_PARSE with the column (a part without
+ * an exact byte: the column it begins at).  A body is parsed completely, and the room for its sets checked,
+ * before anything is added; a bad line (or a file that needs a 257th set: ACM_ERR_LIMIT) leaves nothing of
+ * its file applied.  For a body that holds neither ?? nor a new token both syntaxes add the same patterns
+ * and sequence. */
+#define ACM_WILDCARD_MAX_POSITIONS 4096
+enum { ACM_SIG_EXTENDED = 1 };
+int acm_automaton_add_wildcard(acm_automaton *, const uint8_t *sets, int n, int iid, unsigned flags);
+int acm_automaton_pattern_wildcard(const acm_automaton *, int index, int *pre, int *post,
+    const uint8_t **pre_sets, const uint8_t **post_sets);
+int acm_automaton_wildcards(const acm_automaton *);
+int acm_automaton_wildcard_reach(const acm_automaton *, int *back, int *ahead);
+int acm_automaton_add_signature_ex(acm_automaton *, const char *body, int iid, unsigned flags,
+    unsigned syntax);
+int acm_automaton_load_signature_file_ex(acm_automaton *, const char *path, unsigned flags,
+    unsigned syntax);
 
 /* ASCII case-insensitive matching for every pattern of the automaton.  With
  * it on, fold(b) = b - 0x20 for 'a' <= b <= 'z' and b otherwise (toupper in
@@ -584,6 +644,51 @@ int acm_position_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
     size_t segments, long lead_begin, long text_end, long open_end, int all_patterns,
     int32_t *d_pat_out, int32_t *d_off_out, size_t out_capacity, int32_t *d_info,
     void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Wildcard patterns (acm_automaton_add_wildcard) confirmed on the device: an entry is kept iff the bytes around
+ * its anchor lie in the pattern's context sets.  A pass over the records: cost per record and per context byte,
+ * never per text byte; no scan kernel is involved.
+ * Input: planes in the scan's cell layout; at most min([0], max_records) records are looked at.  report as in
+ * acm_position_matches_async:
+ *   ACM_REPORT_STATE  final states; the entries of a record are its state's match list
+ *   ACM_REPORT_HEAD   pattern indices, one entry per record (a HEAD scan, or the all-patterns output of the
+ *                     expand, case or position pass).  Needs all_patterns != 0, else ACM_ERR_ARG: the first
+ *                     form of acm_position_matches_async behind this pass gives the head per offset.
+ * The text bytes are given as to acm_case_matches_async (d_text, text_origin, text_end, d_before, before_len).
+ * The text [T0, Tend) of a record is found as acm_position_matches_async finds it (d_seg_start, segments,
+ * lead_begin; Tend the next start if it is <= text_end, else open_end, or unknown when that is -1: no end
+ * is then in the way).
+ * The rule for entry (p, o) with L >= 1, a = o - L + 1 and span [a - pre, o + post], int64 arithmetic, in
+ * this order:
+ *   1. p has no context: kept, whatever its text is
+ *   2. the span leaves [T0, Tend): dropped
+ *   3. the span leaves the bytes given, [text_origin - before_len, text_end): UNDECIDED -- dropped and
+ *      counted, whatever the available bytes hold
+ *   4. kept iff every context byte is in its set
+ * Output, the scan's cell layout and overflow contract ([0] = full count, records, trailer -- the input
+ * trailer unchanged -- at min(count + 1, out_capacity - 1)); offsets are the anchors' ends, unchanged, so the
+ * order is the input's (a match ends post bytes behind its offset):
+ *   all_patterns != 0  one record per kept entry, in list order (STATE input) or input order (HEAD input)
+ *   all_patterns == 0  STATE input only: the first kept entry per record
+ *   d_info             int32[4], required, written whole: [0] undecided entries, [1..3] 0.  In the first
+ *                      form only the entries in front of a record's first kept one are looked at and counted.
+ * For an uploaded set without contexts the call is legal and every entry of length >= 1 is kept: STATE input
+ * in the all form is acm_expand_matches_async's output, in the first form the HEAD scan's records, and HEAD
+ * input is the input, all bit for bit (entries of length 0 aside).  A cell that is neither a state nor a
+ * pattern index writes nothing.  No read leaves the input planes, the starts, [0, text_end - text_origin)
+ * of d_text, [0, before_len) of d_before and the library's tables, and no write leaves the outputs and the
+ * workspace, whatever the planes hold.  The outputs must not overlap the inputs.  Stream-ordered, no host
+ * sync, no allocation, no host read of device data; argument errors (a NULL plane, output or d_info,
+ * out_capacity < 2, an unknown report, HEAD input in the first form, a bad text window, open_end outside
+ * {-1} and [text_end, inf), segments without starts, a short workspace) return ACM_ERR_ARG before anything
+ * is enqueued.  Two launches (csrc/wildcard.hip).  The workspace query is monotone and a multiple of 256. */
+size_t acm_wildcard_workspace_bytes(size_t max_records);
+int acm_wildcard_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
+    const int32_t *d_off_plane, size_t max_records, int report, const void *d_text, long text_origin,
+    long text_end, const void *d_before, size_t before_len, const int32_t *d_seg_start,
+    size_t segments, long lead_begin, long open_end, int all_patterns, int32_t *d_pat_out,
+    int32_t *d_off_out, size_t out_capacity, int32_t *d_info, void *d_workspace,
+    size_t workspace_bytes, void *stream);
 
 /* Sequences (acm_automaton_add_sequence) joined on the device: the records of the parts in, one record
  * per sequence match out.  No text is read.
