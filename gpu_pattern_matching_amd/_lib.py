@@ -42,6 +42,8 @@ SEQ_MAX_PARTS = 32
 GAP_UNBOUNDED = 0x7FFFFFFF
 WILDCARD_MAX_POSITIONS = 4096
 SIG_EXTENDED = 1
+RULE_MAX_OPERANDS = 64
+RULE_MAX_NESTING = 8
 
 
 class AcmError(RuntimeError):
@@ -84,6 +86,12 @@ NATIVE_API = {
     "acm_automaton_wildcard_reach": (C.c_int, [_vp, _i32p, _i32p]),
     "acm_automaton_add_signature_ex": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_uint, C.c_uint]),
     "acm_automaton_load_signature_file_ex": (C.c_int, [_vp, C.c_char_p, C.c_uint, C.c_uint]),
+    "acm_automaton_add_rule": (C.c_int, [_vp, _i32p, C.c_int, C.c_char_p, C.c_int]),
+    "acm_automaton_num_rules": (C.c_int, [_vp]),
+    "acm_automaton_rule": (C.c_int, [_vp, C.c_int, _i32p, _i32p, C.POINTER(_i32p), C.POINTER(C.c_char_p)]),
+    "acm_automaton_sequence_rule": (C.c_int, [_vp, C.c_int, _i32p, _i32p]),
+    "acm_automaton_add_logical_signature": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_uint, C.c_uint]),
+    "acm_automaton_load_logical_file": (C.c_int, [_vp, C.c_char_p, C.c_uint, C.c_uint]),
     "acm_automaton_set_nocase": (C.c_int, [_vp, C.c_int]),
     "acm_automaton_nocase": (C.c_int, [_vp]),
     "acm_automaton_compile": (C.c_int, [_vp]),
@@ -137,6 +145,9 @@ NATIVE_API = {
     "acm_sequence_workspace_bytes": (C.c_size_t, [_vp, C.c_size_t]),
     "acm_sequence_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_long, C.c_long, _vp, _vp,
                                              C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "acm_rule_workspace_bytes": (C.c_size_t, [_vp, C.c_size_t]),
+    "acm_rule_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp,
+                                         C.c_size_t, _vp]),
     "acm_tally_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_tally_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t,
                                           _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -253,6 +253,55 @@ class Automaton:
         check(self.lib.acm_automaton_wildcard_reach(self.h, C.byref(b), C.byref(f)), "acm_automaton_wildcard_reach")
         return b.value, f.value
 
+    def add_rule(self, sequences, expr, iid=0):
+        """A condition over the sequences that hit one text (acm_automaton_add_rule): sequences are the operands,
+        sequence indices, expr e.g. "(0&1)|2>3" over their positions in that list.  Before or after compile(),
+        but before the Matcher is made.  Returns the rule index."""
+        sequences = list(sequences)
+        q = (C.c_int32 * max(len(sequences), 1))(*sequences)
+        expr = expr.encode() if isinstance(expr, str) else bytes(expr)
+        r = self.lib.acm_automaton_add_rule(self.h, q, len(sequences), expr, iid)
+        if r < 0:
+            check(r, "acm_automaton_add_rule")
+        return r
+
+    def add_logical_signature(self, line, iid=0, nocase=False, extended=False):
+        """"expr;body0;body1;..." (acm_automaton_add_logical_signature): every body is added as add_signature
+        adds it and the rule registered over the sequences; only before compile().  Returns the rule index."""
+        line = line.encode() if isinstance(line, str) else bytes(line)
+        r = self.lib.acm_automaton_add_logical_signature(self.h, line, iid, _lib.PATTERN_NOCASE if nocase else 0,
+                                                         _lib.SIG_EXTENDED if extended else 0)
+        if r < 0:
+            check(r, "acm_automaton_add_logical_signature")
+        return r
+
+    def load_logical_file(self, path, nocase=False, extended=False):
+        """logical signatures from a file, one per line with an optional leading "<iid>:"; returns how many"""
+        n = self.lib.acm_automaton_load_logical_file(self.h, str(path).encode(), _lib.PATTERN_NOCASE if nocase else 0,
+                                                     _lib.SIG_EXTENDED if extended else 0)
+        if n < 0:
+            check(n, "acm_automaton_load_logical_file")
+        return n
+
+    @property
+    def num_rules(self):
+        return self.lib.acm_automaton_num_rules(self.h)
+
+    def rule(self, i):
+        """(sequences, expr, iid) of rule i (acm_automaton_rule)"""
+        iid, n, seqs, expr = C.c_int32(), C.c_int32(), C.POINTER(C.c_int32)(), C.c_char_p()
+        check(self.lib.acm_automaton_rule(self.h, i, C.byref(iid), C.byref(n), C.byref(seqs), C.byref(expr)),
+              "acm_automaton_rule")
+        return [seqs[j] for j in range(n.value)], expr.value.decode(), iid.value
+
+    def sequence_rule(self, q):
+        """(rule, operand) sequence q is an operand of, or None (acm_automaton_sequence_rule)"""
+        r, op = C.c_int32(), C.c_int32()
+        rc = self.lib.acm_automaton_sequence_rule(self.h, q, C.byref(r), C.byref(op))
+        if rc < 0:
+            check(rc, "acm_automaton_sequence_rule")
+        return (r.value, op.value) if rc else None
+
     @property
     def num_sequences(self):
         return self.lib.acm_automaton_num_sequences(self.h)
@@ -1034,6 +1083,10 @@ class Matcher:
         last_state, info): a record per match, the sequence index and the offset it ends at; info: [records
         that are a part, alive records over all levels, 0, 0].  A sequence whose parts lie in different calls
         is not joined: scan whole texts."""
+        return self._sequences(text, texts, lead_begin, init_state, before, out_capacity, False)
+
+    def _sequences(self, text, texts, lead_begin, init_state, before, out_capacity, rules):
+        """scan_sequences, and with rules scan_rules: the rule pass over the sequence pass's planes"""
         if texts is not None:
             t, starts = self.pack_segments(texts)
         else:
@@ -1099,13 +1152,24 @@ class Matcher:
                                     all_patterns=True, workspace=(pb[0].ptr, nb))
                 n = count_of(pb[1], n + 2)
                 sp, so = pb[1], pb[2]
-            ocap = out_capacity if out_capacity is not None else n + 2
+            ocap = out_capacity if out_capacity is not None and not rules else n + 2
             nb = self.lib.acm_sequence_workspace_bytes(self.dfa, n)
             qb = [DeviceArray(max(nb, 16)), DeviceArray(ocap * 4), DeviceArray(ocap * 4)]
             bufs += qb
             self.sequence_async(sp, so, n, qb[1], qb[2], ocap, info, seg_start=d_st, segments=nseg,
                                 lead_begin=int(lead_begin), text_end=int(t.size), workspace=(qb[0].ptr, nb))
             m = count_of(qb[1], ocap)
+            if rules:
+                rcap = out_capacity if out_capacity is not None else m + 2
+                nb = self.lib.acm_rule_workspace_bytes(self.dfa, m)
+                rb = [DeviceArray(max(nb, 16))] + [DeviceArray(rcap * 4) for _ in range(3)]
+                bufs += rb
+                self.rule_async(qb[1], qb[2], m, rb[1], rb[2], rb[3], rcap, info, seg_start=d_st, segments=nseg,
+                                workspace=(rb[0].ptr, nb))
+                k = count_of(rb[1], rcap)
+                r, x, o = (b.to_numpy(np.int32, k + 2, stream=self.stream) for b in rb[1:])
+                return r[1:1 + k].copy(), x[1:1 + k].copy(), o[1:1 + k].astype(np.uint32), \
+                    info.to_numpy(np.int32, 4, stream=self.stream)
             q = qb[1].to_numpy(np.int32, m + 2, stream=self.stream)
             o = qb[2].to_numpy(np.int32, m + 2, stream=self.stream)
             ends = o[1:1 + m].astype(np.uint32)
@@ -1115,6 +1179,39 @@ class Matcher:
         finally:
             for b in bufs:
                 b.free()
+
+    def rule_async(self, seq_plane, off_plane, max_records, rule_out, text_out, off_out, out_capacity, info, seg_start=None,
+                   segments=0, workspace=None, stream=None):
+        """Enqueue the rule pass (acm_rule_matches_async) over caller-owned device planes of sequence indices
+        and end offsets (the output of sequence_async): one record (rule index, text index or -1 for the lead
+        text, offset of the trigger) per (rule, text) whose expression is true (Automaton.add_rule).  info: device
+        int32[4].  The pass orders max_records cells: size it to the planes.  workspace: (ptr, nbytes), or None
+        for a temporary one that lives until the stream has passed it (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        tmp = None
+        if workspace is None:
+            nb = self.lib.acm_rule_workspace_bytes(self.dfa, max_records)
+            tmp = DeviceArray(max(nb, 16))
+            workspace = (tmp.ptr, nb)
+        try:
+            check(self.lib.acm_rule_matches_async(
+                self.dfa, _ptr(seq_plane), _ptr(off_plane), max_records, _ptr(seg_start), segments, _ptr(rule_out),
+                _ptr(text_out), _ptr(off_out), out_capacity, _ptr(info), _ptr(workspace[0]), workspace[1], st),
+                "acm_rule_matches_async")
+        finally:
+            if tmp is not None:
+                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
+                tmp.free()
+
+    def scan_rules(self, text=None, texts=None, lead_begin=0, init_state=0, before=b"", out_capacity=None):
+        """The automaton's rules that hold (Automaton.add_rule, add_logical_signature): everything scan_sequences
+        runs, then the rule pass (acm_rule_matches_async) over the sequence pass's planes.  text: host bytes, one
+        text (index -1); or None with texts, as scan_sequences takes them: each text is matched and counted
+        alone.  Returns (rules, texts, offsets, info): a record per (rule, text) whose expression is true, text
+        by text: the rule index, the text index and the offset of the trigger record (with wildcard
+        signatures: the end of its last part's anchor); info: [records that are an operand, (operand, text)
+        pairs, (rule, text) pairs evaluated, 0].  Counts are not carried across calls: scan whole texts."""
+        return self._sequences(text, texts, lead_begin, init_state, before, out_capacity, True)
 
     def tally_async(self, pat_plane, off_plane, max_records, class_total, report=0, all_patterns=False,
                     accumulate=False, class_of=None, num_classes=None, seg_start=None, segments=0, seg_class=None,

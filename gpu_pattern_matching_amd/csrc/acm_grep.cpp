@@ -103,7 +103,20 @@ double now_us()
 	       "                 the positions around it are checked on the device where it matched.  A candidate whose\n"
 	       "                 positions reach over a buffer border is not decided: such candidates are counted and\n"
 	       "                 reported on stderr at exit.  Composes with -i, -I, -S and -P (a window counts from a part's\n"
-	       "                 first position) (extension; needs -Q, not with -W)\n"
+	       "                 first position) (extension; needs -Q or -K, not with -W)\n"
+	       "  -K file        rules, one logical signature per line: 'expr;body0;body1;...' with an optional leading\n"
+	       "                 '<decimal id>:' -- a ClamAV .ldb line without its name and target fields.  A body is a\n"
+	       "                 signature as -Q takes it (with -E: in the extended syntax); expr is a condition over the\n"
+	       "                 bodies' hits in ONE text, operand j being body j: '&' and '|' (never mixed at one level\n"
+	       "                 without parentheses), '(..)' and '=n', '>n', '<n' behind an operand or a group, whose count\n"
+	       "                 is the sum of its operands' hits: '(0&1)|2>3', '0&1=0'.  Needs -S: the texts are the files\n"
+	       "                 (with -t: the lines).  Beside or instead of -p / -Q.  The conditions are evaluated on the\n"
+	       "                 device; what is printed and counted are the rules that hold: the -v line is \"Rule <id>\n"
+	       "                 matched in file '<path>' [text at offset <t>]\", t the text's start in its file.  A text\n"
+	       "                 cut by a buffer is NOT evaluated -- the text a buffer begins in the middle of, and a\n"
+	       "                 buffer's last text when its file goes on: the number of such texts is printed on stderr\n"
+	       "                 at exit; use a larger -G/-B.  The pass orders the same cells as -Q.  Composes with -i, -I,\n"
+	       "                 -P, -E and -t (extension; not with -c, -n, -W, -A or -F)\n"
 	       "  -S             every input unit is its own text: a file, or with -t a line; no match\n"
 	       "                 spans two of them (extension; data appended under -F continues its file\n"
 	       "                 when the worker's previous chunk came from the same file)\n"
@@ -157,13 +170,14 @@ std::vector<std::string> regular_files_in(std::string dir)
 }
 
 struct Config {
-	std::string pat_path, data_path, loose_path, pos_path, seq_path;   // loose_path: -I, pos_path: -P, seq_path: -Q
+	std::string pat_path, data_path, loose_path, pos_path, seq_path, rule_path;   // loose_path: -I, pos_path: -P, seq_path: -Q, rule_path: -K
 	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0,
 	    words = 0, count = 0, lineno = 0;
 	int cased = 0;           // -I without -i: the records go through the case pass
 	int pos = 0;             // -P: the records go through the position pass
 	int seq = 0;             // -Q: every pattern of the records goes through the sequence pass; its records are reported
-	int ext = 0;             // -E: the signatures of -Q are read in the extended syntax
+	int ext = 0;             // -E: the signatures of -Q and the bodies of -K are read in the extended syntax
+	int rules = 0;           // -K: the sequence pass's records go through the rule pass; its records are reported (seq is set too)
 	int wild = 0;            // -E and some part has a context: the parts' records go through the wildcard pass
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
@@ -179,6 +193,7 @@ struct Shared {
 	std::vector<int> pat_iid;
 	std::vector<int> seq_iid;             // -Q: the id of every sequence, for the -v line
 	std::vector<int> seq_post;            // -E: the post context of every sequence's last part: a match ends that far behind its record
+	std::vector<int> rule_iid;            // -K: the id of every rule, for the -v line
 	int max_pattern_len = 0;
 	pthread_mutex_t print_lock = PTHREAD_MUTEX_INITIALIZER;
 	pthread_barrier_t ready;   // workers have their buffers; the clock starts (the reference
@@ -215,6 +230,13 @@ struct Buffer {   // one of the two staging buffers of a worker
 	// -Q only: the sequence pass's planes, workspace and info; seq_max: the pattern-form records it takes
 	void *d_seq_pat = nullptr, *d_seq_off = nullptr, *d_seq_ws = nullptr, *d_seq_info = nullptr;
 	size_t seq_ws_bytes = 0, seq_max = 0;
+	// -K only: the rule pass's planes (rule, text, offset: seq_max + 2 cells each), workspace and info; the pinned
+	// count, and the records as collect() copies them back
+	void *d_rule_out = nullptr, *d_rule_text = nullptr, *d_rule_off = nullptr, *d_rule_ws = nullptr, *d_rule_info = nullptr;
+	int32_t *h_rule_count = nullptr;
+	std::vector<int32_t> h_rule, h_rule_text;
+	size_t rule_ws_bytes = 0;
+	std::vector<long> file_off;  // -K: where every chunk begins in its file
 	// -E only: the wildcard pass's planes, workspace and info (pinned twin: [0] = undecided entries, [4] = records written)
 	void *d_wild_pat = nullptr, *d_wild_off = nullptr, *d_wild_ws = nullptr, *d_wild_info = nullptr;
 	int32_t *h_wild_info = nullptr;
@@ -264,6 +286,8 @@ struct Worker {
 	bool file_closed = false; // -P: the file of the last chunk filled has been read to its end
 	uint64_t undecided = 0;   // -P: end-anchored entries dropped because their text went on in the next buffer
 	uint64_t wild_undecided = 0;   // -E: candidates whose positions reach over a buffer border
+	uint64_t cut_texts = 0;   // -K: texts that go on in the next buffer: not evaluated
+	long file_pos = 0;        // -K: bytes of the file being read that the buffers filled so far hold
 	void *d_tail[2] = { nullptr, nullptr };   // -W, -I: the last max_pattern_len bytes of the stream so far, ping-pong
 	int tail_cur = 0;
 	size_t tail_len = 0;
@@ -374,11 +398,12 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 
 // binary mode: fixed chunks, a short tail chunk per file (databuf.c:326-407)
 // returns bytes read (0 = nothing available right now)
-size_t fill_binary(Buffer &b, const Config &c, int fd, int file_id)
+size_t fill_binary(Buffer &b, const Config &c, int fd, int file_id, long *file_pos)
 {
 	const size_t G = (size_t)c.global_ws, B = (size_t)c.chunk;
 	if (b.chunks >= G)
 		return 0;
+	b.file_off.resize(G + 1);
 	const ssize_t got = read(fd, b.h_data + b.chunks * B, (G - b.chunks) * B);
 	if (got <= 0)
 		return 0;
@@ -388,6 +413,8 @@ size_t fill_binary(Buffer &b, const Config &c, int fd, int file_id)
 		b.h_indices[b.chunks] = (int32_t)(b.chunks * B);
 		b.h_sizes[b.chunks] = (int32_t)take;
 		b.file_ids[b.chunks] = file_id;
+		b.file_off[b.chunks] = *file_pos;
+		*file_pos += (long)take;
 		b.chunks++;
 		left -= take;
 	}
@@ -396,10 +423,11 @@ size_t fill_binary(Buffer &b, const Config &c, int fd, int file_id)
 }
 
 // text mode: one chunk per line, 16-byte aligned, gaps zeroed (databuf.c:412-481)
-size_t fill_text(Buffer &b, const Config &c, FILE *fp, int file_id, size_t *lines)
+size_t fill_text(Buffer &b, const Config &c, FILE *fp, int file_id, size_t *lines, long *file_pos)
 {
 	const size_t G = (size_t)c.global_ws, B = (size_t)c.chunk, size = G * B;
 	size_t total = 0;
+	b.file_off.resize(G + 1);
 	while (b.chunks < G && b.bytes < size) {
 		const size_t room = std::min(size - b.bytes, B);
 		if (room < 2)
@@ -413,6 +441,8 @@ size_t fill_text(Buffer &b, const Config &c, FILE *fp, int file_id, size_t *line
 		b.h_indices[b.chunks] = (int32_t)b.bytes;
 		b.h_sizes[b.chunks] = (int32_t)len;
 		b.file_ids[b.chunks] = file_id;
+		b.file_off[b.chunks] = *file_pos;
+		*file_pos += (long)len;
 		b.chunks++;
 		const size_t adv = std::min((len + 15) & ~(size_t)15, size - b.bytes);
 		memset(dst + len, 0, adv - len);
@@ -645,6 +675,15 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		off = (int32_t *)b.d_seq_off;
 		cap = b.seq_max + 2;
 	}
+	if (c.rules) {
+		// the rules: the signatures' records counted per text and the conditions evaluated on the device.  Only the
+		// count comes back here; collect() fetches that many records.  (The bucket planes below keep carrying the
+		// signatures' records: the scan state of the next buffer comes from their trailer.)
+		CK(acm_rule_matches_async(w.dfa, pat, off, b.seq_max, (const int32_t *)b.d_seg_start, b.seg_starts.size(),
+		    (int32_t *)b.d_rule_out, (int32_t *)b.d_rule_text, (int32_t *)b.d_rule_off, b.seq_max + 2, (int32_t *)b.d_rule_info,
+		    b.d_rule_ws, b.rule_ws_bytes, s));
+		CK(acm_rt_memcpy_d2h(b.h_rule_count, b.d_rule_out, 4, s));
+	}
 	if (c.lineno) {
 		// the lines of this buffer's stream, chained to the buffer in front of it on the device; then the
 		// newlines in front of every record and of every file start, in stream coordinates (before the remap)
@@ -698,6 +737,44 @@ void finish(Worker &w, Buffer &b, int next_byte)
 	CK(acm_rt_event_record(b.done, s));
 }
 
+// -K: the rule pass's planes copied back directly -- the count came with the buffer, the records now -- and the
+// records of the texts this buffer holds whole reported.  The text in front of the first start began in an
+// earlier buffer, and the last text goes on unless its end is known: their records are dropped.
+void collect_rules(Worker &w, Buffer &b)
+{
+	const Config &c = w.sh->cfg;
+	const size_t n = std::min((size_t)std::max(*b.h_rule_count, 0), b.seq_max), S = b.seg_starts.size();
+	if (!b.end_known && S > 0)   // (S == 0: the whole buffer lies inside a text that was counted when it was cut first)
+		w.cut_texts++;
+	if (n == 0)
+		return;
+	b.h_rule.resize(n);
+	b.h_rule_text.resize(n);
+	CK(acm_rt_memcpy_d2h(b.h_rule.data(), (const int32_t *)b.d_rule_out + 1, n * 4, w.stream));
+	CK(acm_rt_memcpy_d2h(b.h_rule_text.data(), (const int32_t *)b.d_rule_text + 1, n * 4, w.stream));
+	CK(acm_rt_stream_sync(w.stream));
+	for (size_t j = 0; j < n; j++) {
+		const int32_t r = b.h_rule[j], k = b.h_rule_text[j];
+		if (k < 0 || (size_t)k >= S || r < 0 || (size_t)r >= w.sh->rule_iid.size())   // the lead text: cut
+			continue;
+		if ((size_t)k + 1 == S && !b.end_known)   // the last text goes on in the next buffer: cut
+			continue;
+		w.matches++;
+		w.reported++;
+		if (!c.verbose)
+			continue;
+		// a text begins with a chunk: the chunk whose stream offset is the text's start
+		const size_t i = (size_t)(std::lower_bound(b.starts.begin(), b.starts.begin() + (long)b.chunks, b.seg_starts[(size_t)k]) -
+		                          b.starts.begin());
+		if (i >= b.chunks)
+			continue;
+		pthread_mutex_lock(&w.sh->print_lock);
+		printf("Rule %d matched in file '%s' [text at offset %ld]\n", w.sh->rule_iid[(size_t)r], w.sh->files[b.file_ids[i]].c_str(),
+		    b.file_off[i]);
+		pthread_mutex_unlock(&w.sh->print_lock);
+	}
+}
+
 // wait for the buffer, walk the bucket planes (databuf.c:747-782), print -v lines
 void collect(Worker &w, Buffer &b)
 {
@@ -731,6 +808,13 @@ void collect(Worker &w, Buffer &b)
 	const size_t chunks = b.chunks;
 	const int R = c.max_results;
 	w.last_state = b.h_results[chunks * R];
+	if (c.rules) {
+		collect_rules(w, b);
+		b.chunks = 0;
+		b.bytes = 0;
+		w.rounds++;
+		return;
+	}
 	long k_start = -1;   // -n: the file start the chunk lies behind (-1: its file began in an earlier buffer)
 	if (c.lineno)
 		w.lines += (size_t)b.h_line_info[1];
@@ -809,6 +893,16 @@ void *worker_main(void *arg)
 			CK(acm_rt_malloc(&b.d_seq_off, (b.seq_max + 2) * 4));
 			CK(acm_rt_malloc(&b.d_seq_ws, b.seq_ws_bytes));
 			CK(acm_rt_malloc(&b.d_seq_info, 16));
+			if (c.rules) {
+				b.rule_ws_bytes = acm_rule_workspace_bytes(w.dfa, b.seq_max);
+				CK(acm_rt_malloc(&b.d_rule_out, (b.seq_max + 2) * 4));
+				CK(acm_rt_malloc(&b.d_rule_text, (b.seq_max + 2) * 4));
+				CK(acm_rt_malloc(&b.d_rule_off, (b.seq_max + 2) * 4));
+				CK(acm_rt_malloc(&b.d_rule_ws, b.rule_ws_bytes));
+				CK(acm_rt_malloc(&b.d_rule_info, 16));
+				CK(acm_rt_host_alloc((void **)&b.h_rule_count, 64));
+				*b.h_rule_count = 0;
+			}
 			if (c.wild) {
 				b.wild_ws_bytes = acm_wildcard_workspace_bytes(b.all_cap);
 				CK(acm_rt_malloc(&b.d_wild_pat, b.all_cap * 4));
@@ -857,9 +951,9 @@ void *worker_main(void *arg)
 		Buffer &b = w.buf[filling];
 		size_t got, lines = 0;
 		if (c.text_mode)
-			got = fill_text(b, c, fp, cur, &lines);
+			got = fill_text(b, c, fp, cur, &lines, &w.file_pos);
 		else
-			got = fill_binary(b, c, sh.fds[cur], cur);
+			got = fill_binary(b, c, sh.fds[cur], cur, &w.file_pos);
 		w.bytes += got;
 		w.lines += lines;
 		if (got)
@@ -868,6 +962,7 @@ void *worker_main(void *arg)
 		bool file_done = (got == 0) && !full;
 		if (file_done) {   // current file exhausted: next one of this worker
 			w.file_closed = true;
+			w.file_pos = 0;
 			if (!c.follow) {
 				if (fp) {
 					fclose(fp);
@@ -889,6 +984,21 @@ void *worker_main(void *arg)
 		if (b.chunks > 0 && (full || last || (c.follow && file_done))) {
 			// the scan starts in the state the previous buffer ended in: taken from that buffer's planes on
 			// the device, so this one is enqueued BEFORE the host waits for the previous one and walks its results
+			if (c.rules && !w.file_closed && cur < nfiles) {
+				// -K: a buffer filled to its end with a file's last bytes: the text is whole, not cut
+				if (fp) {
+					const int ch = fgetc(fp);
+					if (ch == EOF)
+						w.file_closed = true;
+					else
+						ungetc(ch, fp);
+				} else {
+					struct stat st;
+					const off_t at = lseek(sh.fds[cur], 0, SEEK_CUR);
+					if (at >= 0 && fstat(sh.fds[cur], &st) == 0 && S_ISREG(st.st_mode) && at >= st.st_size)
+						w.file_closed = true;
+				}
+			}
 			prepare(w, b);
 			b.last_of_input = last;
 			if (in_flight && c.words)   // b's first byte ends the previous buffer's stream
@@ -924,7 +1034,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:E")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -960,11 +1070,13 @@ int main(int argc, char **argv)
 		case 'P': c.pos_path = optarg; break;
 		case 'Q': c.seq_path = optarg; break;
 		case 'E': c.ext = 1; break;
+		case 'K': c.rule_path = optarg; break;
 		default: usage();
 		}
 	}
 	int err = 0;   // check_args, ocl_aho_grep.c:210-266
-	c.seq = !c.seq_path.empty();
+	c.rules = !c.rule_path.empty();
+	c.seq = !c.seq_path.empty() || c.rules;   // (-K: the rule pass takes the sequence pass's records)
 	if (c.pat_path.empty() && !c.seq) { printf("ERROR: No pattern file\n"); err++; }
 	else if (!c.pat_path.empty() && access(c.pat_path.c_str(), R_OK) != 0) {
 		printf("ERROR: File '%s' does not exist\n", c.pat_path.c_str()); err++;
@@ -1002,15 +1114,29 @@ int main(int argc, char **argv)
 		err++;
 	}
 	c.pos = !c.pos_path.empty();
-	if (c.seq && access(c.seq_path.c_str(), R_OK) != 0) {
+	if (!c.seq_path.empty() && access(c.seq_path.c_str(), R_OK) != 0) {
 		printf("ERROR: File '%s' does not exist\n", c.seq_path.c_str()); err++;
 	}
-	if (c.seq && (c.count || c.lineno || c.words || c.all_patterns)) {   // the records are sequence matches, not patterns
+	if (c.rules && access(c.rule_path.c_str(), R_OK) != 0) {
+		printf("ERROR: File '%s' does not exist\n", c.rule_path.c_str()); err++;
+	}
+	if (c.rules && (c.count || c.lineno || c.words || c.all_patterns)) {   // the records are rules that hold, not patterns
+		printf("ERROR: -K cannot be combined with -c, -n, -W or -A: the records of -K are rules that hold\n");
+		err++;
+	} else if (c.seq && (c.count || c.lineno || c.words || c.all_patterns)) {   // the records are sequence matches, not patterns
 		printf("ERROR: -Q cannot be combined with -c, -n, -W or -A: the records of -Q are signature matches\n");
 		err++;
 	}
+	if (c.rules && !c.segmented) {   // a condition counts the hits of one text: the texts must be told apart
+		printf("ERROR: -K needs -S: a rule is a condition over the hits in one file (with -t: in one line)\n");
+		err++;
+	}
+	if (c.rules && c.follow) {
+		printf("ERROR: -K cannot be combined with -F: the end of a paused input is not known\n");
+		err++;
+	}
 	if (c.ext && !c.seq) {
-		printf("ERROR: -E needs -Q: it is the syntax of the signature file\n");
+		printf("ERROR: -E needs -Q or -K: it is the syntax of the signature file\n");
 		err++;
 	}
 	if (c.ext && c.words) {
@@ -1085,9 +1211,18 @@ int main(int argc, char **argv)
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}
-	if (c.seq && acm_automaton_load_signature_file_ex(aut, c.seq_path.c_str(), 0, c.ext ? ACM_SIG_EXTENDED : 0) < 0) {
+	if (!c.seq_path.empty() && acm_automaton_load_signature_file_ex(aut, c.seq_path.c_str(), 0, c.ext ? ACM_SIG_EXTENDED : 0) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
+	}
+	if (c.rules && acm_automaton_load_logical_file(aut, c.rule_path.c_str(), 0, c.ext ? ACM_SIG_EXTENDED : 0) < 0) {
+		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
+		return 1;
+	}
+	for (int i = 0; i < acm_automaton_num_rules(aut); i++) {
+		int iid = 0;
+		acm_automaton_rule(aut, i, &iid, nullptr, nullptr, nullptr);
+		sh.rule_iid.push_back(iid);
 	}
 	c.wild = c.ext && acm_automaton_wildcards(aut);
 	for (int i = 0; i < acm_automaton_num_sequences(aut); i++) {
@@ -1141,11 +1276,12 @@ int main(int argc, char **argv)
 	pthread_barrier_wait(&sh.ready);
 	const double t0 = now_us();
 	size_t matches = 0, reported = 0, bytes = 0, lines = 0, rounds = 0;
-	uint64_t undecided = 0, wild_undecided = 0;
+	uint64_t undecided = 0, wild_undecided = 0, cut_texts = 0;
 	for (auto &w : workers) {
 		pthread_join(w.thread, nullptr);
 		undecided += w.undecided;
 		wild_undecided += w.wild_undecided;
+		cut_texts += w.cut_texts;
 		matches += w.matches;
 		reported += w.reported;
 		bytes += w.bytes;
@@ -1185,6 +1321,9 @@ int main(int argc, char **argv)
 	if (wild_undecided)   // no silent loss: a signature cut by a buffer border is not found, and here that is known
 		fprintf(stderr, "NOTE: %lu wildcard candidates reach over a buffer border and were not decided (raise -B/-G)\n",
 		    (unsigned long)wild_undecided);
+	if (cut_texts)   // no silent loss: the rules of these texts were not evaluated
+		fprintf(stderr, "NOTE: %lu texts are cut by a buffer border and their rules were not evaluated (use a larger -G/-B)\n",
+		    (unsigned long)cut_texts);
 	if (undecided) {   // no silent loss: the counts and records above are without them
 		printf("ERROR: %lu end-anchored candidates lie in files that span buffers (raise -B/-G)\n", (unsigned long)undecided);
 		return 1;

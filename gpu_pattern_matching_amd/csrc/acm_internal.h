@@ -33,6 +33,18 @@ constexpr uint32_t kHotBytes = kHotRowsMax * 512;
 constexpr uint32_t kHotSentinel = 0xFFFFu;    // hot cell value meaning "look in the cold plane"
 constexpr uint32_t kNoPattern = 0xFFFFFFFFu;
 
+// the postfix program of a rule (acm_automaton_add_rule; run by rule.hip): {op, argument} pairs.  A program of
+// nesting d needs a stack of d + 2 entries: binary operators, left to right.
+enum RuleOp : int32_t {
+	kRulePush = 0,   // push operand `argument`: its count, and count > 0
+	kRuleAnd = 1,    // pop b, a; push {a.count + b.count, a.truth && b.truth}
+	kRuleOr = 2,     //                                  ... a.truth || b.truth
+	kRuleEq = 3,     // the top's truth becomes count == argument
+	kRuleGt = 4,     //                         count > argument
+	kRuleLt = 5,     //                         count < argument
+};
+constexpr int kRuleStack = ACM_RULE_MAX_NESTING + 2;
+
 }  // namespace acm
 
 // Host automaton.  States carry two numberings:
@@ -74,8 +86,18 @@ struct acm_automaton {
 	struct Sequence {
 		int iid;
 		std::vector<int32_t> parts, gap_lo, gap_hi;   // gaps: parts.size() - 1 cells, gap j - 1 in front of part j
+		int32_t rule = -1, rule_op = 0;               // the rule this sequence is an operand of (acm_automaton_add_rule), or -1
 	};
 	std::vector<Sequence> sequences;
+	// conditions over the sequences that hit one text (acm_automaton_add_rule).  compile never reads these:
+	// acm_dfa_upload copies them for the rule pass (rule.hip)
+	struct Rule {
+		int iid;
+		std::vector<int32_t> sequences;   // the operands
+		std::string expr;                 // as given
+		std::vector<int32_t> code;        // the postfix program: {op, argument} pairs (acm::RuleOp)
+	};
+	std::vector<Rule> rules;
 	std::vector<Pattern> patterns;         // bytes folded by compile when nocase: every table is built from these
 	int max_pattern_len = 0;
 	bool compiled = false;

@@ -751,6 +751,345 @@ extern "C" int acm_automaton_load_signature_file_ex(acm_automaton *a, const char
 	return load_signature_file("acm_automaton_load_signature_file_ex", a, path, flags, syntax);
 }
 
+// ---- rules -------------------------------------------------------------------------
+
+namespace {
+
+// A rule's expression, compiled to its postfix program (acm::RuleOp).  Recursive descent over
+//   expr := term ( '&' term )*  |  term ( '|' term )*
+//   term := ( NUMBER | '(' expr ')' ) [ ( '=' | '>' | '<' ) NUMBER ]
+// The first error stops it: code (ACM_ERR_PARSE or ACM_ERR_LIMIT), col (from 1) and why.
+struct RuleParser {
+	const char *s;
+	int nops;
+	std::vector<int32_t> &code;
+	size_t i = 0;
+	int err = 0, col = 0;
+	const char *why = "";
+
+	bool bad(int code_, size_t at, const char *w)
+	{
+		err = code_;
+		col = (int)at + 1;
+		why = w;
+		return false;
+	}
+	void blanks()
+	{
+		while (s[i] == ' ' || s[i] == '\t')
+			i++;
+	}
+	// digits at s[i], at most INT32_MAX
+	bool number(int64_t &v)
+	{
+		const size_t at = i;
+		for (v = 0; isdigit((unsigned char)s[i]); i++)
+			if ((v = v * 10 + (s[i] - '0')) > INT32_MAX)
+				return bad(ACM_ERR_PARSE, at, "number too large");
+		return true;
+	}
+	bool term(int depth)
+	{
+		blanks();
+		const size_t at = i;
+		if (isdigit((unsigned char)s[i])) {
+			int64_t op;
+			if (!number(op))
+				return false;
+			if (op >= nops)
+				return bad(ACM_ERR_PARSE, at, "operand out of range");
+			code.insert(code.end(), { acm::kRulePush, (int32_t)op });
+		} else if (s[i] == '(') {
+			if (depth + 1 > ACM_RULE_MAX_NESTING)
+				return bad(ACM_ERR_LIMIT, at, "parentheses nested too deep");
+			i++;
+			if (!expr(depth + 1))
+				return false;
+			blanks();
+			if (s[i] != ')')
+				return bad(ACM_ERR_PARSE, i, "expected )");
+			i++;
+		} else {
+			return bad(ACM_ERR_PARSE, at, "expected an operand or (");
+		}
+		blanks();
+		if (s[i] == '=' || s[i] == '>' || s[i] == '<') {
+			const int32_t op = s[i] == '=' ? acm::kRuleEq : s[i] == '>' ? acm::kRuleGt : acm::kRuleLt;
+			i++;
+			blanks();
+			if (!isdigit((unsigned char)s[i]))
+				return bad(ACM_ERR_PARSE, i, "expected a number");
+			int64_t n;
+			if (!number(n))
+				return false;
+			if (s[i] == ',')
+				return bad(ACM_ERR_PARSE, i, "the distinct-count form =n,m is not provided");
+			code.insert(code.end(), { op, (int32_t)n });
+		}
+		return true;
+	}
+	bool expr(int depth)
+	{
+		if (!term(depth))
+			return false;
+		blanks();
+		const char op = s[i];
+		if (op != '&' && op != '|')
+			return true;
+		while (s[i] == op) {
+			i++;
+			if (!term(depth))
+				return false;
+			code.insert(code.end(), { op == '&' ? acm::kRuleAnd : acm::kRuleOr, 0 });
+			blanks();
+		}
+		if (s[i] == '&' || s[i] == '|')
+			return bad(ACM_ERR_PARSE, i, "& and | at one level without parentheses");
+		return true;
+	}
+	bool all()
+	{
+		if (!expr(0))
+			return false;
+		blanks();
+		if (s[i])
+			return bad(ACM_ERR_PARSE, i, "unexpected character");
+		return true;
+	}
+};
+
+// the program over counts that are all 0: is the expression true for a text without a hit?
+bool rule_true_when_empty(const std::vector<int32_t> &code)
+{
+	std::vector<std::pair<int64_t, bool>> st;
+	for (size_t k = 0; k + 1 < code.size(); k += 2) {
+		const int32_t op = code[k], arg = code[k + 1];
+		if (op == acm::kRulePush) {
+			st.push_back({ 0, false });
+		} else if (op == acm::kRuleAnd || op == acm::kRuleOr) {
+			const auto b = st.back();
+			st.pop_back();
+			auto &a = st.back();
+			a.first += b.first;
+			a.second = op == acm::kRuleAnd ? (a.second && b.second) : (a.second || b.second);
+		} else {
+			auto &a = st.back();
+			a.second = op == acm::kRuleEq ? a.first == arg : op == acm::kRuleGt ? a.first > arg : a.first < arg;
+		}
+	}
+	return !st.empty() && st.back().second;
+}
+
+// compiles expr over nops operands; on an error sets acm_last_error with the column shifted by col0
+int compile_rule(const char *where, const char *expr, int nops, int col0, std::vector<int32_t> &code)
+{
+	code.clear();
+	RuleParser p{ expr, nops, code };
+	if (!p.all())
+		return acm::fail(p.err, "%s: column %d: %s", where, col0 + p.col, p.why);
+	if (rule_true_when_empty(code))
+		return acm::fail(ACM_ERR_ARG, "%s: the expression is true for a text without any hit", where);
+	return ACM_OK;
+}
+
+int rule_operand_count(const char *fn, int nops)
+{
+	if (nops < 1)
+		return acm::fail(ACM_ERR_ARG, "%s: %d operands", fn, nops);
+	if (nops > ACM_RULE_MAX_OPERANDS)
+		return acm::fail(ACM_ERR_LIMIT, "%s: %d operands, at most %d", fn, nops, ACM_RULE_MAX_OPERANDS);
+	return ACM_OK;
+}
+
+// registers a compiled rule over sequences that are free: cannot fail but for memory
+int apply_rule(acm_automaton *a, const int32_t *sequences, int nops, const char *expr, std::vector<int32_t> code, int iid)
+{
+	acm_automaton::Rule r;
+	r.iid = iid;
+	r.sequences.assign(sequences, sequences + nops);
+	r.expr = expr;
+	r.code = std::move(code);
+	const int index = (int)a->rules.size();
+	a->rules.push_back(std::move(r));
+	for (int j = 0; j < nops; j++) {
+		a->sequences[sequences[j]].rule = index;
+		a->sequences[sequences[j]].rule_op = j;
+	}
+	return index;
+}
+
+// a logical signature, parsed: "expr;body0;body1;..."
+struct Logical {
+	std::string expr;
+	std::vector<int32_t> code;
+	std::vector<Signature> bodies;
+	int iid = 0;
+	bool has_iid = false;
+};
+
+// parses line (its first byte is column col0 + 1 of what the caller shows); where: the prefix of the message
+int parse_logical(const char *where, const char *line, int col0, unsigned syntax, Logical &out)
+{
+	const char *semi = strchr(line, ';');
+	if (!semi)
+		return acm::fail(ACM_ERR_PARSE, "%s: column %d: no ';' and subsignature behind the expression", where,
+		    col0 + (int)strlen(line) + 1);
+	out.expr.assign(line, semi);
+	out.bodies.clear();
+	for (const char *b = semi + 1;;) {
+		const char *e = strchr(b, ';');
+		const std::string body = e ? std::string(b, e) : std::string(b);
+		const int at = col0 + (int)(b - line);
+		if (const size_t colon = body.find(':'); colon != std::string::npos)
+			return acm::fail(ACM_ERR_PARSE, "%s: column %d: subsignature offsets and modifiers are not supported", where,
+			    at + (int)colon + 1);
+		Signature sig;
+		const char *why = "";
+		if (const int col = (syntax & ACM_SIG_EXTENDED) ? parse_signature_ex(body.c_str(), sig, why)
+		                                                : parse_signature(body.c_str(), sig, why))
+			return acm::fail(ACM_ERR_PARSE, "%s: column %d: %s", where, at + col, why);
+		out.bodies.push_back(std::move(sig));
+		if (!e)
+			break;
+		b = e + 1;
+	}
+	if (int rc = rule_operand_count(where, (int)out.bodies.size()))
+		return rc;
+	return compile_rule(where, out.expr.c_str(), (int)out.bodies.size(), col0, out.code);
+}
+
+// adds the bodies and the rule of parsed logical signatures: cannot fail but for memory, once they fit
+int apply_logical(acm_automaton *a, const Logical &l, int iid, unsigned flags)
+{
+	std::vector<int32_t> seqs;
+	for (const Signature &sig : l.bodies) {
+		const int q = apply_signature(a, sig, iid, flags);
+		if (q < 0)
+			return q;
+		seqs.push_back(q);
+	}
+	return apply_rule(a, seqs.data(), (int)seqs.size(), l.expr.c_str(), l.code, iid);
+}
+
+bool logicals_fit(const acm_automaton *a, const std::vector<Logical> &ls)
+{
+	std::vector<Signature> all;
+	for (const Logical &l : ls)
+		all.insert(all.end(), l.bodies.begin(), l.bodies.end());
+	return signatures_fit(a, all.data(), all.size());
+}
+
+}  // namespace
+
+extern "C" int acm_automaton_add_rule(acm_automaton *a, const int32_t *sequences, int nops, const char *expr, int iid)
+{
+	const char *fn = "acm_automaton_add_rule";
+	if (!a || !sequences || !expr)
+		return acm::fail(ACM_ERR_ARG, "%s: bad arguments", fn);
+	if (int rc = rule_operand_count(fn, nops))
+		return rc;
+	if (a->rules.size() >= (size_t)INT32_MAX)
+		return acm::fail(ACM_ERR_LIMIT, "%s: too many rules", fn);
+	for (int j = 0; j < nops; j++) {
+		const int32_t q = sequences[j];
+		if (q < 0 || q >= (int)a->sequences.size())
+			return acm::fail(ACM_ERR_ARG, "%s: operand %d: sequence index %d out of range", fn, j, q);
+		if (a->sequences[q].rule >= 0)
+			return acm::fail(ACM_ERR_ARG, "%s: operand %d: sequence %d is an operand of rule %d", fn, j, q, a->sequences[q].rule);
+		for (int i = 0; i < j; i++)
+			if (sequences[i] == q)
+				return acm::fail(ACM_ERR_ARG, "%s: sequence %d is operand %d and operand %d", fn, q, i, j);
+	}
+	std::vector<int32_t> code;
+	if (int rc = compile_rule(fn, expr, nops, 0, code))
+		return rc;
+	return apply_rule(a, sequences, nops, expr, std::move(code), iid);
+}
+
+extern "C" int acm_automaton_num_rules(const acm_automaton *a) { return a ? (int)a->rules.size() : 0; }
+
+extern "C" int acm_automaton_rule(const acm_automaton *a, int index, int *iid, int *nops, const int32_t **sequences,
+    const char **expr)
+{
+	if (!a || index < 0 || index >= (int)a->rules.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_rule: index out of range");
+	const acm_automaton::Rule &r = a->rules[index];
+	if (iid) *iid = r.iid;
+	if (nops) *nops = (int)r.sequences.size();
+	if (sequences) *sequences = r.sequences.data();
+	if (expr) *expr = r.expr.c_str();
+	return ACM_OK;
+}
+
+extern "C" int acm_automaton_sequence_rule(const acm_automaton *a, int sequence, int *rule, int *operand)
+{
+	if (!a || sequence < 0 || sequence >= (int)a->sequences.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_sequence_rule: index out of range");
+	const acm_automaton::Sequence &s = a->sequences[sequence];
+	if (s.rule < 0)
+		return 0;
+	if (rule) *rule = s.rule;
+	if (operand) *operand = s.rule_op;
+	return 1;
+}
+
+extern "C" int acm_automaton_add_logical_signature(acm_automaton *a, const char *line, int iid, unsigned flags, unsigned syntax)
+{
+	const char *fn = "acm_automaton_add_logical_signature";
+	if (int rc = sig_args(fn, a, line, flags, syntax))
+		return rc;
+	std::vector<Logical> l(1);
+	if (int rc = parse_logical("logical signature", line, 0, syntax, l[0]))
+		return rc;
+	if (!logicals_fit(a, l))
+		return acm::fail(ACM_ERR_LIMIT, "%s: more than 256 distinct context sets", fn);
+	return apply_logical(a, l[0], iid, flags);
+}
+
+extern "C" int acm_automaton_load_logical_file(acm_automaton *a, const char *path, unsigned flags, unsigned syntax)
+{
+	const char *fn = "acm_automaton_load_logical_file";
+	if (int rc = sig_args(fn, a, path, flags, syntax))
+		return rc;
+	std::ifstream in(path);
+	if (!in)
+		return acm::fail(ACM_ERR_IO, "cannot open logical signature file '%s': %s", path, strerror(errno));
+	std::vector<Logical> ls;   // applied only when the whole file has parsed
+	std::string line;
+	for (int line_no = 1; std::getline(in, line); line_no++) {
+		while (!line.empty() && (line.back() == '\n' || line.back() == '\r' || line.back() == ' ' || line.back() == '\t'))
+			line.pop_back();
+		size_t b = line.find_first_not_of(" \t");
+		if (b == std::string::npos || line[b] == '#')
+			continue;
+		Logical l;
+		size_t k = b;
+		int64_t iid = 0;
+		while (k < line.size() && isdigit((unsigned char)line[k]) && iid <= INT32_MAX)
+			iid = iid * 10 + (line[k++] - '0');
+		if (k > b && k < line.size() && line[k] == ':') {
+			if (iid > INT32_MAX)
+				return acm::fail(ACM_ERR_PARSE, "%s:%d: iid too large", path, line_no);
+			l.iid = (int)iid;
+			l.has_iid = true;
+			b = k + 1;
+		}
+		char where[320];
+		snprintf(where, sizeof(where), "%.280s:%d", path, line_no);
+		if (int rc = parse_logical(where, line.c_str() + b, (int)b, syntax, l))
+			return rc;
+		ls.push_back(std::move(l));
+	}
+	if (!logicals_fit(a, ls))
+		return acm::fail(ACM_ERR_LIMIT, "%s: '%s' needs more than 256 distinct context sets", fn, path);
+	for (const Logical &l : ls) {
+		const int rc = apply_logical(a, l, l.has_iid ? l.iid : (int)a->rules.size(), flags);
+		if (rc < 0)
+			return rc;
+	}
+	return (int)ls.size();
+}
+
 // ---- wildcard patterns -----------------------------------------------------------
 
 extern "C" int acm_automaton_add_wildcard(acm_automaton *a, const uint8_t *sets, int n, int iid, unsigned flags)

@@ -68,6 +68,13 @@ struct acm_dfa {
 	int32_t *d_seq_slot = nullptr;       // [slots][2] {slot of the part in front or -1, sequence index or -1: not the last part}
 	uint32_t seq_slots = 0, seq_levels = 0;
 	uint32_t seq_level_base[ACM_SEQ_MAX_PARTS + 1] = { 0 };   // slots [base[j], base[j + 1]) are level j
+	// an automaton with rules only (acm_automaton_add_rule before upload), for the rule pass (rule.hip); null
+	// otherwise.  A SLOT is an operand of a rule; slots are numbered rule-major.
+	int32_t *d_rule_ent = nullptr;       // [rule_sequences] slot of the sequence, or -1: no operand
+	int32_t *d_rule_slot = nullptr;      // [slots][2] {rule, operand}
+	int32_t *d_rule_tab = nullptr;       // [rules][4] {first slot, operands, first cell of the program in d_rule_prog, its cells}
+	int32_t *d_rule_prog = nullptr;      // [rule_prog_cells][2] the postfix programs: {acm::RuleOp, argument}
+	uint32_t rule_slots = 0, num_rules = 0, rule_sequences = 0, rule_prog_cells = 0;
 	// an automaton with wildcard contexts only (acm_automaton_wildcards at upload), for the wildcard pass
 	// (wildcard.hip); null otherwise.  The position and sequence tables above then hold the folded lengths.
 	bool wild = false;

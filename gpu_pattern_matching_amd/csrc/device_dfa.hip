@@ -316,6 +316,31 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 			rc = upload(&d->d_seq_ent, ent.data(), ent.size(), &d->device_bytes);
 			if (rc == ACM_OK) rc = upload(&d->d_seq_slot, slot.data(), slot.size(), &d->device_bytes);
 		}
+		// an automaton with rules (acm_automaton_add_rule): every operand is a slot, numbered rule by rule; per
+		// sequence its slot, per slot its rule and operand, per rule its slots and its program (rule.hip).
+		// Allocations of their own, as above.
+		if (rc == ACM_OK && !a->rules.empty()) {
+			std::vector<int32_t> ent(a->sequences.size(), -1), slot, tab, prog;
+			for (size_t r = 0; r < a->rules.size(); r++) {
+				const auto &rule = a->rules[r];
+				tab.insert(tab.end(), { (int32_t)(slot.size() / 2), (int32_t)rule.sequences.size(), (int32_t)(prog.size() / 2),
+				                          (int32_t)(rule.code.size() / 2) });
+				for (size_t j = 0; j < rule.sequences.size(); j++) {
+					ent[rule.sequences[j]] = (int32_t)(slot.size() / 2);
+					slot.push_back((int32_t)r);
+					slot.push_back((int32_t)j);
+				}
+				prog.insert(prog.end(), rule.code.begin(), rule.code.end());
+			}
+			d->rule_slots = (uint32_t)(slot.size() / 2);
+			d->num_rules = (uint32_t)a->rules.size();
+			d->rule_sequences = (uint32_t)ent.size();
+			d->rule_prog_cells = (uint32_t)(prog.size() / 2);
+			rc = upload(&d->d_rule_ent, ent.data(), ent.size(), &d->device_bytes);
+			if (rc == ACM_OK) rc = upload(&d->d_rule_slot, slot.data(), slot.size(), &d->device_bytes);
+			if (rc == ACM_OK) rc = upload(&d->d_rule_tab, tab.data(), tab.size(), &d->device_bytes);
+			if (rc == ACM_OK) rc = upload(&d->d_rule_prog, prog.data(), prog.size(), &d->device_bytes);
+		}
 		// an automaton with wildcard contexts (acm_automaton_wildcards): per pattern where its context cells lie,
 		// the cells, and the interned sets as words (wildcard.hip).  Allocations of their own, as above.
 		d->wild = acm_automaton_wildcards(a) != 0;
@@ -402,6 +427,10 @@ extern "C" void acm_dfa_release(acm_dfa *d)
 		hipFree(d->d_pos_ent);
 		hipFree(d->d_seq_ent);
 		hipFree(d->d_seq_slot);
+		hipFree(d->d_rule_ent);
+		hipFree(d->d_rule_slot);
+		hipFree(d->d_rule_tab);
+		hipFree(d->d_rule_prog);
 		hipFree(d->d_wild_ent);
 		hipFree(d->d_wild_pool);
 		hipFree(d->d_wild_sets);

@@ -17,7 +17,7 @@
 // inclusive alive-prefix.  Launches, on the record-pass grid (record_pass.h) over n = max_records cells:
 //   k_seq_key            per cell: sort key (slot, or all-ones: no part, or behind the count), its index, T0
 //                        (the tile's starts staged in LDS, as the position pass) and emit[] = 0
-//   k_seq_hist / k_seq_offsets / k_seq_scatter
+//   k_radix_hist / k_radix_offsets / k_radix_scatter   (radix_pass.h, shared with rule.hip)
 //                        one stable LSD radix pass of 8 bits: per-block digit counts, their exclusive scan in
 //                        (digit, block) order (a block per digit over the blocks' counts; the scatter adds the
 //                        digits in front), the scatter with ranks from wave ballots.  1 to 4 passes:
@@ -26,23 +26,22 @@
 //   k_seq_level<first>   per level: the alive flag of the level's range, a block count, emit[index] = 1 for an
 //                        alive record of a last part
 //   k_seq_prefix         per level: blocks_before, then the flags become the level's inclusive alive-prefix
-//   k_seq_emit<write>    the core's count and write launches over the input order: a record per emit[] cell set
+//   k_seq_emit<write>    the core's count and write launches over the input order (emit_flagged, radix_pass.h): a
+//                        record per emit[] cell set
 // 4 + 3 * passes + 2 * levels launches, whatever the planes hold.  No atomics decide an order (the LDS atomics of
-// k_seq_hist only count).  Every index that is read from memory is bounded before it is used.
+// k_radix_hist only count).  Every index that is read from memory is bounded before it is used.
 #include <hip/hip_runtime.h>
 
 #include "acm_internal.h"
 #include "device_dfa.h"
+#include "radix_pass.h"
 #include "record_pass.h"
 
 namespace {
 
 using namespace acm_rp;
 
-constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
-constexpr uint32_t kDigits = 256;
-// the radix kernels keep one digit per thread: h[tid], run[tid], wcnt[.. + tid]
-static_assert(kThreads == kDigits, "a radix pass has one thread per digit");
+constexpr uint32_t kNoSlot = kNoKey;
 
 struct SeqArgs {
 	const int32_t *pat_plane, *off_plane;   // the input: [0] the count, then the records, then the trailer
@@ -55,14 +54,11 @@ struct SeqArgs {
 	uint32_t num_patterns, slots, levels;
 	// workspace
 	int64_t *t0;                            // [n] by input index: where the record's text begins
-	uint32_t *key_in, *val_in, *key_out, *val_out;   // a radix pass; keys/vals: the ordered cells
+	uint32_t *key_in, *val_in;              // the cells as keyed; keys/vals: the ordered cells
 	const uint32_t *keys, *vals;
-	uint32_t shift;
 	int32_t *ends;                          // [n] in slot order: the record's offset
 	uint32_t *prefix;                       // [n] in slot order: alive flag, then the level's inclusive alive-prefix
 	uint32_t *emit;                         // [n] by input index: 1: an alive record of a last part
-	uint32_t *hist;                         // [gridDim.x][256]
-	uint32_t *digit_total;                  // [256] cells of each digit, of the radix pass at hand
 	uint32_t *slot_begin;                   // [slots + 1] first ordered cell of each slot; [slots]: the cells with a slot
 	int32_t *counts;                        // [gridDim.x] block counts of a two-launch step
 	uint32_t *level_total;                  // [ACM_SEQ_MAX_PARTS] alive records of each level
@@ -74,20 +70,6 @@ struct SeqArgs {
 };
 
 __device__ __forceinline__ uint32_t records_of(const SeqArgs &g) { return min((uint32_t)g.pat_plane[0], g.n); }
-
-// number of cells of the sorted a[0, n) that are < key
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *a, uint32_t n, uint32_t key)
-{
-	uint32_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (a[mid] < key)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
 
 __global__ __launch_bounds__(kThreads) void k_seq_key(SeqArgs g)
 {
@@ -132,102 +114,6 @@ __global__ __launch_bounds__(kThreads) void k_seq_key(SeqArgs g)
 			g.emit[i] = 0;
 		}
 	}
-}
-
-// ---- one stable radix pass over the n cells: digit = (key >> shift) & 255 ----
-
-__global__ __launch_bounds__(kThreads) void k_seq_hist(SeqArgs g)
-{
-	__shared__ uint32_t h[kDigits];
-
-	const uint32_t tid = threadIdx.x;
-	h[tid] = 0;
-	__syncthreads();
-	const Share sh = share_of((g.n + kTile - 1) / kTile);
-	for (uint32_t t = sh.t_begin; t < sh.t_end; t++)
-#pragma unroll
-		for (int q = 0; q < kPer; q++) {
-			const uint32_t i = t * kTile + q * kThreads + tid;
-			if (i < g.n)
-				atomicAdd(&h[(g.key_in[i] >> g.shift) & (kDigits - 1)], 1u);   // (a count: no order depends on it)
-		}
-	__syncthreads();
-	g.hist[blockIdx.x * kDigits + tid] = h[tid];
-}
-
-// A block per digit d (a grid of kDigits blocks): hist[b][d] becomes the cells of digit d in the blocks in front of
-// b, and digit_total[d] the cells of digit d; k_seq_scatter adds the cells of the digits in front.  Every block reads
-// and writes its own column only.  blocks: the grid of the other launches; a thread takes a run of them.
-__global__ __launch_bounds__(kThreads) void k_seq_offsets(SeqArgs g, uint32_t blocks)
-{
-	__shared__ uint32_t red[kWaves];
-
-	const uint32_t d = blockIdx.x;
-	const uint32_t per = (blocks + kThreads - 1) / kThreads;
-	const uint32_t b0 = min(threadIdx.x * per, blocks), b1 = min(b0 + per, blocks);
-	uint32_t sum = 0;
-	for (uint32_t b = b0; b < b1; b++)
-		sum += g.hist[b * kDigits + d];
-	uint32_t total;
-	uint32_t at = block_prefix(sum, red, total);
-	for (uint32_t b = b0; b < b1; b++) {
-		const uint32_t c = g.hist[b * kDigits + d];
-		g.hist[b * kDigits + d] = at;
-		at += c;
-	}
-	if (threadIdx.x == 0)
-		g.digit_total[d] = total;
-}
-
-__global__ __launch_bounds__(kThreads) void k_seq_scatter(SeqArgs g)
-{
-	__shared__ uint32_t run[kDigits];             // the next output cell of each digit
-	__shared__ uint32_t wcnt[kWaves * kDigits];   // cells of each digit in each wave of the row at hand
-	__shared__ uint32_t red[kWaves];
-
-	const uint32_t tid = threadIdx.x, wave = tid / 64;
-	uint32_t all;
-	const uint32_t digits_before = block_prefix(g.digit_total[tid], red, all);   // cells of the digits in front of tid
-	run[tid] = digits_before + g.hist[blockIdx.x * kDigits + tid];
-	for (int w = 0; w < kWaves; w++)
-		wcnt[w * kDigits + tid] = 0;
-	__syncthreads();
-	const Share sh = share_of((g.n + kTile - 1) / kTile);
-	for (uint32_t t = sh.t_begin; t < sh.t_end; t++)
-		for (int q = 0; q < kPer; q++) {   // a row of kThreads cells: cell order is (row, thread)
-			const uint32_t i = t * kTile + q * kThreads + tid;
-			const bool valid = i < g.n;
-			const uint32_t key = valid ? g.key_in[i] : 0, val = valid ? g.val_in[i] : 0;
-			const uint32_t digit = (key >> g.shift) & (kDigits - 1);
-			uint64_t same = __ballot(valid);   // the lanes of this wave with this lane's digit
-#pragma unroll
-			for (int b = 0; b < 8; b++) {
-				const bool bit = (digit >> b) & 1;
-				const uint64_t v = __ballot(bit);
-				same &= bit ? v : ~v;
-			}
-			const uint32_t rank = mbcnt64(same);
-			if (valid && rank == 0)
-				wcnt[wave * kDigits + digit] = (uint32_t)__popcll(same);
-			__syncthreads();
-			if (valid) {
-				uint32_t dst = run[digit] + rank;
-				for (uint32_t w = 0; w < wave; w++)
-					dst += wcnt[w * kDigits + digit];
-				if (dst < g.n) {   // (always: the counts are those of k_seq_hist)
-					g.key_out[dst] = key;
-					g.val_out[dst] = val;
-				}
-			}
-			__syncthreads();
-			uint32_t c = 0;
-			for (int w = 0; w < kWaves; w++) {
-				c += wcnt[w * kDigits + tid];
-				wcnt[w * kDigits + tid] = 0;
-			}
-			run[tid] += c;
-			__syncthreads();
-		}
 }
 
 // ---- the ordered cells: where every slot begins, and the ends in order ----
@@ -354,66 +240,31 @@ __global__ __launch_bounds__(kThreads) void k_seq_emit(SeqArgs g)
 	__shared__ uint32_t wave_cnt[kPer * kWaves];
 	__shared__ uint32_t red[2 * kWaves];
 
-	const uint32_t tid = threadIdx.x;
 	const uint32_t m = records_of(g);
-	const Share sh = share_of((m + kTile - 1) / kTile);
-	uint32_t base = 0;
-	if (WRITE) {
-		uint32_t total;
-		base = blocks_before(g.counts, red, total);
-		if (blockIdx.x == 0 && tid == 0) {
-			const int32_t last = g.pat_plane[1 + m];   // the trailer is the input's
-			write_ends(g.seq_out, g.cap, total, last);
-			write_ends(g.off_out, g.cap, total, last);
-			uint32_t alive = 0;
-			for (uint32_t j = 0; j < g.levels; j++)
-				alive += g.level_total[j];
-			g.info[0] = (int32_t)g.slot_begin[g.slots];
-			g.info[1] = (int32_t)alive;
-			g.info[2] = g.info[3] = 0;
-		}
-	}
-	uint32_t kept = 0;
-	for (uint32_t t = sh.t_begin; t < sh.t_end; t++) {
-		uint32_t flag[kPer], incl[kPer], wave_total[kPer];
-#pragma unroll
-		for (int q = 0; q < kPer; q++) {
-			const uint32_t i = t * kTile + q * kThreads + tid;
-			flag[q] = i < m ? (g.emit[i] != 0) : 0u;
-			kept += flag[q];
-		}
-		if (!WRITE)
-			continue;
-#pragma unroll
-		for (int q = 0; q < kPer; q++) {
-			incl[q] = wave_inclusive(flag[q]);
-			wave_total[q] = (uint32_t)__shfl((int)incl[q], 63, 64);
-		}
-		tile_publish(wave_total, wave_cnt);
-		uint32_t tile_total = 0;
-#pragma unroll
-		for (int q = 0; q < kPer; q++) {
-			const uint32_t i = t * kTile + q * kThreads + tid;
-			const uint32_t d = base + tile_row(wave_cnt, q, tile_total) + incl[q] - flag[q];
-			if (flag[q] && d + 2 < g.cap) {
-				const uint32_t p = (uint32_t)g.pat_plane[1 + i];
-				int32_t seq = -1;
-				if (p < g.num_patterns) {
-					const int32_t slot = g.ent[p].x;
-					if (slot >= 0 && (uint32_t)slot < g.slots)
-						seq = g.slot_tab[slot].y;
-				}
-				g.seq_out[1 + d] = seq;
-				g.off_out[1 + d] = g.off_plane[1 + i];
-			}
-		}
-		base += tile_total;
-	}
-	if (!WRITE) {
-		kept = block_sum(kept, red);
-		if (tid == 0)
-			g.counts[blockIdx.x] = (int32_t)kept;
-	}
+	emit_flagged<WRITE>(
+	    g.emit, m, g.counts, g.cap, wave_cnt, red,
+	    [&](uint32_t total) {
+		    const int32_t last = g.pat_plane[1 + m];   // the trailer is the input's
+		    write_ends(g.seq_out, g.cap, total, last);
+		    write_ends(g.off_out, g.cap, total, last);
+		    uint32_t alive = 0;
+		    for (uint32_t j = 0; j < g.levels; j++)
+			    alive += g.level_total[j];
+		    g.info[0] = (int32_t)g.slot_begin[g.slots];
+		    g.info[1] = (int32_t)alive;
+		    g.info[2] = g.info[3] = 0;
+	    },
+	    [&](uint32_t i, uint32_t d) {
+		    const uint32_t p = (uint32_t)g.pat_plane[1 + i];
+		    int32_t seq = -1;
+		    if (p < g.num_patterns) {
+			    const int32_t slot = g.ent[p].x;
+			    if (slot >= 0 && (uint32_t)slot < g.slots)
+				    seq = g.slot_tab[slot].y;
+		    }
+		    g.seq_out[1 + d] = seq;
+		    g.off_out[1 + d] = g.off_plane[1 + i];
+	    });
 }
 
 // a set without sequences: no record
@@ -428,15 +279,6 @@ __global__ void k_seq_none(SeqArgs g)
 }
 
 // ---- host side ----
-
-// 8-bit passes that order keys in [0, slots] (slots: the key of a cell without a part, through its low digits)
-uint32_t radix_passes(uint32_t slots)
-{
-	uint32_t passes = 1;
-	while (passes < 4 && ((uint64_t)slots >> (8 * passes)) != 0)
-		passes++;
-	return passes;
-}
 
 struct Layout {
 	size_t t0, key[2], val[2], ends, prefix, emit, hist, digit_total, slot_begin, counts, level_total, total;
@@ -459,8 +301,8 @@ Layout layout_of(size_t n, uint32_t blocks, uint32_t slots)
 	l.ends = take(n * sizeof(int32_t));
 	l.prefix = take(n * sizeof(uint32_t));
 	l.emit = take(n * sizeof(uint32_t));
-	l.hist = take((size_t)blocks * kDigits * sizeof(uint32_t));
-	l.digit_total = take(kDigits * sizeof(uint32_t));
+	l.hist = take(radix_hist_bytes(blocks));
+	l.digit_total = take(radix_digit_total_bytes());
 	l.slot_begin = take(((size_t)slots + 1) * sizeof(uint32_t));
 	l.counts = take((size_t)blocks * sizeof(int32_t));
 	l.level_total = take(ACM_SEQ_MAX_PARTS * sizeof(uint32_t));
@@ -507,8 +349,6 @@ extern "C" int acm_sequence_matches_async(const acm_dfa *d, const int32_t *d_pat
 	g.ends = (int32_t *)(ws + l.ends);
 	g.prefix = (uint32_t *)(ws + l.prefix);
 	g.emit = (uint32_t *)(ws + l.emit);
-	g.hist = (uint32_t *)(ws + l.hist);
-	g.digit_total = (uint32_t *)(ws + l.digit_total);
 	g.slot_begin = (uint32_t *)(ws + l.slot_begin);
 	g.counts = (int32_t *)(ws + l.counts);
 	g.level_total = (uint32_t *)(ws + l.level_total);
@@ -525,26 +365,15 @@ extern "C" int acm_sequence_matches_async(const acm_dfa *d, const int32_t *d_pat
 		ACM_HIP_TRY(hipGetLastError());
 		return ACM_OK;
 	}
-	int cur = 0;   // the buffers that hold the cells
-	g.key_in = (uint32_t *)(ws + l.key[0]);
-	g.val_in = (uint32_t *)(ws + l.val[0]);
+	uint32_t *const key[2] = { (uint32_t *)(ws + l.key[0]), (uint32_t *)(ws + l.key[1]) };
+	uint32_t *const val[2] = { (uint32_t *)(ws + l.val[0]), (uint32_t *)(ws + l.val[1]) };
+	g.key_in = key[0];
+	g.val_in = val[0];
 	hipLaunchKernelGGL(k_seq_key, grid, block, 0, s, g);
 	ACM_HIP_TRY(hipGetLastError());
-	const uint32_t passes = radix_passes(d->seq_slots);
-	for (uint32_t k = 0; k < passes; k++) {
-		g.key_in = (uint32_t *)(ws + l.key[cur]);
-		g.val_in = (uint32_t *)(ws + l.val[cur]);
-		g.key_out = (uint32_t *)(ws + l.key[cur ^ 1]);
-		g.val_out = (uint32_t *)(ws + l.val[cur ^ 1]);
-		g.shift = 8 * k;
-		hipLaunchKernelGGL(k_seq_hist, grid, block, 0, s, g);
-		ACM_HIP_TRY(hipGetLastError());
-		hipLaunchKernelGGL(k_seq_offsets, dim3(kDigits), block, 0, s, g, blocks);
-		ACM_HIP_TRY(hipGetLastError());
-		hipLaunchKernelGGL(k_seq_scatter, grid, block, 0, s, g);
-		ACM_HIP_TRY(hipGetLastError());
-		cur ^= 1;
-	}
+	int cur = 0;   // the buffers that hold the ordered cells
+	ACM_HIP_TRY(radix_order(g.n, key, val, (uint32_t *)(ws + l.hist), (uint32_t *)(ws + l.digit_total),
+	    radix_passes(d->seq_slots), blocks, s, cur));
 	g.keys = (const uint32_t *)(ws + l.key[cur]);
 	g.vals = (const uint32_t *)(ws + l.val[cur]);
 	hipLaunchKernelGGL(k_seq_bounds, grid, block, 0, s, g);

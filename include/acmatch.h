@@ -268,6 +268,63 @@ int acm_automaton_add_signature_ex(acm_automaton *, const char *body, int iid, u
 int acm_automaton_load_signature_file_ex(acm_automaton *, const char *path, unsigned flags,
     unsigned syntax);
 
+/* Rules: a boolean condition over the signatures that hit ONE text.  A RULE is nops operands, 1 <= nops <=
+ * ACM_RULE_MAX_OPERANDS, an expression over them and a user id iid.  Operand j is a SEQUENCE index: the id
+ * space in which plain patterns (1-part sequences), multi-part signatures and wildcard signatures meet.  A
+ * sequence may be an operand of at most one rule and appear at most once in that rule's operand list; the
+ * expression may name an operand any number of times.  To use the same bytes in two rules, add the
+ * signature twice.
+ * Expressions.  Blanks and tabs between tokens are skipped, nothing else is allowed there:
+ *   expr := term ( '&' term )*  |  term ( '|' term )*
+ *   term := ( NUMBER | '(' expr ')' ) [ ( '=' | '>' | '<' ) NUMBER ]
+ * '&' and '|' at one nesting level without parentheses are ACM_ERR_PARSE: there is no precedence to get
+ * wrong.  An operand NUMBER is < nops (else ACM_ERR_PARSE), a comparison NUMBER lies in [0, INT32_MAX].
+ * Parentheses nest at most ACM_RULE_MAX_NESTING deep; deeper, or more operands than the maximum, is
+ * ACM_ERR_LIMIT.  ClamAV's distinct-count form "=n,m" is ACM_ERR_PARSE: not provided.  Every parse error
+ * names the column, counted from 1, in acm_last_error.
+ * Values.  Every node has a COUNT (int64) and a TRUTH:
+ *   operand      count: the occurrences of its sequence in the text      truth: count > 0
+ *   '&'          count: the sum of its children's counts                 truth: all children true
+ *   '|'          count: the sum of its children's counts                 truth: any child true
+ *   comparison   count: unchanged                                        truth: count = n, count > n, count < n
+ * So "A=0" is "A does not occur", and "(0|1)>3" is "more than three hits of the two together" (ClamAV's
+ * reading of a block).  A rule whose expression is true with every count 0 ("0=0", "0<5") is refused with
+ * ACM_ERR_ARG: no record could trigger it, which is what lets the pass look only at (rule, text) pairs that
+ * have a hit.  Negation is legal beside something positive: "0&1=0".
+ * Rules do not enter acm_automaton_compile: tables, digests, self-tests, the reference table and
+ * acm_dfa_device_bytes of an automaton without rules are what they were.  They may be added before or after
+ * compile; acm_dfa_upload takes a copy.  acm_rule_matches_async evaluates them on the device.
+ *   acm_automaton_add_rule           returns the rule index.  ACM_ERR_ARG: a bad sequence index, a sequence
+ *                                    already an operand (also twice in this call), nops < 1, the empty-text
+ *                                    refusal.  On any error nothing is applied.
+ *   acm_automaton_rule               rule i: iid, nops, borrowed pointers to the operands and the expression
+ *                                    as given (any may be NULL)
+ *   acm_automaton_sequence_rule      1 and (rule, operand) if the sequence is an operand, else 0
+ *   acm_automaton_add_logical_signature  parses "expr;body0;body1;..." -- a ClamAV .ldb line without its name
+ *                                    and target fields -- adds each body with
+ *                                    acm_automaton_add_signature_ex(..., iid, flags, syntax) and registers the
+ *                                    rule over the sequences that came back; returns the rule index.  The
+ *                                    whole line is parsed (the expression, every body, the room for
+ *                                    wildcard sets) before anything is added.  Subsignature offsets
+ *                                    ("EOF-10:") and "::" modifiers are ACM_ERR_PARSE.  Only before compile.
+ *   acm_automaton_load_logical_file  one such line per line, with an optional leading "<decimal iid>:",
+ *                                    otherwise the iid is the rule index; '#' lines and blank lines are
+ *                                    skipped.  A bad line names its line number and nothing of the file is
+ *                                    applied.  Returns the number of rules added.
+ * Not provided: counts carried across calls (a text whose records lie in different calls: scan whole
+ * texts), the distinct-count form "=n,m", .ldb target blocks and subsignature offsets.  The reference-named
+ * layer is unchanged. */
+#define ACM_RULE_MAX_OPERANDS 64
+#define ACM_RULE_MAX_NESTING 8
+int acm_automaton_add_rule(acm_automaton *, const int32_t *sequences, int nops, const char *expr, int iid);
+int acm_automaton_num_rules(const acm_automaton *);
+int acm_automaton_rule(const acm_automaton *, int index, int *iid, int *nops, const int32_t **sequences,
+    const char **expr);
+int acm_automaton_sequence_rule(const acm_automaton *, int sequence, int *rule, int *operand);
+int acm_automaton_add_logical_signature(acm_automaton *, const char *line, int iid, unsigned flags,
+    unsigned syntax);
+int acm_automaton_load_logical_file(acm_automaton *, const char *path, unsigned flags, unsigned syntax);
+
 /* ASCII case-insensitive matching for every pattern of the automaton.  With
  * it on, fold(b) = b - 0x20 for 'a' <= b <= 'z' and b otherwise (toupper in
  * the C locale; bytes >= 0x80 are never folded), and a scan of text T gives
@@ -717,6 +774,40 @@ int acm_sequence_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
     const int32_t *d_off_plane, size_t max_records, const int32_t *d_seg_start, size_t segments,
     long lead_begin, long text_end, int32_t *d_seq_out, int32_t *d_off_out, size_t out_capacity,
     int32_t *d_info, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Rules (acm_automaton_add_rule) evaluated on the device: the records of the sequence pass and the text
+ * starts in, one record per (rule, text) whose expression is true out.  No text is read.
+ * Input: the output planes of acm_sequence_matches_async: sequence index and end offset, offsets
+ * non-decreasing.  At most min([0], max_records) records are looked at.  A cell that is no sequence index,
+ * or a sequence that is no operand, takes part in nothing.
+ * Texts: d_seg_start[segments] as in acm_tally_matches_async: a record at offset o belongs to the last k
+ * with start[k] <= o; a record in front of start[0], and every record when segments == 0, belongs to the
+ * lead text, index -1.  Nothing is clamped: for per-text matching the caller runs the segment pass first,
+ * as for sequences.  Counts are not carried across calls.
+ * Output, three planes in the scan's cell layout and overflow contract ([0] = full count, records, trailer
+ * -- the input trailer unchanged -- at min(count + 1, out_capacity - 1)): one record per (rule, text) whose
+ * expression is true, at the position of its TRIGGER in input order: the first record in that text of the
+ * rule's lowest-numbered operand that occurs there.  So records come text by text, and inside a text by the
+ * trigger's offset.  d_rule_out the rule index, d_text_out k (-1: the lead text), d_off_out the trigger's
+ * offset.
+ *   d_info   int32[4], required, written whole: [0] input records that are an operand, [1] distinct
+ *            (operand, text) pairs, [2] (rule, text) pairs evaluated, [3] 0
+ * For an uploaded set without rules the call is legal and writes count 0.  Results are the same bytes on
+ * every run (integers; no order decided by atomics).  No read leaves the inputs, the starts and the
+ * library's tables and no write leaves the outputs and the workspace, whatever the planes hold; offsets out
+ * of order give unspecified records, nothing worse.  The outputs must not overlap the inputs.
+ * Stream-ordered, no host sync, no allocation, no host read of device data; argument errors (a NULL plane,
+ * output or d_info, out_capacity < 2, segments without starts, a short workspace) return ACM_ERR_ARG before
+ * anything is enqueued.  The records are keyed by operand and ordered by a stable radix sort over
+ * max_records cells (cost per max_records: size it to the planes); the first record of every (operand,
+ * text) run that no lower-numbered operand precedes evaluates its rule's postfix program, every count two
+ * binary searches (csrc/rule.hip).  The launch count depends on the uploaded set alone.  The workspace query
+ * is monotone in max_records and a multiple of 256. */
+size_t acm_rule_workspace_bytes(const acm_dfa *, size_t max_records);
+int acm_rule_matches_async(const acm_dfa *, const int32_t *d_seq_plane, const int32_t *d_off_plane,
+    size_t max_records, const int32_t *d_seg_start, size_t segments, int32_t *d_rule_out,
+    int32_t *d_text_out, int32_t *d_off_out, size_t out_capacity, int32_t *d_info, void *d_workspace,
+    size_t workspace_bytes, void *stream);
 
 /* Match tallies: counts of the records of any pass, reduced on the device, so a caller who only counts
  * (a classifier, grep -c, "which signatures hit which file") copies back the counts, not the records.
