@@ -42,6 +42,16 @@ SEQ_MAX_PARTS = 32
 GAP_UNBOUNDED = 0x7FFFFFFF
 WILDCARD_MAX_POSITIONS = 4096
 SIG_EXTENDED = 1
+SIG_GROUPS = 2
+GROUP_MAX_WIDTH = 32
+GROUP_MAX_ALTERNATIVES = 256
+PATTERN_MAX_GROUPS = 16
+
+
+class WildGroup(C.Structure):
+    """struct acm_wild_group (include/acmatch.h)."""
+    _fields_ = [("at", C.c_int32), ("width", C.c_int32), ("count", C.c_int32), ("negated", C.c_int32),
+                ("bytes", C.c_char_p)]
 RULE_MAX_OPERANDS = 64
 RULE_MAX_NESTING = 8
 
@@ -84,6 +94,11 @@ NATIVE_API = {
     "acm_automaton_pattern_wildcard": (C.c_int, [_vp, C.c_int, _i32p, _i32p, C.POINTER(_vp), C.POINTER(_vp)]),
     "acm_automaton_wildcards": (C.c_int, [_vp]),
     "acm_automaton_wildcard_reach": (C.c_int, [_vp, _i32p, _i32p]),
+    "acm_automaton_add_wildcard_groups": (C.c_int, [_vp, C.c_char_p, C.c_int, C.POINTER(WildGroup), C.c_int, C.c_int,
+                                                    C.c_uint]),
+    "acm_automaton_pattern_groups": (C.c_int, [_vp, C.c_int]),
+    "acm_automaton_pattern_group": (C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.POINTER(_vp)]),
+    "acm_automaton_groups": (C.c_int, [_vp]),
     "acm_automaton_add_signature_ex": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_uint, C.c_uint]),
     "acm_automaton_load_signature_file_ex": (C.c_int, [_vp, C.c_char_p, C.c_uint, C.c_uint]),
     "acm_automaton_add_rule": (C.c_int, [_vp, _i32p, C.c_int, C.c_char_p, C.c_int]),

@@ -169,27 +169,33 @@ class Automaton:
             check(r, "acm_automaton_add_sequence")
         return r
 
-    def add_signature(self, body, iid=0, nocase=False, extended=False):
+    @staticmethod
+    def _syntax(extended, groups):
+        return _lib.SIG_EXTENDED | _lib.SIG_GROUPS if groups else _lib.SIG_EXTENDED if extended else 0
+
+    def add_signature(self, body, iid=0, nocase=False, extended=False, groups=False):
         """A ClamAV-style hex body (acm_automaton_add_signature): hex byte pairs, ??, *, {n}, {n-m}, {-m}, {n-}.
         Adds its fixed parts as patterns and registers the sequence; only before compile().  extended
         (acm_automaton_add_signature_ex, ACM_SIG_EXTENDED): also a?, ?a, (aa|bb), !(aa|bb), ?? a position; the
-        parts are wildcard patterns (add_wildcard).  Returns the sequence index."""
+        parts are wildcard patterns (add_wildcard).  groups (ACM_SIG_GROUPS, implies extended): also alternatives
+        of more than one byte, (aabb|ccdd) and !(aabb|ccdd), all of one width.  Returns the sequence index."""
         body = body.encode() if isinstance(body, str) else bytes(body)
         fl = _lib.PATTERN_NOCASE if nocase else 0
-        if extended:
-            r = self.lib.acm_automaton_add_signature_ex(self.h, body, iid, fl, _lib.SIG_EXTENDED)
+        if extended or groups:
+            r = self.lib.acm_automaton_add_signature_ex(self.h, body, iid, fl, self._syntax(extended, groups))
         else:
             r = self.lib.acm_automaton_add_signature(self.h, body, iid, fl)
         if r < 0:
             check(r, "acm_automaton_add_signature")
         return r
 
-    def load_signature_file(self, path, nocase=False, extended=False):
+    def load_signature_file(self, path, nocase=False, extended=False, groups=False):
         """signatures from a file, one per line with an optional leading "<iid>:"; returns how many.  extended:
-        the extended body syntax (acm_automaton_load_signature_file_ex)"""
+        the extended body syntax (acm_automaton_load_signature_file_ex); groups: with multi-byte alternatives"""
         fl = _lib.PATTERN_NOCASE if nocase else 0
-        if extended:
-            n = self.lib.acm_automaton_load_signature_file_ex(self.h, str(path).encode(), fl, _lib.SIG_EXTENDED)
+        if extended or groups:
+            n = self.lib.acm_automaton_load_signature_file_ex(self.h, str(path).encode(), fl,
+                                                              self._syntax(extended, groups))
         else:
             n = self.lib.acm_automaton_load_signature_file(self.h, str(path).encode(), fl)
         if n < 0:
@@ -209,16 +215,49 @@ class Automaton:
             out[b >> 3] |= 1 << (b & 7)
         return bytes(out)
 
-    def add_wildcard(self, positions, iid=0, nocase=False):
+    def add_wildcard(self, positions, iid=0, nocase=False, groups=()):
         """A wildcard pattern (acm_automaton_add_wildcard): every position a set of byte values, given as an int,
         bytes or an iterable of ints.  The longest run of one-byte positions, its anchor, enters the automaton
         (nocase applies to it alone); the positions around it are checked by Matcher.scan_wildcards.  Only before
-        compile().  Returns the pattern index."""
+        compile().  groups (acm_automaton_add_wildcard_groups): (at, strings, negated) triples, ascending and
+        disjoint, strings of one width >= 2; the text under positions [at, at + width), which all carry the full
+        set, must equal one of the strings (negated: none).  Returns the pattern index."""
         sets = b"".join(self.byte_set(p) for p in positions)
-        r = self.lib.acm_automaton_add_wildcard(self.h, sets, len(sets) // 32, iid, _lib.PATTERN_NOCASE if nocase else 0)
+        fl = _lib.PATTERN_NOCASE if nocase else 0
+        groups = list(groups)
+        if not groups:
+            r = self.lib.acm_automaton_add_wildcard(self.h, sets, len(sets) // 32, iid, fl)
+        else:
+            arr, raw = (_lib.WildGroup * len(groups))(), []
+            for k, (at, strings, negated) in enumerate(groups):
+                strings = [bytes(x) for x in strings]
+                if not strings or any(len(x) != len(strings[0]) for x in strings):
+                    raise ValueError("group %d: the strings must be of one width, and at least one" % k)
+                raw.append(b"".join(strings))   # (alive until the call returns)
+                arr[k] = _lib.WildGroup(at, len(strings[0]), len(strings), 1 if negated else 0, raw[-1])
+            r =self.lib.acm_automaton_add_wildcard_groups(self.h, sets, len(sets) // 32, arr, len(groups), iid, fl)
         if r < 0:
             check(r, "acm_automaton_add_wildcard")
         return r
+
+    def wildcard_groups(self, i):
+        """the groups of pattern i: a list of (at, strings, negated), at counted from the pattern's first position"""
+        n = self.lib.acm_automaton_pattern_groups(self.h, i)
+        if n < 0:
+            check(n, "acm_automaton_pattern_groups")
+        out = []
+        for j in range(n):
+            at, w, cnt, neg, ptr = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_void_p()
+            check(self.lib.acm_automaton_pattern_group(self.h, i, j, C.byref(at), C.byref(w), C.byref(cnt), C.byref(neg),
+                                                       C.byref(ptr)), "acm_automaton_pattern_group")
+            raw = C.string_at(ptr.value, w.value * cnt.value)
+            out.append((at.value, [raw[k * w.value:(k + 1) * w.value] for k in range(cnt.value)], bool(neg.value)))
+        return out
+
+    @property
+    def has_groups(self):
+        """some pattern has a group (acm_automaton_groups)"""
+        return bool(self.lib.acm_automaton_groups(self.h))
 
     def wildcard(self, i):
         """(pre, post) of pattern i (acm_automaton_pattern_wildcard): the context positions in front of and behind
@@ -265,20 +304,20 @@ class Automaton:
             check(r, "acm_automaton_add_rule")
         return r
 
-    def add_logical_signature(self, line, iid=0, nocase=False, extended=False):
+    def add_logical_signature(self, line, iid=0, nocase=False, extended=False, groups=False):
         """"expr;body0;body1;..." (acm_automaton_add_logical_signature): every body is added as add_signature
         adds it and the rule registered over the sequences; only before compile().  Returns the rule index."""
         line = line.encode() if isinstance(line, str) else bytes(line)
         r = self.lib.acm_automaton_add_logical_signature(self.h, line, iid, _lib.PATTERN_NOCASE if nocase else 0,
-                                                         _lib.SIG_EXTENDED if extended else 0)
+                                                         self._syntax(extended, groups))
         if r < 0:
             check(r, "acm_automaton_add_logical_signature")
         return r
 
-    def load_logical_file(self, path, nocase=False, extended=False):
+    def load_logical_file(self, path, nocase=False, extended=False, groups=False):
         """logical signatures from a file, one per line with an optional leading "<iid>:"; returns how many"""
         n = self.lib.acm_automaton_load_logical_file(self.h, str(path).encode(), _lib.PATTERN_NOCASE if nocase else 0,
-                                                     _lib.SIG_EXTENDED if extended else 0)
+                                                     self._syntax(extended, groups))
         if n < 0:
             check(n, "acm_automaton_load_logical_file")
         return n

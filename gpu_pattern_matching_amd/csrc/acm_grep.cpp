@@ -104,6 +104,10 @@ double now_us()
 	       "                 positions reach over a buffer border is not decided: such candidates are counted and\n"
 	       "                 reported on stderr at exit.  Composes with -i, -I, -S and -P (a window counts from a part's\n"
 	       "                 first position) (extension; needs -Q or -K, not with -W)\n"
+	       "  -X             with -E: alternatives may be of more than one byte, (aabb|ccdd) and !(aabb|ccdd), all\n"
+	       "                 alternatives of one group of one width (at most 32 bytes, 256 alternatives, 16 groups a part).\n"
+	       "                 The group is checked on the device where the part's exact run and its other positions\n"
+	       "                 held.  For the files of -Q and -K; composes and refuses as -E does (extension; needs -E)\n"
 	       "  -K file        rules, one logical signature per line: 'expr;body0;body1;...' with an optional leading\n"
 	       "                 '<decimal id>:' -- a ClamAV .ldb line without its name and target fields.  A body is a\n"
 	       "                 signature as -Q takes it (with -E: in the extended syntax); expr is a condition over the\n"
@@ -176,6 +180,7 @@ struct Config {
 	int cased = 0;           // -I without -i: the records go through the case pass
 	int pos = 0;             // -P: the records go through the position pass
 	int seq = 0;             // -Q: every pattern of the records goes through the sequence pass; its records are reported
+	int grp = 0;             // -X: with -E, alternatives of more than one byte
 	int ext = 0;             // -E: the signatures of -Q and the bodies of -K are read in the extended syntax
 	int rules = 0;           // -K: the sequence pass's records go through the rule pass; its records are reported (seq is set too)
 	int wild = 0;            // -E and some part has a context: the parts' records go through the wildcard pass
@@ -1034,7 +1039,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:X")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -1070,6 +1075,7 @@ int main(int argc, char **argv)
 		case 'P': c.pos_path = optarg; break;
 		case 'Q': c.seq_path = optarg; break;
 		case 'E': c.ext = 1; break;
+		case 'X': c.grp = 1; break;
 		case 'K': c.rule_path = optarg; break;
 		default: usage();
 		}
@@ -1137,6 +1143,10 @@ int main(int argc, char **argv)
 	}
 	if (c.ext && !c.seq) {
 		printf("ERROR: -E needs -Q or -K: it is the syntax of the signature file\n");
+		err++;
+	}
+	if (c.grp && !c.ext) {
+		printf("ERROR: -X needs -E\n");
 		err++;
 	}
 	if (c.ext && c.words) {
@@ -1211,11 +1221,12 @@ int main(int argc, char **argv)
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}
-	if (!c.seq_path.empty() && acm_automaton_load_signature_file_ex(aut, c.seq_path.c_str(), 0, c.ext ? ACM_SIG_EXTENDED : 0) < 0) {
+	const unsigned syntax = c.ext ? (c.grp ? ACM_SIG_EXTENDED | ACM_SIG_GROUPS : ACM_SIG_EXTENDED) : 0;
+	if (!c.seq_path.empty() && acm_automaton_load_signature_file_ex(aut, c.seq_path.c_str(), 0, syntax) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}
-	if (c.rules && acm_automaton_load_logical_file(aut, c.rule_path.c_str(), 0, c.ext ? ACM_SIG_EXTENDED : 0) < 0) {
+	if (c.rules && acm_automaton_load_logical_file(aut, c.rule_path.c_str(), 0, syntax) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}

@@ -78,6 +78,13 @@ struct acm_automaton {
 		int32_t wild_pre = 0, wild_post = 0;
 		std::vector<uint8_t> wild_sets;
 		std::vector<uint16_t> wild_cells;
+		// its groups (acm_automaton_add_wildcard_groups), ascending: at counts from the pattern's first position,
+		// bytes holds the distinct strings of width bytes each.  Covered positions carry the full set above
+		struct Group {
+			int32_t at, width, negated;
+			std::vector<uint8_t> bytes;
+		};
+		std::vector<Group> wild_groups;
 	};
 	// the distinct context sets of two or more bytes, interned: at most 256
 	std::vector<std::array<uint8_t, 32>> wild_classes;

@@ -319,8 +319,14 @@ namespace {
 
 // a signature body, parsed: the parts and the gap in front of every part but the first.  Syntax 0: a part is
 // its bytes.  ACM_SIG_EXTENDED: a part is its positions, 32 bytes of set each (acm_automaton_add_wildcard).
+struct SigGroup {
+	int32_t at, width, negated;
+	std::vector<unsigned char> bytes;   // the distinct strings
+};
+
 struct Signature {
 	std::vector<std::vector<unsigned char>> parts;
+	std::vector<std::vector<SigGroup>> groups;   // ACM_SIG_GROUPS: per part (empty without the bit)
 	std::vector<int32_t> gap_lo, gap_hi;
 	int iid = 0;
 	bool has_iid = false;
@@ -466,10 +472,13 @@ int set_count(const unsigned char *set)
 
 // The extended syntax (ACM_SIG_EXTENDED): a position is HH, H?, ?H, ??, (HH|HH|...) or !(HH|...); * and {..}
 // separate parts.  A part is its positions' sets.  Returns 0, or the column (from 1) of the first byte that is
-// wrong, with why; a part without an exact byte is reported at the column it begins at.
-int parse_signature_ex(const char *s, Signature &sig, const char *&why)
+// wrong, with why; a part without an exact byte is reported at the column it begins at.  with_groups
+// (ACM_SIG_GROUPS): an alternative is one or more byte pairs, and a part has its groups beside its sets.
+int parse_signature_ex(const char *s, Signature &sig, const char *&why, bool with_groups = false)
 {
 	sig.parts.clear();
+	sig.groups.clear();
+	std::vector<SigGroup> part_groups;
 	sig.gap_lo.clear();
 	sig.gap_hi.clear();
 	sig.extended = true;
@@ -519,7 +528,75 @@ int parse_signature_ex(const char *s, Signature &sig, const char *&why)
 				return (int)at + 1;
 			}
 			i += c == '!' ? 2 : 1;
-			for (;;) {
+			size_t width = 1;
+			std::vector<unsigned char> strings;   // with_groups: the distinct alternatives, width bytes each
+			while (with_groups) {   // (left by break)
+				const size_t alt_at = i;
+				std::vector<unsigned char> alt;
+				for (int b; (b = hex_pair(i)) >= 0; i += 2)
+					alt.push_back((unsigned char)b);
+				if (alt.empty() || hex_nibble((unsigned char)s[i]) >= 0) {
+					why = alt.empty() ? "not a hex byte in an alternative" : "odd hex digit";
+					return (int)i + 1;
+				}
+				if (alt_at == at + (c == '!' ? 2 : 1))
+					width = alt.size();
+				if (alt.size() != width) {
+					why = "an alternative of another width than the first";
+					return (int)alt_at + 1;
+				}
+				bool seen = false;
+				for (size_t k = 0; k < strings.size() && !seen; k += width)
+					seen = !memcmp(&strings[k], alt.data(), width);
+				if (!seen)
+					strings.insert(strings.end(), alt.begin(), alt.end());
+				if (s[i] == ')')
+					break;
+				if (s[i] != '|') {
+					why = "not | or ) in an alternative";
+					return (int)i + 1;
+				}
+				i++;
+			}
+			if (with_groups && width > 1) {
+				i++;
+				const size_t count = strings.size() / width;
+				if (width > (size_t)ACM_GROUP_MAX_WIDTH || count > (size_t)ACM_GROUP_MAX_ALTERNATIVES) {
+					why = width > (size_t)ACM_GROUP_MAX_WIDTH ? "alternatives of too many bytes" : "too many alternatives";
+					return (int)at + 1;
+				}
+				const bool exact_run = c != '!' && count == 1;
+				if (!exact_run && part_groups.size() >= (size_t)ACM_PATTERN_MAX_GROUPS) {
+					why = "too many groups in a part";
+					return (int)at + 1;
+				}
+				if (part.size() / 32 + width > (size_t)ACM_WILDCARD_MAX_POSITIONS) {
+					why = "a part of too many positions";
+					return (int)at + 1;
+				}
+				if (gap.open)
+					gap.close(sig);
+				if (part.empty()) {
+					part_at = at;
+					exact = false;
+				}
+				if (!exact_run)
+					part_groups.push_back(SigGroup{ (int32_t)(part.size() / 32), (int32_t)width, c == '!', strings });
+				for (size_t k = 0; k < width; k++) {
+					unsigned char one[32] = { 0 };
+					if (exact_run)
+						set_add(one, strings[k]);
+					else
+						memset(one, 0xFF, 32);
+					part.insert(part.end(), one, one + 32);
+				}
+				exact = exact || exact_run;
+				last_any = false;
+				continue;
+			}
+			for (size_t k = 0; k < strings.size(); k++)   // (one-byte alternatives: a set position)
+				set_add(set, strings[k]);
+			while (!with_groups) {
 				const int b = hex_pair(i);
 				if (b < 0) {
 					why = "not a hex byte in an alternative";
@@ -589,7 +666,9 @@ int parse_signature_ex(const char *s, Signature &sig, const char *&why)
 				return (int)part_at + 1;
 			}
 			sig.parts.push_back(part);
+			sig.groups.push_back(part_groups);
 			part.clear();
+			part_groups.clear();
 			gap = GapSum{ 0, 0, true };
 		}
 		if (!gap.add(l, h)) {
@@ -610,11 +689,20 @@ int parse_signature_ex(const char *s, Signature &sig, const char *&why)
 		return (int)part_at + 1;
 	}
 	sig.parts.push_back(part);
+	sig.groups.push_back(part_groups);
 	if (sig.parts.size() > (size_t)ACM_SEQ_MAX_PARTS) {
 		why = "too many parts";
 		return (int)i + 1;
 	}
 	return 0;
+}
+
+// a body in the syntax asked for
+int parse_body(unsigned syntax, const char *s, Signature &sig, const char *&why)
+{
+	if (!(syntax & ACM_SIG_EXTENDED))
+		return parse_signature(s, sig, why);
+	return parse_signature_ex(s, sig, why, (syntax & ACM_SIG_GROUPS) != 0);
 }
 
 // the context sets of two or more bytes among the n positions of sets that the automaton has not interned and
@@ -637,10 +725,17 @@ bool wild_room(const acm_automaton *a, const unsigned char *sets, int n, std::ve
 int apply_signature(acm_automaton *a, const Signature &sig, int iid, unsigned flags)
 {
 	std::vector<int32_t> parts;
-	for (const auto &p : sig.parts) {
+	for (size_t k = 0; k < sig.parts.size(); k++) {
+		const auto &p = sig.parts[k];
 		parts.push_back((int32_t)a->patterns.size());
-		const int rc = sig.extended ? acm_automaton_add_wildcard(a, p.data(), (int)(p.size() / 32), iid, flags)
-		                            : acm_automaton_add_ex(a, p.data(), (int)p.size(), iid, flags);
+		std::vector<acm_wild_group> groups;   // (their limits were checked by the parser)
+		if (k < sig.groups.size())
+			for (const SigGroup &g : sig.groups[k])
+				groups.push_back(acm_wild_group{ g.at, g.width, (int32_t)(g.bytes.size() / (size_t)g.width), g.negated, g.bytes.data() });
+		const int rc = !sig.extended ? acm_automaton_add_ex(a, p.data(), (int)p.size(), iid, flags)
+		               : groups.empty() ? acm_automaton_add_wildcard(a, p.data(), (int)(p.size() / 32), iid, flags)
+		                                : acm_automaton_add_wildcard_groups(a, p.data(), (int)(p.size() / 32), groups.data(),
+		                                      (int)groups.size(), iid, flags);
 		if (rc < 0)
 			return rc;
 	}
@@ -666,8 +761,10 @@ int sig_args(const char *fn, acm_automaton *a, const void *arg, unsigned flags, 
 		return acm::fail(ACM_ERR_ARG, "%s: bad arguments", fn);
 	if (flags & ~(unsigned)ACM_PATTERN_NOCASE)
 		return acm::fail(ACM_ERR_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~(unsigned)ACM_PATTERN_NOCASE);
-	if (syntax & ~(unsigned)ACM_SIG_EXTENDED)
-		return acm::fail(ACM_ERR_ARG, "%s: unknown syntax bits 0x%x", fn, syntax & ~(unsigned)ACM_SIG_EXTENDED);
+	if (syntax & ~(unsigned)(ACM_SIG_EXTENDED | ACM_SIG_GROUPS))
+		return acm::fail(ACM_ERR_ARG, "%s: unknown syntax bits 0x%x", fn, syntax & ~(unsigned)(ACM_SIG_EXTENDED | ACM_SIG_GROUPS));
+	if ((syntax & ACM_SIG_GROUPS) && !(syntax & ACM_SIG_EXTENDED))
+		return acm::fail(ACM_ERR_ARG, "%s: ACM_SIG_GROUPS needs ACM_SIG_EXTENDED", fn);
 	if (a->compiled)
 		return acm::fail(ACM_ERR_ARG, "%s: automaton already compiled", fn);
 	return ACM_OK;
@@ -679,7 +776,7 @@ int add_signature(const char *fn, acm_automaton *a, const char *body, int iid, u
 		return rc;
 	Signature sig;
 	const char *why = "";
-	if (const int col = (syntax & ACM_SIG_EXTENDED) ? parse_signature_ex(body, sig, why) : parse_signature(body, sig, why))
+	if (const int col = parse_body(syntax, body, sig, why))
 		return acm::fail(ACM_ERR_PARSE, "signature: column %d: %s", col, why);
 	if (!signatures_fit(a, &sig, 1))
 		return acm::fail(ACM_ERR_LIMIT, "%s: more than 256 distinct context sets", fn);
@@ -715,7 +812,7 @@ int load_signature_file(const char *fn, acm_automaton *a, const char *path, unsi
 		}
 		const char *why = "";
 		const char *body = line.c_str() + b;
-		if (const int col = (syntax & ACM_SIG_EXTENDED) ? parse_signature_ex(body, sig, why) : parse_signature(body, sig, why))
+		if (const int col = parse_body(syntax, body, sig, why))
 			return acm::fail(ACM_ERR_PARSE, "%s:%d: column %d: %s", path, line_no, (int)b + col, why);
 		sigs.push_back(std::move(sig));
 	}
@@ -945,8 +1042,7 @@ int parse_logical(const char *where, const char *line, int col0, unsigned syntax
 			    at + (int)colon + 1);
 		Signature sig;
 		const char *why = "";
-		if (const int col = (syntax & ACM_SIG_EXTENDED) ? parse_signature_ex(body.c_str(), sig, why)
-		                                                : parse_signature(body.c_str(), sig, why))
+		if (const int col = parse_body(syntax, body.c_str(), sig, why))
 			return acm::fail(ACM_ERR_PARSE, "%s: column %d: %s", where, at + col, why);
 		out.bodies.push_back(std::move(sig));
 		if (!e)
@@ -1092,22 +1188,68 @@ extern "C" int acm_automaton_load_logical_file(acm_automaton *a, const char *pat
 
 // ---- wildcard patterns -----------------------------------------------------------
 
-extern "C" int acm_automaton_add_wildcard(acm_automaton *a, const uint8_t *sets, int n, int iid, unsigned flags)
+// the groups of a wildcard pattern of n positions, checked and with equal strings dropped: ACM_OK or the error
+static int checked_groups(const char *fn, const uint8_t *sets, int n, const acm_wild_group *groups, int ngroups,
+    std::vector<acm_automaton::Pattern::Group> &out)
+{
+	if (ngroups < 0 || (ngroups > 0 && !groups))
+		return acm::fail(ACM_ERR_ARG, "%s: bad arguments", fn);
+	if (ngroups > ACM_PATTERN_MAX_GROUPS)
+		return acm::fail(ACM_ERR_LIMIT, "%s: %d groups, at most %d", fn, ngroups, ACM_PATTERN_MAX_GROUPS);
+	int end = 0;   // behind the group in front
+	for (int j = 0; j < ngroups; j++) {
+		const acm_wild_group &g = groups[j];
+		if (!g.bytes || g.width < 2 || g.count < 1 || (g.negated != 0 && g.negated != 1))
+			return acm::fail(ACM_ERR_ARG, "%s: group %d: width %d, count %d, negated %d", fn, j, g.width, g.count, g.negated);
+		if (g.width > ACM_GROUP_MAX_WIDTH)
+			return acm::fail(ACM_ERR_LIMIT, "%s: group %d: width %d, at most %d", fn, j, g.width, ACM_GROUP_MAX_WIDTH);
+		if (g.at < 0 || g.at > n - g.width)
+			return acm::fail(ACM_ERR_ARG, "%s: group %d: positions [%d, %ld) leave the pattern's %d", fn, j, g.at,
+			    (long)g.at + g.width, n);
+		if (g.at < end)
+			return acm::fail(ACM_ERR_ARG, "%s: group %d begins at %d, inside or in front of the group before it", fn, j, g.at);
+		end = g.at + g.width;
+		for (int i = g.at; i < end; i++)
+			for (int k = 0; k < 32; k++)
+				if (sets[32 * (size_t)i + k] != 0xFF)
+					return acm::fail(ACM_ERR_ARG, "%s: group %d: position %d does not carry the full set", fn, j, i);
+		acm_automaton::Pattern::Group o{ g.at, g.width, g.negated, {} };
+		for (int c = 0; c < g.count; c++) {
+			const uint8_t *str = g.bytes + (size_t)c * g.width;
+			bool seen = false;
+			for (size_t k = 0; k < o.bytes.size() && !seen; k += g.width)
+				seen = !memcmp(&o.bytes[k], str, g.width);
+			if (seen)
+				continue;
+			if (o.bytes.size() / g.width >= (size_t)ACM_GROUP_MAX_ALTERNATIVES)
+				return acm::fail(ACM_ERR_LIMIT, "%s: group %d: more than %d distinct strings", fn, j, ACM_GROUP_MAX_ALTERNATIVES);
+			o.bytes.insert(o.bytes.end(), str, str + g.width);
+		}
+		out.push_back(std::move(o));
+	}
+	return ACM_OK;
+}
+
+static int add_wildcard(const char *fn, acm_automaton *a, const uint8_t *sets, int n, const acm_wild_group *groups, int ngroups,
+    int iid, unsigned flags)
 {
 	if (!a || !sets || n < 1)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_wildcard: bad arguments");
+		return acm::fail(ACM_ERR_ARG, "%s: bad arguments", fn);
 	if (flags & ~(unsigned)ACM_PATTERN_NOCASE)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_wildcard: unknown flag bits 0x%x", flags & ~(unsigned)ACM_PATTERN_NOCASE);
+		return acm::fail(ACM_ERR_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~(unsigned)ACM_PATTERN_NOCASE);
 	if (a->compiled)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_wildcard: automaton already compiled");
+		return acm::fail(ACM_ERR_ARG, "%s: automaton already compiled", fn);
 	if (n > ACM_WILDCARD_MAX_POSITIONS)
-		return acm::fail(ACM_ERR_LIMIT, "acm_automaton_add_wildcard: %d positions, at most %d", n, ACM_WILDCARD_MAX_POSITIONS);
+		return acm::fail(ACM_ERR_LIMIT, "%s: %d positions, at most %d", fn, n, ACM_WILDCARD_MAX_POSITIONS);
+	std::vector<acm_automaton::Pattern::Group> checked;
+	if (int rc = checked_groups(fn, sets, n, groups, ngroups, checked))
+		return rc;
 	// the anchor: the longest run of one-byte sets, the leftmost among equal runs
 	int at = 0, len = 0, run = 0;
 	for (int i = 0; i < n; i++) {
 		const int c = set_count(sets + 32 * (size_t)i);
 		if (c == 0)
-			return acm::fail(ACM_ERR_ARG, "acm_automaton_add_wildcard: position %d: empty set", i);
+			return acm::fail(ACM_ERR_ARG, "%s: position %d: empty set", fn, i);
 		run = c == 1 ? run + 1 : 0;
 		if (run > len) {
 			len = run;
@@ -1115,11 +1257,11 @@ extern "C" int acm_automaton_add_wildcard(acm_automaton *a, const uint8_t *sets,
 		}
 	}
 	if (len == 0)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_wildcard: no position with a one-byte set");
+		return acm::fail(ACM_ERR_ARG, "%s: no position with a one-byte set", fn);
 	const int pre = at, post = n - at - len;
 	std::vector<std::array<uint8_t, 32>> fresh;
 	if (!wild_room(a, sets, pre, fresh) || !wild_room(a, sets + 32 * (size_t)(at + len), post, fresh))
-		return acm::fail(ACM_ERR_LIMIT, "acm_automaton_add_wildcard: more than 256 distinct context sets");
+		return acm::fail(ACM_ERR_LIMIT, "%s: more than 256 distinct context sets", fn);
 	auto only_byte = [&](int i) {
 		const uint8_t *s = sets + 32 * (size_t)i;
 		for (int b = 0; b < 256; b++)
@@ -1137,6 +1279,7 @@ extern "C" int acm_automaton_add_wildcard(acm_automaton *a, const uint8_t *sets,
 	acm_automaton::Pattern &p = a->patterns[index];
 	p.wild_pre = pre;
 	p.wild_post = post;
+	p.wild_groups = std::move(checked);
 	for (int i = 0; i < n; i++) {
 		if (i >= at && i < at + len)
 			continue;
@@ -1152,6 +1295,47 @@ extern "C" int acm_automaton_add_wildcard(acm_automaton *a, const uint8_t *sets,
 		}
 	}
 	return index;
+}
+
+extern "C" int acm_automaton_add_wildcard(acm_automaton *a, const uint8_t *sets, int n, int iid, unsigned flags)
+{
+	return add_wildcard("acm_automaton_add_wildcard", a, sets, n, nullptr, 0, iid, flags);
+}
+
+extern "C" int acm_automaton_add_wildcard_groups(acm_automaton *a, const uint8_t *sets, int n, const acm_wild_group *groups,
+    int ngroups, int iid, unsigned flags)
+{
+	return add_wildcard("acm_automaton_add_wildcard_groups", a, sets, n, groups, ngroups, iid, flags);
+}
+
+extern "C" int acm_automaton_pattern_groups(const acm_automaton *a, int index)
+{
+	if (!a || index < 0 || index >= (int)a->patterns.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_pattern_groups: index out of range");
+	return (int)a->patterns[index].wild_groups.size();
+}
+
+extern "C" int acm_automaton_pattern_group(const acm_automaton *a, int index, int j, int *at, int *width, int *count,
+    int *negated, const uint8_t **bytes)
+{
+	if (!a || index < 0 || index >= (int)a->patterns.size() || j < 0 || j >= (int)a->patterns[index].wild_groups.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_pattern_group: index out of range");
+	const acm_automaton::Pattern::Group &g = a->patterns[index].wild_groups[j];
+	if (at) *at = g.at;
+	if (width) *width = g.width;
+	if (count) *count = (int)(g.bytes.size() / (size_t)g.width);
+	if (negated) *negated = g.negated;
+	if (bytes) *bytes = g.bytes.data();
+	return ACM_OK;
+}
+
+extern "C" int acm_automaton_groups(const acm_automaton *a)
+{
+	if (a)
+		for (auto &p : a->patterns)
+			if (!p.wild_groups.empty())
+				return 1;
+	return 0;
 }
 
 extern "C" int acm_automaton_pattern_wildcard(const acm_automaton *a, int index, int *pre, int *post, const uint8_t **pre_sets,

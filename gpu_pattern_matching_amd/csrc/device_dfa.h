@@ -139,4 +139,11 @@ struct acm_dfa {
 	mutable std::vector<void *> profile_events;
 	mutable std::vector<void *> profile_pool;   // idle events, reused
 	mutable std::mutex profile_mutex;
+
+	// an automaton with groups only (acm_automaton_groups at upload; wild is then set too), for the wildcard pass;
+	// null otherwise.  Behind everything else: the fields the scan paths touch lie where they lay without these.
+	bool groups = false;
+	int32_t *d_grp_ent = nullptr;        // [patterns][2] {first group in d_grp, groups}
+	int32_t *d_grp = nullptr;            // [groups][4] {first byte counted from the span's, width, count | negated << 31, word index in d_grp_pool}
+	uint32_t *d_grp_pool = nullptr;      // the strings, each zero-padded to whole words
 };

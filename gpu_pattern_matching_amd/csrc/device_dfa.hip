@@ -367,6 +367,31 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 			if (rc == ACM_OK) rc = upload(&d->d_wild_pool, pool.data(), pool.size(), &d->device_bytes);
 			if (rc == ACM_OK) rc = upload(&d->d_wild_sets, sets.data(), sets.size(), &d->device_bytes);
 		}
+		// an automaton with groups (acm_automaton_groups): per pattern its groups, per group where it lies in
+		// the span and its strings, each padded with zeros to whole words (wildcard.hip).  Allocations of their
+		// own, as above.
+		d->groups = acm_automaton_groups(a) != 0;
+		if (rc == ACM_OK && d->groups) {
+			std::vector<int32_t> ent(2 * a->patterns.size()), grp;
+			std::vector<uint32_t> pool;
+			for (size_t i = 0; i < a->patterns.size(); i++) {
+				const acm_automaton::Pattern &p = a->patterns[i];
+				ent[2 * i] = (int32_t)(grp.size() / 4);
+				ent[2 * i + 1] = (int32_t)p.wild_groups.size();
+				for (const auto &g : p.wild_groups) {
+					const size_t count = g.bytes.size() / (size_t)g.width, words = ((size_t)g.width + 3) / 4;
+					grp.insert(grp.end(), { g.at, g.width, (int32_t)((uint32_t)count | (g.negated ? 0x80000000u : 0u)),
+					                          (int32_t)pool.size() });
+					for (size_t c = 0; c < count; c++) {
+						pool.resize(pool.size() + words, 0);
+						memcpy(&pool[pool.size() - words], &g.bytes[c * (size_t)g.width], (size_t)g.width);
+					}
+				}
+			}
+			rc = upload(&d->d_grp_ent, ent.data(), ent.size(), &d->device_bytes);
+			if (rc == ACM_OK) rc = upload(&d->d_grp, grp.data(), grp.size(), &d->device_bytes);
+			if (rc == ACM_OK) rc = upload(&d->d_grp_pool, pool.data(), pool.size(), &d->device_bytes);
+		}
 	} catch (const std::bad_alloc &) {
 		rc = acm::fail(ACM_ERR_NOMEM, "acm_dfa_upload: out of host memory");
 	}
@@ -434,6 +459,9 @@ extern "C" void acm_dfa_release(acm_dfa *d)
 		hipFree(d->d_wild_ent);
 		hipFree(d->d_wild_pool);
 		hipFree(d->d_wild_sets);
+		hipFree(d->d_grp_ent);
+		hipFree(d->d_grp);
+		hipFree(d->d_grp_pool);
 		free_small(d, d->d_depth);
 		free_small(d, d->d_class);
 		free_small(d, d->d_sv_bloom);

@@ -7,7 +7,7 @@
 //   1. no context: kept, whatever its text is
 //   2. the span leaves [T0, Tend): dropped (Tend unknown: no end is in the way)
 //   3. the span leaves the bytes given, [text_origin - before_len, text_end): undecided, dropped and counted
-//   4. kept iff every context byte is in its set
+//   4. kept iff every context byte is in its set and every group holds
 // It has the case pass's shape (the text under and around a record is read: TextWindow) and the position
 // pass's (the record's text is found in the staged slice of starts; STATE cells or pattern cells; undecided
 // entries are counted per block and summed by block 0 into d_info).  Cost per record and per context byte.
@@ -17,6 +17,14 @@
 // 0x100 | class; d_wild_sets[class][8], the interned sets of two or more bytes, at most 256 of them (8 KiB),
 // staged in LDS in ready(): a set test is one LDS read.  A set without contexts has none of these; the pass
 // then reads d_pat_len, keeps every entry of length >= 1, looks up no text and stages nothing.
+//
+// Groups (acm_automaton_add_wildcard_groups; tables only for a set that has some): d_grp_ent[p] = {first group,
+// groups}; d_grp[g] = {first byte counted from the span's, width w, count | negated << 31, word index of its
+// strings in d_grp_pool}, one 16-byte load; d_grp_pool, the strings, each zero-padded to whole words.  A group
+// holds iff the w text bytes equal one of its strings (negated: none).  The positions a group covers carry the
+// full set, so context_ok passes over them and groups_ok decides, for the few lanes that get that far.  The
+// kernels are instantiated a second time for such a set, over WildGroupArgs (141 and 178 VGPRs, nothing in
+// scratch): a set without groups runs the code it ran before there were any.  DESIGN.md 6m.
 //
 // LDS: the slice (8 KiB), the sets (at most 8 KiB, kSetWords) and the ranks' few cells: 16.1 KiB a block.  Eight
 // blocks of 256 threads would fill a CU's 32 wave slots with 129 KiB of its 160 KiB: LDS does not bound the
@@ -48,7 +56,19 @@ struct WildArgs {
 	const uint32_t *sets;
 	uint32_t classes;
 	int32_t *info;               // [4]
+	static constexpr bool kGroups = false;
 };
+
+// the arguments of the GROUPS kernels: a set without groups is launched with WildArgs as it was, so that its
+// kernels are the instructions they were
+struct WildGroupArgs : WildArgs {
+	const int2 *grp_ent;
+	const int4 *grp;
+	const uint32_t *grp_pool;
+	static constexpr bool kGroups = true;
+};
+
+constexpr int kGroupWords = ACM_GROUP_MAX_WIDTH / 4;
 
 enum { kDrop = 0, kKeep = 1, kUndecided = 2 };
 
@@ -79,8 +99,59 @@ __device__ __forceinline__ bool context_ok(const TextWindow &w, const uint32_t *
 	return true;
 }
 
+// Do the groups of pattern p hold where its span begins at stream offset `first`?  The span lies inside
+// before ++ text and a group inside the span.  The w text bytes of a group are packed once into words as the
+// pool holds a string (little-endian, zeros behind byte w), then compared word by word with every string until
+// one is equal.  The words are indexed by unrolled loops only: they stay in registers.
+__device__ __forceinline__ bool groups_ok(const WildGroupArgs &g, uint32_t p, int64_t first)
+{
+	const int2 ge = g.grp_ent[p];   // {first group, groups}
+	for (int32_t k = 0; k < ge.y; k++) {
+		const int4 e = g.grp[ge.x + k];   // {rel, width, count | negated << 31, word index}
+		const int64_t at = first + e.x;
+		const int32_t w = e.y, words = (w + 3) >> 2;
+		uint32_t t[kGroupWords];
+#pragma unroll
+		for (int j = 0; j < kGroupWords; j++) {
+			uint32_t v = 0;
+#pragma unroll
+			for (int b = 0; b < 4; b++)
+				if (4 * j + b < w)
+					v |= window_byte(g.w, at + 4 * j + b) << (8 * b);
+			t[j] = v;
+		}
+		const uint32_t count = (uint32_t)e.z & 0x7FFFFFFFu;
+		const uint32_t *str = g.grp_pool + e.w;
+		bool any = false;
+		// four strings a step: their first words are four loads that do not wait for each other, and only a
+		// string whose first word is the text's has its other words read (early exit per string)
+		for (uint32_t c = 0; c < count && !any; c += 4, str += 4 * words) {
+			uint32_t hit = 0;
+#pragma unroll
+			for (uint32_t u = 0; u < 4; u++)
+				if (c + u < count)
+					hit |= (uint32_t)(str[u * words] == t[0]) << u;
+			for (; hit && !any; hit &= hit - 1) {
+				const uint32_t *s = str + (uint32_t)(__ffs((int)hit) - 1) * words;
+				bool eq = true;
+#pragma unroll
+				for (int j = 1; j < kGroupWords; j++) {
+					if (j >= words || !eq)
+						break;
+					eq = s[j] == t[j];
+				}
+				any = eq;
+			}
+		}
+		if (any == (e.z < 0))   // one is equal and negated, or none and not negated
+			return false;
+	}
+	return true;
+}
+
 // entry (p, o) in the text [T0, Tend) (Tend: kEndUnknown).  Reads text only inside before ++ text.
-__device__ __forceinline__ int verdict(const WildArgs &g, const uint32_t *sets, uint32_t p, int32_t o, int64_t T0, int64_t Tend)
+template <class Args>
+__device__ __forceinline__ int verdict(const Args &g, const uint32_t *sets, uint32_t p, int32_t o, int64_t T0, int64_t Tend)
 {
 	if (p >= g.e.num_patterns)   // (a cell of a HEAD plane may hold anything)
 		return kDrop;
@@ -98,11 +169,17 @@ __device__ __forceinline__ int verdict(const WildArgs &g, const uint32_t *sets, 
 	if (first < g.w.text_origin - g.w.before_len || last >= g.w.text_end)
 		return kUndecided;
 	const uint16_t *c = g.pool + e.x;
-	return context_ok(g.w, sets, c, e.y, first) && context_ok(g.w, sets, c + e.y, e.z, (int64_t)o + 1) ? kKeep : kDrop;
+	if constexpr (Args::kGroups)   // (behind both contexts: only lanes whose every position held get there)
+		return context_ok(g.w, sets, c, e.y, first) && context_ok(g.w, sets, c + e.y, e.z, (int64_t)o + 1) && groups_ok(g, p, first)
+		           ? kKeep
+		           : kDrop;
+	else
+		return context_ok(g.w, sets, c, e.y, first) && context_ok(g.w, sets, c + e.y, e.z, (int64_t)o + 1) ? kKeep : kDrop;
 }
 
+template <class Args>
 struct WildPass : EntryPass {
-	const WildArgs &g;
+	const Args &g;
 	int32_t *slice;     // kSliceMax cells of LDS
 	uint32_t *bounds;   // 2 cells of LDS
 	uint32_t *sets;     // kSetWords cells of LDS
@@ -114,7 +191,7 @@ struct WildPass : EntryPass {
 		uint32_t kept;      // bit k: the k-th entry of the record's list that the walk asks about is kept (k < 32)
 	};
 
-	__device__ __forceinline__ WildPass(const WildArgs &g, int32_t *slice, uint32_t *bounds, uint32_t *sets)
+	__device__ __forceinline__ WildPass(const Args &g, int32_t *slice, uint32_t *bounds, uint32_t *sets)
 	    : g(g), slice(slice), bounds(bounds), sets(sets)
 	{
 	}
@@ -199,8 +276,8 @@ struct WildPass : EntryPass {
 	}
 };
 
-template <bool WRITE>
-__global__ __launch_bounds__(kThreads) void k_wildcard(WildArgs g)
+template <bool WRITE, class Args>
+__global__ __launch_bounds__(kThreads) void k_wildcard(Args g)
 {
 	__shared__ int32_t slice[kSliceMax];
 	__shared__ uint32_t sets[kSetWords];
@@ -208,7 +285,7 @@ __global__ __launch_bounds__(kThreads) void k_wildcard(WildArgs g)
 	__shared__ uint32_t wave_cnt[kPer * kWaves];
 	__shared__ uint32_t red[2 * kWaves];
 
-	WildPass pass(g, slice, bounds, sets);
+	WildPass<Args> pass(g, slice, bounds, sets);
 	entry_pass<WRITE>(g.e, pass, wave_cnt, red);
 }
 
@@ -225,16 +302,17 @@ extern "C" int acm_wildcard_matches_async(const acm_dfa *d, const int32_t *d_pat
     int32_t *d_pat_out, int32_t *d_off_out, size_t out_capacity, int32_t *d_info, void *d_workspace, size_t workspace_bytes,
     void *stream)
 {
-	WildArgs g;
+	WildGroupArgs g;
 	const bool own_ok = d_info && (report == ACM_REPORT_STATE || (report == ACM_REPORT_HEAD && all_patterns)) &&
 	                    window_ok(d_text, text_origin, text_end, d_before, before_len) && (!segments || d_seg_start) &&
 	                    segments <= 0x7FFFFFFFul && (open_end == -1 || open_end >= text_end);
 	const char *tables = tables_error(d, [&](const acm_dfa &a) -> const char * {
 		if (report == ACM_REPORT_STATE && (!a.d_list_begin || !a.d_list_len || !a.d_list_pool))
 			return "automaton has no match lists";
-		return a.wild && (!a.d_wild_ent || !a.d_wild_pool || !a.d_wild_sets || a.wild_classes > 256)
-		           ? "automaton with wildcard contexts without their tables"
-		           : nullptr;
+		if (a.wild && (!a.d_wild_ent || !a.d_wild_pool || !a.d_wild_sets || a.wild_classes > 256))
+			return "automaton with wildcard contexts without their tables";
+		return a.groups && (!a.wild || !a.d_grp_ent || !a.d_grp || !a.d_grp_pool) ? "automaton with groups without their tables"
+		                                                                         : nullptr;
 	});
 	if (int rc = entry_args(g.e, "acm_wildcard_matches_async",
 	        EntryCall{ d, d_pat_plane, d_off_plane, max_records, all_patterns, d_pat_out, d_off_out, out_capacity, d_workspace,
@@ -252,5 +330,10 @@ extern "C" int acm_wildcard_matches_async(const acm_dfa *d, const int32_t *d_pat
 	g.sets = d->d_wild_sets;
 	g.classes = d->wild_classes;
 	g.info = d_info;
-	return launch_passes(k_wildcard<false>, k_wildcard<true>, d, max_records, g, stream);
+	g.grp_ent = (const int2 *)d->d_grp_ent;
+	g.grp = (const int4 *)d->d_grp;
+	g.grp_pool = d->d_grp_pool;
+	if (d->groups)
+		return launch_passes(k_wildcard<false, WildGroupArgs>, k_wildcard<true, WildGroupArgs>, d, max_records, g, stream);
+	return launch_passes(k_wildcard<false, WildArgs>, k_wildcard<true, WildArgs>, d, max_records, (const WildArgs &)g, stream);
 }

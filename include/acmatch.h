@@ -195,8 +195,8 @@ int acm_automaton_load_position_file(acm_automaton *, const char *path);
  *                                    naming the line, and nothing of the file is applied.  Returns the
  *                                    number of sequences added.  A pure hex line is a 1-part sequence.
  * Not provided: sequences whose parts lie in different calls (a stream cut inside a signature is not
- * joined: scan whole texts), negative distances or overlapping parts, alternatives of more than one byte,
- * where a match begins.  Nibble wildcards and one-byte alternatives: the extended syntax below.  The
+ * joined: scan whole texts), negative distances or overlapping parts, alternatives of unequal length,
+ * where a match begins.  Nibble wildcards and alternatives: the extended syntax below.  The
  * reference-named layer is unchanged. */
 #define ACM_SEQ_MAX_PARTS 32
 #define ACM_GAP_UNBOUNDED INT32_MAX
@@ -250,19 +250,69 @@ int acm_automaton_load_signature_file(acm_automaton *, const char *path, unsigne
  *   (HH|HH|...)   the listed bytes (one entry: an exact byte)        !(HH|...)   every other byte
  * and only * and {...} separate parts.  Every part needs an exact byte and is added with
  * acm_automaton_add_wildcard.  The body begins and ends with a position that is not ??.  Alternatives of more
- * than one byte ((aabb|ccdd)), a ! that no ( follows, a part of more than ACM_WILDCARD_MAX_POSITIONS
- * positions and everything syntax 0 rejects in gap tokens are ACM_ERR_PARSE with the column (a part without
- * an exact byte: the column it begins at).  A body is parsed completely, and the room for its sets checked,
+ * than one byte ((aabb|ccdd): without ACM_SIG_GROUPS, below), a ! that no ( follows, a part of more than
+ * ACM_WILDCARD_MAX_POSITIONS positions and everything syntax 0 rejects in gap tokens are ACM_ERR_PARSE with
+ * the column (a part without an exact byte: the column it begins at).  A body is parsed completely, and the room for its sets checked,
  * before anything is added; a bad line (or a file that needs a 257th set: ACM_ERR_LIMIT) leaves nothing of
  * its file applied.  For a body that holds neither ?? nor a new token both syntaxes add the same patterns
- * and sequence. */
+ * and sequence.
+ * Groups: alternatives of more than one byte.  A wildcard pattern may carry up to ACM_PATTERN_MAX_GROUPS
+ * GROUPS.  A group is a first position `at` (counted from the pattern's first position), a width w,
+ * 2 <= w <= ACM_GROUP_MAX_WIDTH, `count` strings of exactly w bytes each, 1 <= count <=
+ * ACM_GROUP_MAX_ALTERNATIVES (bytes: count * width bytes, string after string), and a negated flag (0 or 1).
+ * It HOLDS at an occurrence iff the w text bytes under the positions [at, at + w) equal one of the strings
+ * (negated: equal none of them).  Groups are ascending and disjoint and lie inside [0, n), and every position
+ * a group covers carries the full set (??): the anchor stays a function of the sets alone, a covered position
+ * is never part of it, and a pattern with a group always has a context.  The pattern matches where every
+ * position holds a byte of its set AND every group holds.  Groups compare raw text bytes (ACM_PATTERN_NOCASE
+ * applies to the anchor alone).  The span keeps its fixed length, so position windows and sequence gaps see a
+ * pattern with groups exactly as above.  Groups do not enter acm_automaton_compile, and an automaton without
+ * any is bit for bit what it is without this interface.
+ *   acm_automaton_add_wildcard_groups  acm_automaton_add_wildcard with groups; ngroups == 0 is exactly that
+ *                                   call.  Beside its errors, ACM_ERR_ARG: ngroups < 0, a null pointer, a width
+ *                                   below 2, count < 1, a flag that is not 0 or 1, a group that leaves [0, n),
+ *                                   overlaps the one in front or is not ascending, a covered position whose
+ *                                   set is not full; ACM_ERR_LIMIT: more groups, a larger width or more
+ *                                   distinct strings than the maxima.  Equal strings of a group are kept once
+ *                                   (the first of them).  On an error nothing is applied.
+ *   acm_automaton_pattern_groups    the number of groups of pattern `index` (negative: a bad index)
+ *   acm_automaton_pattern_group     group j of pattern `index`: at, width, the count of distinct strings, negated
+ *                                   and a borrowed pointer to count * width bytes (any pointer may be NULL)
+ *   acm_automaton_groups            1 if some pattern has a group
+ * ACM_SIG_GROUPS is a second syntax bit, legal only together with ACM_SIG_EXTENDED (alone: ACM_ERR_ARG);
+ * ACM_SIG_EXTENDED alone is exactly what it was.  With both, inside (..) and !(..) every alternative is one
+ * or more hex byte pairs:
+ *   (HHHH|HHHH|...)   one of the listed strings               !(HHHH|...)   none of them
+ * All alternatives of one group have the width of the first: another width is ACM_ERR_PARSE at the column
+ * where that alternative begins.  A width above ACM_GROUP_MAX_WIDTH, more than ACM_GROUP_MAX_ALTERNATIVES
+ * distinct alternatives, or a group beyond ACM_PATTERN_MAX_GROUPS in one part is ACM_ERR_PARSE naming the
+ * column of the ( or !.  Alternatives of one byte are a set position as without the bit; a group that is not
+ * negated and lists one distinct string is that many exact positions (and may be the anchor); nothing is
+ * factored out of the alternatives.  A group may begin or end a body (its positions are not the ?? that
+ * may not), and "every part needs an exact byte" stands.  The parts are added with
+ * acm_automaton_add_wildcard_groups; a refused body, line or file applies nothing.
+ * Not provided: alternatives of unequal length ((aa|bbcc)): the span of a pattern has one length, which is
+ * what lets the position and sequence rules fold it into their tables. */
 #define ACM_WILDCARD_MAX_POSITIONS 4096
-enum { ACM_SIG_EXTENDED = 1 };
+#define ACM_GROUP_MAX_WIDTH 32
+#define ACM_GROUP_MAX_ALTERNATIVES 256
+#define ACM_PATTERN_MAX_GROUPS 16
+enum { ACM_SIG_EXTENDED = 1, ACM_SIG_GROUPS = 2 };
+typedef struct acm_wild_group {
+	int32_t at, width, count, negated;
+	const uint8_t *bytes;   /* count * width bytes */
+} acm_wild_group;
 int acm_automaton_add_wildcard(acm_automaton *, const uint8_t *sets, int n, int iid, unsigned flags);
 int acm_automaton_pattern_wildcard(const acm_automaton *, int index, int *pre, int *post,
     const uint8_t **pre_sets, const uint8_t **post_sets);
 int acm_automaton_wildcards(const acm_automaton *);
 int acm_automaton_wildcard_reach(const acm_automaton *, int *back, int *ahead);
+int acm_automaton_add_wildcard_groups(acm_automaton *, const uint8_t *sets, int n, const acm_wild_group *groups,
+    int ngroups, int iid, unsigned flags);
+int acm_automaton_pattern_groups(const acm_automaton *, int index);
+int acm_automaton_pattern_group(const acm_automaton *, int index, int j, int *at, int *width, int *count,
+    int *negated, const uint8_t **bytes);
+int acm_automaton_groups(const acm_automaton *);
 int acm_automaton_add_signature_ex(acm_automaton *, const char *body, int iid, unsigned flags,
     unsigned syntax);
 int acm_automaton_load_signature_file_ex(acm_automaton *, const char *path, unsigned flags,
