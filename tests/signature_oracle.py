@@ -1,11 +1,17 @@
 """Logical signatures on bytes (test infrastructure only, not a conftest): what a database of
 "expr;body0;body1;..." lines matches in a list of texts, computed with numpy from the text of the lines and
 include/acmatch.h alone.  Nothing here knows of states, records, slots, planes or passes, and nothing is shared
-with the C side; the body grammar is wildcard_model.parse_body_ex and the expression grammar rule_model.parse.
+with the C side; the body grammar is wildcard_model.parse_body_ex (group_model.parse_body_groups for a database with
+groups) and the expression grammar rule_model.parse.
 
   part        a list of 256-entry truth tables, one per position.  It occurs at k iff table[i][T[k + i]] for every
               i, and k .. k + n - 1 lie in one text.  Candidates come from the first position and are thinned by
               the others (the AND over positions of a lookup on the shifted text).
+  group       (at, strings, negated) on a part (acmatch.h, "Groups: alternatives of more than one byte"): after the
+              truth tables have thinned the candidates k, the group holds iff the w bytes T[k + at : k + at + w]
+              equal one of its strings (negated: none).  Raw bytes, whatever the case flag says.  The positions it
+              covers carry the full set and a full set is no one-byte set: they are never part of the anchor, so
+              the anchor, post, nocase and the windows are what they are without the group.
   nocase      acmatch.h: "ACM_PATTERN_NOCASE applies to the anchor only", the anchor being the longest run of
               one-byte positions, the leftmost among equal runs.  Those positions compare through fold(), every
               other position with the raw byte.  (wildcard_model.Pattern.holds folds the same positions.)
@@ -21,6 +27,7 @@ Offsets are those of the concatenation of the texts, as Matcher.pack_segments la
 """
 import numpy as np
 
+import group_model as gm
 import rule_model as rm
 import wildcard_model as wm
 
@@ -47,8 +54,11 @@ def longest_exact_run(sets):
 
 
 class Part:
-    def __init__(self, sets, nocase):
+    """sets: one per position; groups: (at, strings, negated) tuples, at counted from the part's first position"""
+
+    def __init__(self, sets, nocase, groups=()):
         self.sets = sets
+        self.groups = [(int(at), [bytes(x) for x in strings], bool(neg)) for at, strings, neg in groups]
         self.n = len(sets)
         self.at, self.L = longest_exact_run(sets)
         self.post = self.n - self.at - self.L              # positions behind the anchor
@@ -70,9 +80,10 @@ class Part:
 
 class Database:
     """lines: logical signatures; nocase: one flag per SIGNATURE (body), in the order of the file; windows:
-    {(signature, part): (lo, hi or None, from_end)}"""
+    {(signature, part): (lo, hi or None, from_end)}; groups: the bodies are in the grammar with multi-byte alternatives,
+    (aabb|ccdd) and !(aabb|ccdd)"""
 
-    def __init__(self, lines, nocase=None, windows=None):
+    def __init__(self, lines, nocase=None, windows=None, groups=False):
         self.sigs, self.rules = [], []                     # (parts, gaps); (operand signatures, tree)
         self.windows = dict(windows or {})
         for line in lines:
@@ -80,9 +91,9 @@ class Database:
             ops = []
             for b in bodies:
                 q = len(self.sigs)
-                parts, gaps = wm.parse_body_ex(b)
+                parts, gaps, grps = gm.parse_body_groups(b) if groups else wm.parse_body_ex(b) + (None,)
                 nc = bool(nocase[q]) if nocase is not None else False
-                self.sigs.append(([Part(p, nc) for p in parts], gaps))
+                self.sigs.append(([Part(p, nc, grps[j] if grps else ()) for j, p in enumerate(parts)], gaps))
                 ops.append(q)
             self.rules.append((ops, rm.parse(expr, len(ops))))
 
@@ -99,15 +110,29 @@ class Corpus:
         self.tend = np.repeat(self.starts + lens, lens)
 
 
-def occurrences(c, tables):
-    """first positions k at which the tables hold and whose span lies in one text"""
+def group_holds(c, k, group):
+    """per candidate k (the part's first position, its span inside the text): does the group hold there?"""
+    at, strings, negated = group
+    w = len(strings[0])
+    under = c.T[(k + at)[:, None] + np.arange(w)[None, :]]                   # [candidate, byte of the group]
+    one = np.zeros(k.size, dtype=bool)
+    for s in strings:
+        one |= (under == np.frombuffer(s, dtype=np.uint8)[None, :]).all(axis=1)
+    return ~one if negated else one
+
+
+def occurrences(c, tables, groups=()):
+    """first positions k at which the tables hold, whose span lies in one text, and at which every group holds"""
     n = len(tables)
     if c.N < n:
         return np.zeros(0, dtype=np.int64)
     k = np.flatnonzero(tables[0][c.T[:c.N - n + 1]])
     for i in range(1, n):
         k = k[tables[i][c.T[k + i]]]
-    return k[k + n <= c.tend[k]]
+    k = k[k + n <= c.tend[k]]
+    for g in groups:
+        k = k[group_holds(c, k, g)]
+    return k
 
 
 def in_window(c, k, w):
@@ -116,11 +141,12 @@ def in_window(c, k, w):
     return (rel >= lo) & (rel <= hi if hi is not None else True)
 
 
-def sequences(db, texts, nocase=True, windows=True, contexts=True, counts=None, anchors_from=0):
+def sequences(db, texts, nocase=True, windows=True, contexts=True, counts=None, anchors_from=0, groups=True):
     """(ends, anchor_ends, signatures): every match of every signature, sorted by (anchor end, signature).  ends:
-    where the match ends; anchor_ends: where its last part's anchor ends.  nocase / windows / contexts False: the
-    database as if it had none.  counts: a dict that receives what each stage of a record chain sees:
-    "anchors" (anchor occurrences inside a text), "parts" (with their contexts), "windowed" (inside their
+    where the match ends; anchor_ends: where its last part's anchor ends.  nocase / windows / contexts / groups
+    False: the database as if it had none (a group then is as many ?? as it is wide).  counts: a dict that
+    receives what each stage of a record chain sees:
+    "anchors" (anchor occurrences inside a text), "parts" (with their contexts and groups), "windowed" (inside their
     windows), "matches".  anchors_from: only parts whose anchor begins at or behind this offset take part (a scan
     that begins there, with the bytes in front given as context, finds no other)."""
     c = texts if isinstance(texts, Corpus) else Corpus(texts)
@@ -132,7 +158,7 @@ def sequences(db, texts, nocase=True, windows=True, contexts=True, counts=None, 
             tabs = p.tables(nocase, contexts)
             if counts is not None:
                 tally["anchors"] += occurrences(c, tabs[p.at:p.at + p.L]).size
-            k = occurrences(c, tabs)
+            k = occurrences(c, tabs, p.groups if groups and contexts else ())
             k = k[k + p.at >= anchors_from]
             tally["parts"] += k.size
             if windows and (q, j) in db.windows:
@@ -158,6 +184,20 @@ def sequences(db, texts, nocase=True, windows=True, contexts=True, counts=None, 
     if counts is not None:
         counts.update(tally)
     return ends[order], aends[order], sigs[order]
+
+
+def group_decisions(db, texts, nocase=True):
+    """(held, kept): the occurrences of the parts that have a group with their groups taken as ??, and how many
+    of those the groups keep"""
+    c = texts if isinstance(texts, Corpus) else Corpus(texts)
+    held = kept = 0
+    for parts, _ in db.sigs:
+        for p in parts:
+            if p.groups:
+                tabs = p.tables(nocase)
+                held += occurrences(c, tabs).size
+                kept += occurrences(c, tabs, p.groups).size
+    return held, kept
 
 
 def count_matrix(db, c, aends, sigs):
@@ -216,19 +256,65 @@ EDGE_KINDS = ("hi", "lo", "alt", "not", "not2")
 INNER_KINDS = EDGE_KINDS + ("any", "any")
 
 
-def random_part(rng, alphabet=LETTERS, anchor=(2, 4), context=2):
+GROUP_WIDTHS = (2, 3, 4, 5, 8)
+GROUP_PLACES = ("first", "last", "front", "behind", "adjacent", "exact")
+
+
+def random_group(rng, alphabet, kind=None):
+    """(token, strings, negated) of one group.  Widths 2, 3, 4, 5, 8 and one time in ten 31 or 32; 1 to 8 strings
+    and one time in twelve 255 or 256 (of a width up to 5); a group of one string is negated, but for kind "exact":
+    a non-negated group of one string, which the grammar turns into exact bytes.  The first strings are letters
+    of the alphabet (so that text hits them by chance and nocase would matter), the others any bytes."""
+    wide, many = rng.random() < 0.1, rng.random() < 1 / 12
+    w = int(rng.integers(31, 33)) if wide else int(GROUP_WIDTHS[int(rng.integers(len(GROUP_WIDTHS)))])
+    n = int(rng.integers(1, 9))
+    if many and not wide:
+        w, n = min(w, 5), int(rng.integers(255, 257))
+    negated = bool(rng.random() < 0.4)
+    if kind == "exact":
+        n, negated, w = 1, False, min(w, 8)
+    elif n == 1:
+        negated = True
+    pool = np.frombuffer(alphabet, dtype=np.uint8)
+    strings = []
+    while len(strings) < n:
+        s = bytes(rng.choice(pool, size=w)) if len(strings) < 6 else bytes(rng.integers(0, 256, size=w, dtype=np.uint8))
+        if s not in strings:
+            strings.append(s)
+    return ("!(" if negated else "(") + "|".join(s.hex() for s in strings) + ")", strings, negated
+
+
+def random_part(rng, alphabet=LETTERS, anchor=(2, 4), context=2, group_share=0.0, groups_out=None):
     """(body text, sets) of one part: up to `context` positions in front of and behind an anchor of exact bytes,
-    sometimes a ?? and one more exact byte inside; ?? never at an edge"""
+    sometimes a ?? and one more exact byte inside; ?? never at an edge.  group_share: the share of parts that get
+    a group token (two for "adjacent") at one of GROUP_PLACES: as the part's first or last positions, directly in
+    front of or behind the anchor; its positions are full sets, and groups_out receives the (at, strings, negated)
+    of the part.  With a share of 0 no random number is drawn for it."""
     def exact(n):
         bs = [int(x) for x in rng.choice(np.frombuffer(alphabet, dtype=np.uint8), size=n)]
         return [("%02x" % c, frozenset((c,))) for c in bs]
     pre, post = int(rng.integers(0, context + 1)), int(rng.integers(0, context + 1))
     pos = [_position(rng, alphabet, EDGE_KINDS if i == 0 else INNER_KINDS) for i in range(pre)]
     pos += exact(int(rng.integers(anchor[0], anchor[1] + 1)))
+    behind = len(pos)
     if rng.random() < 0.25:
         pos += [("??", wm.FULL)] + exact(1)
     pos += [_position(rng, alphabet, EDGE_KINDS if i == post - 1 else INNER_KINDS) for i in range(post)]
-    return "".join(t for t, _ in pos), [s for _, s in pos]
+    if not group_share or rng.random() >= group_share:
+        return "".join(t for t, _ in pos), [s for _, s in pos]
+    # tokens of one position so far; a group token stands for several
+    place = GROUP_PLACES[int(rng.integers(len(GROUP_PLACES)))]
+    at = {"first": 0, "last": len(pos), "front": pre, "behind": behind}.get(place, (pre, behind, 0, len(pos))[int(rng.integers(4))])
+    new = [random_group(rng, alphabet, place) for _ in range(2 if place == "adjacent" else 1)]
+    toks = [(t, [s], None) for t, s in pos]
+    toks[at:at] = [(t, [frozenset((b,)) for b in strings[0]], None) if place == "exact" else (t, [wm.FULL] * len(strings[0]), (strings, neg))
+                   for t, strings, neg in new]
+    sets = []
+    for _, ss, grp in toks:
+        if grp is not None and groups_out is not None:
+            groups_out.append((len(sets), grp[0], grp[1]))
+        sets += ss
+    return "".join(t for t, _, _ in toks), sets
 
 
 def random_gap(rng, longest=6):
@@ -239,8 +325,9 @@ def random_gap(rng, longest=6):
             ("*", 0, None)][int(rng.integers(5))]
 
 
-def random_body(rng, parts=(1, 4), **kw):
-    """(body, [sets of each part], [(lo, hi)])"""
+def random_body(rng, parts=(1, 4), groups_out=None, **kw):
+    """(body, [sets of each part], [(lo, hi)]); groups_out: a list that receives the groups of each part (with
+    group_share=..., see random_part)"""
     k = int(rng.integers(parts[0], parts[1] + 1))
     body, sets, gaps = "", [], []
     for j in range(k):
@@ -248,28 +335,71 @@ def random_body(rng, parts=(1, 4), **kw):
             tok, lo, hi = random_gap(rng)
             body += tok
             gaps.append((lo, hi))
+        if groups_out is not None:
+            groups_out.append([])
+            kw["groups_out"] = groups_out[-1]
         t, s = random_part(rng, **kw)
         body += t
         sets.append(s)
     return body, sets, gaps
 
 
-def materialise(rng, sets, gaps, alphabet=LETTERS, nocase=False):
-    """bytes that the signature matches from their first to their last byte"""
+def other_than(rng, strings, s, alphabet):
+    """s with one byte changed, its last or for widths above 4 its first, and none of the strings: the bytes a
+    word-wise compare sees last, or that a compare of the first word alone does not see"""
+    i = 0 if len(s) > 4 else len(s) - 1
+    while True:
+        c = int(alphabet[int(rng.integers(len(alphabet)))]) if rng.random() < 0.7 else int(rng.integers(0, 256))
+        t = s[:i] + bytes([c]) + s[i + 1:]
+        if t not in strings:
+            return t
+
+
+def group_bytes(rng, group, alphabet, miss):
+    """the bytes to lay under a group.  It holds: one of the strings of a positive group; for a negated one
+    letters that are none of them, or every other time a string with one byte changed (other_than).  miss, a
+    near miss, it fails: a string of a positive group with one byte changed, a string of a negated one as it is."""
+    _, strings, negated = group
+    s = strings[int(rng.integers(len(strings)))]
+    if negated != miss:                                   # bytes that are none of the strings
+        if negated and rng.random() < 0.5:
+            while True:
+                t = bytes(rng.choice(np.frombuffer(alphabet, dtype=np.uint8), size=len(s)))
+                if t not in strings:
+                    return t
+        return other_than(rng, strings, s, alphabet)
+    return s
+
+
+NEAR_MISS = 0.5     # materialise(near_miss=True): the share of groups under which it lays bytes that fail
+
+
+def materialise(rng, sets, gaps, alphabet=LETTERS, nocase=False, groups=None, near_miss=False):
+    """bytes that the signature matches from their first to their last byte.  groups: per part its (at, strings,
+    negated); near_miss: every position holds a byte of its set, but each group fails with probability NEAR_MISS
+    (and the last one if none did): only the groups decide that this is no match."""
     pool = np.frombuffer(alphabet, dtype=np.uint8)
     out = bytearray()
+    todo = sum(len(g) for g in groups) if groups else 0
+    missed = False
     for j, part in enumerate(sets):
         if j:
             lo, hi = gaps[j - 1]
             n = lo + int(rng.integers(0, 3 if hi is None else min(hi - lo, 2) + 1))
             out += bytes(rng.choice(pool, size=n))
         at, L = longest_exact_run(part)
+        base = len(out)
         for i, s in enumerate(part):
             good = [c for c in alphabet if c in s] or sorted(s)
             c = good[int(rng.integers(len(good)))]
             if nocase and at <= i < at + L and rng.random() < 0.5:
                 c = c ^ 0x20 if 0x41 <= (c & 0xDF) <= 0x5A else c
             out.append(c)
+        for g in groups[j] if groups else ():
+            todo -= 1
+            miss = near_miss and (rng.random() < NEAR_MISS or (todo == 0 and not missed))
+            missed |= miss
+            out[base + g[0]:base + g[0] + len(g[1][0])] = group_bytes(rng, g, alphabet, miss)
     return bytes(out)
 
 
@@ -313,22 +443,32 @@ def _random_text(rng, n, alphabet=ALPHABET):
 
 
 def make(seed, rules=64, texts=3000, total=204 * 1024, empties=2200, long_text=17000, max_ops=8, window_share=0.2,
-         anchor=(5, 6)):
+         anchor=(5, 6), group_share=0.0):
     """about 4.5 * rules signatures of 1 - 4 parts with anchors of 5 or 6 bytes (every pattern has its three bytes:
     the sparse pipeline applies; and a text has fewer anchor records than bytes, which is what acm_grep -Q takes
     per buffer) and a corpus in which every signature is planted: texts that are one match, texts
     that hold all or some operands of a rule, one long text, a run of empty texts, texts of one byte and of exactly
-    one part.  The expressions are drawn last, so that every rule holds in some text and fails in another that has
-    a hit (the draw looks at sequences() of the corpus, never at a device)."""
+    one part.  group_share: that share of the parts carries a group (random_part); the database is then in the
+    grammar with groups, every planted match lays bytes under its groups that hold, and every signature with a
+    group has a text of its own that is a near miss (materialise).  The expressions are drawn last, so that every
+    rule holds in some text and fails in another that has a hit (the draw looks at sequences() of the corpus,
+    never at a device)."""
     rng = np.random.default_rng(seed)
     g = Generated()
     sigs, bodies, ops_of, g.rule_nocase, g.nocase, g.windows = [], [], [], [], [], {}
+    with_groups = group_share > 0
+    g.groups = []                                        # per signature, per part: (at, strings, negated)
     for r in range(rules):
         nc = bool(rng.random() < 0.34)
         g.rule_nocase.append(nc)
         ops = []
         for _ in range(int(rng.integers(1, max_ops + 1))):
-            body, sets, gaps = random_body(rng, parts=(1, 4), alphabet=ALPHABET, anchor=anchor)
+            if with_groups:
+                g.groups.append([])
+                body, sets, gaps = random_body(rng, parts=(1, 4), alphabet=ALPHABET, anchor=anchor, group_share=group_share,
+                                               groups_out=g.groups[-1])
+            else:
+                body, sets, gaps = random_body(rng, parts=(1, 4), alphabet=ALPHABET, anchor=anchor)
             q = len(sigs)
             sigs.append((sets, gaps))
             bodies.append(body)
@@ -344,7 +484,7 @@ def make(seed, rules=64, texts=3000, total=204 * 1024, empties=2200, long_text=1
 
     def planted(q, room=12):
         """a text in which signature q matches inside its window"""
-        inst = materialise(rng, sigs[q][0], sigs[q][1], ALPHABET, g.nocase[q])
+        inst = materialise(rng, sigs[q][0], sigs[q][1], ALPHABET, g.nocase[q], g.groups[q] if with_groups else None)
         lo, hi, from_end = g.windows.get((q, 0), (0, None, False))
         if from_end:
             after = max(lo - len(inst), 0) if hi == lo else int(rng.integers(max(lo - len(inst), 0), max(lo - len(inst), 0) + 3))
@@ -356,7 +496,10 @@ def make(seed, rules=64, texts=3000, total=204 * 1024, empties=2200, long_text=1
     for q in range(len(sigs)):
         out.append(planted(q))
         if q % 5 == 0:
-            out.append(materialise(rng, sigs[q][0][:1], [], ALPHABET, g.nocase[q]))   # exactly one part
+            out.append(materialise(rng, sigs[q][0][:1], [], ALPHABET, g.nocase[q], g.groups[q][:1] if with_groups else None))   # exactly one part
+        if with_groups and any(g.groups[q]):
+            miss = materialise(rng, sigs[q][0], sigs[q][1], ALPHABET, g.nocase[q], g.groups[q], near_miss=True)
+            out.append(_random_text(rng, int(rng.integers(0, 6))) + miss + _random_text(rng, int(rng.integers(0, 6))))
     for ops in ops_of:
         for share in (1.0, 0.6, 0.3):
             t = b""
@@ -380,7 +523,7 @@ def make(seed, rules=64, texts=3000, total=204 * 1024, empties=2200, long_text=1
     g.texts = out[:cut] + [b""] * empties + [bytes(long_one)] + out[cut:]
     # the expressions
     g.db = Database(["%s;%s" % ("|".join("%d" % j for j in range(len(ops))), ";".join(bodies[q] for q in ops)) for ops in ops_of],
-                    g.nocase, g.windows)
+                    g.nocase, g.windows, with_groups)
     c = Corpus(g.texts)
     found = sequences(g.db, c)
     counts = count_matrix(g.db, c, found[1], found[2])
@@ -396,7 +539,7 @@ def make(seed, rules=64, texts=3000, total=204 * 1024, empties=2200, long_text=1
                 expr = e
                 break
         g.lines.append("%s;%s" % (expr or "|".join("%d" % j for j in range(len(ops))), ";".join(bodies[q] for q in ops)))
-    g.db = Database(g.lines, g.nocase, g.windows)
+    g.db = Database(g.lines, g.nocase, g.windows, with_groups)
     return g
 
 

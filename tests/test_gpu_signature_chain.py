@@ -313,11 +313,14 @@ GUARD = 0x3C
 
 
 class Case:
-    """the generated database and corpus, what the oracle says of them, and the models' view of the patterns"""
+    """the generated database and corpus, what the oracle says of them, and the models' view of the patterns.
+    made: another so.make() result than the one of this file (test_gpu_signature_chain_groups.py); groups: its
+    lines are in the grammar with groups"""
 
-    def __init__(self):
+    def __init__(self, made=None, groups=False):
         t0 = time.perf_counter()
-        self.g = g = so.make(SEED, rules=70)
+        self.g = g = so.make(SEED, rules=70) if made is None else made()
+        self.groups = groups
         self.corpus = so.Corpus(g.texts)
         self.counts = {}
         self.found = so.sequences(g.db, self.corpus, counts=self.counts)
@@ -336,7 +339,7 @@ class Case:
         lines = g.lines if lines is None else lines
         rule_nocase = g.rule_nocase if rule_nocase is None else rule_nocase
         for r, line in enumerate(lines):
-            assert a.add_logical_signature(line, iid=r, nocase=rule_nocase[r], extended=True) == r
+            assert a.add_logical_signature(line, iid=r, nocase=rule_nocase[r], extended=True, groups=self.groups) == r
         if extra is not None:
             a.add(extra, 0)
         a.compile()

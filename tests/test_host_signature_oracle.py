@@ -7,12 +7,18 @@ rule_model.parse / evaluate, as 1 does; only 2 shares no body parser, and only t
      alone, and "a match ends at e" is fullmatch(text, 0, e + 1) of .*? + body
   3. the hand-derived expectations that test_gpu_rules.test_scan_rules and
      test_gpu_wildcards.test_scan_sequences_extended assert of the device
+Bodies with groups, (aabb|ccdd) and !(aabb|ccdd), go the same three ways: the oracle shares only the grammar
+(group_model.parse_body_groups) with 1, whose Patterns ask group_model.group_holds offset by offset; 2 is
+group_model.body_regex, a translation of the body text; 3 are the texts of test_gpu_groups.test_span_rules_by_hand
+and the body of test_the_issue_body.
 No GPU: only the host library (the parsers of rule_model and wildcard_model are Python)."""
+import hashlib
 import re
 
 import numpy as np
 import pytest
 
+import group_model as gm
 import rule_model as rm
 import signature_oracle as so
 import wildcard_model as wm
@@ -20,16 +26,23 @@ import wildcard_model as wm
 CASES = 240
 
 
-def random_case(seed):
-    """(lines, nocase per signature, windows, texts)"""
+def random_case(seed, group_share=0.0):
+    """(lines, nocase per signature, windows, texts); group_share > 0: a fifth value, the groups per signature and
+    part, and some texts are near misses of a signature's groups"""
     rng = np.random.default_rng(seed)
+    groups = []
     alphabet = so.LETTERS[:int(rng.integers(3, 6))]
     lines, nocase, windows, sigs = [], [], {}, []
     for _ in range(int(rng.integers(1, 4))):
         nops = int(rng.integers(1, 4))
         bodies = []
         for _ in range(nops):
-            body, sets, gaps = so.random_body(rng, parts=(1, 3), alphabet=alphabet, anchor=(1, 3))
+            if group_share:
+                groups.append([])
+                body, sets, gaps = so.random_body(rng, parts=(1, 3), alphabet=alphabet, anchor=(1, 3), group_share=group_share,
+                                                  groups_out=groups[-1])
+            else:
+                body, sets, gaps = so.random_body(rng, parts=(1, 3), alphabet=alphabet, anchor=(1, 3))
             q = len(sigs)
             nocase.append(bool(rng.random() < 0.3))
             sigs.append((sets, gaps))
@@ -47,14 +60,20 @@ def random_case(seed):
         if kind < 0.7:                                  # one or two planted matches; kind < 0.15: nothing around them
             for _ in range(int(rng.integers(1, 3))):
                 q = int(rng.integers(len(sigs)))
-                inst = so.materialise(rng, sigs[q][0], sigs[q][1], alphabet, nocase[q])
+                if group_share:
+                    inst = so.materialise(rng, sigs[q][0], sigs[q][1], alphabet, nocase[q], groups[q],
+                                          near_miss=any(groups[q]) and rng.random() < 0.4)
+                else:
+                    inst = so.materialise(rng, sigs[q][0], sigs[q][1], alphabet, nocase[q])
                 t = inst if kind < 0.15 else t + inst + bytes(rng.choice(pool, size=int(rng.integers(0, 8))))
         texts.append(t[:120])
     texts.insert(int(rng.integers(len(texts))), b"")
+    if group_share:
+        return lines, nocase, windows, texts, groups
     return lines, nocase, windows, texts
 
 
-def by_model(lines, nocase, windows, texts):
+def by_model(lines, nocase, windows, texts, groups=False):
     """(sorted (end, signature), sorted (rule, text, offset)) by span_sequences and RuleModel"""
     pats, seqs, rules, win = [], [], [], {}
     for line in lines:
@@ -62,12 +81,12 @@ def by_model(lines, nocase, windows, texts):
         ops = []
         for b in bodies:
             q = len(seqs)
-            parts, gaps = wm.parse_body_ex(b)
+            parts, gaps, grps = gm.parse_body_groups(b) if groups else wm.parse_body_ex(b) + (None,)
             for j in range(len(parts)):
                 if (q, j) in windows:
                     win[len(pats) + j] = windows[q, j]
             seqs.append((list(range(len(pats), len(pats) + len(parts))), gaps))
-            pats += [wm.Pattern(p, nocase[q]) for p in parts]
+            pats += [gm.Pattern(p, grps[j], nocase[q]) if groups else wm.Pattern(p, nocase[q]) for j, p in enumerate(parts)]
             ops.append(q)
         rules.append((ops, expr))
     found = sorted(wm.span_sequences(pats, seqs, texts, win))
@@ -78,8 +97,8 @@ def by_model(lines, nocase, windows, texts):
     return found, sorted(zip(er.tolist(), et.tolist(), eo.tolist()))
 
 
-def by_oracle(lines, nocase, windows, texts, **kw):
-    db = so.Database(lines, nocase, windows)
+def by_oracle(lines, nocase, windows, texts, db_groups=False, **kw):
+    db = so.Database(lines, nocase, windows, db_groups)
     m = so.sequences(db, texts, **kw)
     return sorted(zip(m[0].tolist(), m[2].tolist())), so.rules(db, texts, m)
 
@@ -150,6 +169,119 @@ def test_against_the_models_and_re():
     # in which the windows and the case flags decide
     assert seen["matches"] > 10 * CASES and seen["cases_with_rules"] > CASES // 2 and seen["last"] > CASES // 2
     assert seen["first"] > 20 and seen["windows"] > 20 and seen["nocase"] > 20, seen
+
+
+def digest(g):
+    h = hashlib.sha256()
+    for part in ("\n".join(g.lines).encode(), b"".join(len(t).to_bytes(4, "little") + t for t in g.texts),
+                 repr(sorted(g.windows.items())).encode(), repr((g.nocase, g.rule_nocase)).encode()):
+        h.update(hashlib.sha256(part).digest())
+    return h.hexdigest()
+
+
+def test_the_generator_without_groups_is_what_it_was():
+    """make() with the share of groups at its default of 0 draws the random numbers it drew before it knew groups:
+    the digest is that of the lines, texts, windows and case flags the module gave before (computed with it), the
+    database of tests/test_gpu_signature_chain.py, whose seeded counts rest on it"""
+    g = so.make(1, rules=70)
+    assert digest(g) == "6287609dbe7ac9663aca6d420695450bb48b85f9260fe905e3ff0baaee35a496"
+    assert not any(p.groups for parts, _ in g.db.sigs for p in parts)
+    assert digest(so.make(1, rules=8, texts=300, total=20 * 1024, empties=100, long_text=2000, group_share=0.45)) != digest(
+        so.make(1, rules=8, texts=300, total=20 * 1024, empties=100, long_text=2000))
+
+
+GROUP_CASES = 200
+
+
+def test_groups_against_the_models_and_re():
+    """bodies of which half the parts carry a group: the oracle against span_sequences over group_model.Patterns with
+    RuleModel, against re through group_model.body_regex, and against itself with the groups off"""
+    seen = dict(matches=0, rules=0, dropped=0, rules_differ=0, negated=0, positive=0, exact=0, wide=0, many=0, adjacent=0,
+                first=0, last=0, nocase=0, window_on_group=0)
+    for seed in range(GROUP_CASES):
+        lines, nocase, windows, texts, groups = random_case(1000 + seed, group_share=0.5)
+        found, fired = by_oracle(lines, nocase, windows, texts, db_groups=True)
+        xfound, xfired = by_model(lines, nocase, windows, texts, groups=True)
+        assert found == xfound, (seed, lines, sorted(set(found) ^ set(xfound))[:5])
+        assert fired == xfired, (seed, lines, sorted(set(fired) ^ set(xfired))[:5])
+        plain = lambda q: not nocase[q] and (q, 0) not in windows
+        base, want, bodies = 0, set(), [b for line in lines for b in so.split_line(line)[1]]
+        for t in texts:
+            for q, body in enumerate(bodies):
+                if plain(q):
+                    want |= {(base + e, q) for e in gm.regex_ends(body, t)}
+            base += len(t)
+        assert {x for x in found if plain(x[1])} == want, (seed, lines)
+        # the groups off: what the same database matches with ?? in their place, a superset
+        loose, lfired = by_oracle(lines, nocase, windows, texts, db_groups=True, groups=False)
+        assert set(found) <= set(loose)
+        db = so.Database(lines, nocase, windows, True)
+        for q, (parts, _) in enumerate(db.sigs):           # the generator's record of the groups is the parser's
+            assert [p.groups for p in parts] == [[(at, list(ss), neg) for at, ss, neg in gs] for gs in groups[q]], (seed, q)
+            for j, p in enumerate(parts):
+                for at, strings, neg in p.groups:
+                    seen["negated" if neg else "positive"] += 1
+                    seen["wide"] += len(strings[0]) >= 31
+                    seen["many"] += len(strings) >= 255
+                    seen["first"] += at == 0
+                    seen["last"] += at + len(strings[0]) == p.n
+                    seen["nocase"] += nocase[q]
+                    seen["window_on_group"] += at == 0 and (q, j) in windows
+                seen["adjacent"] += any(a[0] + len(a[1][0]) == b[0] for a, b in zip(p.groups, p.groups[1:]))
+        seen["exact"] += sum(len(re.findall(r"(?<!!)\((?:[0-9a-f]{2}){2,}\)", b)) for b in bodies)      # one string: exact bytes
+        seen["matches"] += len(found)
+        seen["rules"] += len(fired)
+        seen["dropped"] += len(loose) - len(found)
+        seen["rules_differ"] += fired != lfired
+    assert seen["matches"] > 5 * GROUP_CASES and seen["dropped"] > GROUP_CASES and seen["rules_differ"] > 20, seen
+    assert min(seen["negated"], seen["positive"], seen["first"], seen["last"], seen["nocase"]) > 40, seen
+    assert min(seen["wide"], seen["many"], seen["adjacent"], seen["window_on_group"], seen["exact"]) >= 5, seen
+    print(seen)
+
+
+def hits(bodies, texts, **kw):
+    """sorted (offset at which the last part's ANCHOR ends, signature) of bodies with groups"""
+    db = so.Database(["%s;%s" % ("|".join("%d" % j for j in range(len(bodies))), ";".join(bodies))], groups=True)
+    _, aends, sigs = so.sequences(db, texts, **kw)
+    return sorted(zip(aends.tolist(), sigs.tolist()))
+
+
+def test_the_hand_derived_expectations_of_the_group_tests():
+    # test_gpu_groups.test_span_rules_by_hand: its three patterns as bodies, its texts and what it derives by hand
+    edge = ["(6378|7863)6262", "6262(6362|6262)", "!(637863)6262"]
+    text = b"cxbbcbbbb"                                                   # bb ends at 3, 6, 7, 8
+    assert hits(edge, [text]) == [(3, 0), (3, 1), (6, 1), (6, 2), (7, 2), (8, 2)]
+    assert (7, 1) not in hits(edge, [text])                              # its group would need the byte at 9
+    recs = hits(edge, [text[:1], text[1:]])                              # a text that starts at 1
+    assert (3, 0) not in recs and (3, 1) in recs
+    recs = hits(edge, [text[:5], text[5:]])                              # texts [0, 5) and [5, 9)
+    assert (3, 1) not in recs and (3, 0) in recs and (6, 2) not in recs and (8, 2) not in recs
+    for t, want in ((b"cxcbb", [(4, 0)]), (b"qxcbb", [(4, 0), (4, 2)]), (b"\x00xcbb", [(4, 0), (4, 2)]), (b"cqcbb", [(4, 2)]),
+                    (b"c\x00cbb", [(4, 2)]), (b"zzcxcbb", [(6, 0)])):
+        assert hits(edge, [t]) == want, t
+    # with the groups off every bb with enough bytes around it is a hit
+    assert hits(edge, [text], groups=False) == [(3, 0), (3, 1), (6, 0), (6, 1), (6, 2), (7, 0), (7, 2), (8, 0), (8, 2)]
+    # the body of test_gpu_groups.test_the_issue_body, on its texts against re and on two texts by hand
+    body = "aa(bbcc|ddee)ff*!(0102|0304)11"
+    rng = np.random.default_rng(2)
+    menu = [bytes.fromhex(x) for x in ("aabbccff", "aaddeeff", "aabbeeff", "010211", "030411", "010411", "ff11", "00", "aa")]
+    texts = [b"".join(menu[int(k)] for k in rng.integers(0, len(menu), size=int(rng.integers(0, 14)))) for _ in range(30)]
+    want, base = [], 0
+    for t in texts:
+        want += [(base + o, 0) for o in gm.regex_ends(body, t)]
+        base += len(t)
+    assert len(want) > 20 and hits([body], texts) == sorted(want)
+    assert hits([body], [bytes.fromhex("aabbccff00010311")]) == [(7, 0)]
+    assert hits([body], [bytes.fromhex("aaddeeff010211aabbccff03041111")]) == [(14, 0)]
+    assert hits([body], [bytes.fromhex("aabbccff"), bytes.fromhex("010311")]) == []
+    counts, loose = {}, {}
+    so.sequences(so.Database(["0;" + body], groups=True), texts, counts=counts)
+    so.sequences(so.Database(["0;" + body], groups=True), texts, counts=loose, groups=False)
+    assert loose["anchors"] == counts["anchors"] and loose["parts"] > counts["parts"] > 0
+    with pytest.raises(gm.BodyError):
+        so.Database(["0;" + body])                       # the grammar without groups refuses it
+    with pytest.raises(gm.BodyError):
+        so.Database(["0;aa(bbcc|dd)"], groups=True)
 
 
 def test_the_hand_derived_expectations_of_the_device_tests():
