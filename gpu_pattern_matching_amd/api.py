@@ -3,6 +3,7 @@
 Used by tests/ and bench.py.  Everything that computes runs in libacmatch.so
 on the GPU; this module only moves bytes and keeps handles alive.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -440,6 +441,162 @@ class Automaton:
             pass
 
 
+def _host_bytes(x):
+    """contiguous uint8 array of host bytes: bytes, bytearray, memoryview or an array"""
+    return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) \
+        else np.ascontiguousarray(x, dtype=np.uint8)
+
+
+class _Pipeline:
+    """One convenience call of a Matcher (scan_*), as a context manager.  It owns the text, `before` and starts
+    on the device and every DeviceArray it hands out, and frees them all on the way out, raised or not.  It
+    carries the current planes (pat, off: room cells, max_records of them to read, in report form); a stage
+    enqueues one pass over them into planes of its own and makes those current.  Everything is on the matcher's
+    stream.  A stage is sized by max_records: where the one in front left fewer, the caller reads the count
+    (count(): the host waits there) and sets max_records from it."""
+
+    def __init__(self, m, where, text=None, texts=None, segments=None, before=b""):
+        self.m, self.where, self.stream, self.bufs = m, where, m.stream, []
+        if texts is not None:
+            self.t, self.starts = m.pack_segments(texts)
+        else:
+            self.t = _host_bytes(text)
+            self.starts = np.ascontiguousarray(segments if segments is not None else [], dtype=np.int32)
+        self.bf = np.frombuffer(bytes(before), dtype=np.uint8)
+        self.n, self.nseg, self.before_len = int(self.t.size), int(self.starts.size), int(self.bf.size)
+
+    def __enter__(self):
+        m = self.m
+        m.reserve(max(self.n, 1))
+        self.cap = m.plane_capacity
+        self._advance(m.pat_plane, m.off_plane, self.cap, _lib.REPORT_STATE)
+        try:
+            self.d = self.upload(self.t)
+            self.d_bf = self.upload(self.bf) if self.before_len else None
+            self.d_st = self.upload(self.starts, pad_to=0) if self.nseg else None
+        except BaseException:
+            self.__exit__()
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        for b in self.bufs:
+            b.free()
+
+    def _advance(self, pat, off, room, report):
+        self.pat, self.off, self.room, self.max_records, self.report = pat, off, room, room - 2, report
+
+    # ---- device memory, freed on the way out
+
+    def alloc(self, nbytes):
+        self.bufs.append(DeviceArray(nbytes))
+        return self.bufs[-1]
+
+    def upload(self, a, pad_to=16):
+        self.bufs.append(DeviceArray.from_numpy(a, pad_to=pad_to, stream=self.stream))
+        return self.bufs[-1]
+
+    def planes(self, cells, k=2):
+        return [self.alloc(cells * 4) for _ in range(k)]
+
+    def workspace(self, query, *args):
+        """(ptr, nbytes) of a block of query(*args) bytes, as the *_async calls take it"""
+        nb = query(*args)
+        return self.alloc(max(nb, 16)).ptr, nb
+
+    # ---- stages: cells is the room of the planes the stage writes; ws a workspace() made earlier
+
+    def scan(self, init_state=0, report=_lib.REPORT_STATE):
+        self.m.scan_async(self.d, self.n, init_state, report=report)
+
+    def segment(self, report=_lib.REPORT_STATE, seg_start=None, segments=None, seg_out=None, seg_counts=None, ws=None):
+        """clamp every record to its own text: by default the call's starts, in STATE form for the next stage"""
+        ws = ws or self.workspace(self.m.lib.acm_segment_workspace_bytes, self.max_records)
+        pat, off = self.planes(self.cap)
+        self.m.segment_async(self.pat, self.off, self.max_records, self.d_st if seg_start is None else seg_start,
+                             self.nseg if segments is None else segments, self.n, pat, off, self.cap, seg_out=seg_out,
+                             seg_counts=seg_counts, report=report, workspace=ws)
+        self._advance(pat, off, self.cap, report)
+
+    def expand(self, cells, ws=None):
+        ws = ws or self.workspace(self.m.lib.acm_expand_workspace_bytes, self.max_records)
+        pat, off = self.planes(cells)
+        check(self.m.lib.acm_expand_matches_async(self.m.dfa, _ptr(self.pat), _ptr(self.off), self.max_records, pat.ptr,
+                                                  off.ptr, cells, ws[0], ws[1], self.stream), "acm_expand_matches_async")
+        self._advance(pat, off, cells, _lib.REPORT_HEAD)
+
+    def every_pattern(self, cells):
+        """every pattern of every record: the case pass when the matcher is mixed, else the expansion"""
+        if self.m.mixed:
+            self.case(cells, True)
+        else:
+            self.expand(cells)
+
+    def word(self, cells, all_patterns, next_byte=-1, word_mask=None, ws=None):
+        ws = ws or self.workspace(self.m.lib.acm_word_workspace_bytes, self.max_records)
+        pat, off = self.planes(cells)
+        self.m.word_async(self.pat, self.off, self.max_records, self.d, 0, self.n, pat, off, cells, before=self.d_bf,
+                          before_len=self.before_len, next_byte=next_byte, seg_start=self.d_st, segments=self.nseg,
+                          word_mask=word_mask, all_patterns=all_patterns, workspace=ws)
+        self._advance(pat, off, cells, _lib.REPORT_HEAD)
+
+    def case(self, cells, all_patterns, ws=None):
+        ws = ws or self.workspace(self.m.lib.acm_case_workspace_bytes, self.max_records)
+        pat, off = self.planes(cells)
+        self.m.case_async(self.pat, self.off, self.max_records, self.d, 0, self.n, pat, off, cells, before=self.d_bf,
+                          before_len=self.before_len, all_patterns=all_patterns, workspace=ws)
+        self._advance(pat, off, cells, _lib.REPORT_HEAD)
+
+    def wildcard(self, cells, info, all_patterns, lead_begin):
+        ws = self.workspace(self.m.lib.acm_wildcard_workspace_bytes, self.max_records)
+        pat, off = self.planes(cells)
+        self.m.wildcard_async(self.pat, self.off, self.max_records, self.d, 0, self.n, pat, off, cells, info,
+                              report=self.report, before=self.d_bf, before_len=self.before_len, seg_start=self.d_st,
+                              segments=self.nseg, lead_begin=lead_begin, open_end=self.n, all_patterns=all_patterns,
+                              workspace=ws)
+        self._advance(pat, off, cells, _lib.REPORT_HEAD)
+
+    def position(self, cells, info, all_patterns, lead_begin, open_end, ws=None):
+        ws = ws or self.workspace(self.m.lib.acm_position_workspace_bytes, self.max_records)
+        pat, off = self.planes(cells)
+        self.m.position_async(self.pat, self.off, self.max_records, pat, off, cells, info, report=self.report,
+                              seg_start=self.d_st, segments=self.nseg, lead_begin=lead_begin, text_end=self.n,
+                              open_end=open_end, all_patterns=all_patterns, workspace=ws)
+        self._advance(pat, off, cells, _lib.REPORT_HEAD)
+
+    def sequence(self, cells, info, lead_begin):
+        ws = self.workspace(self.m.lib.acm_sequence_workspace_bytes, self.m.dfa, self.max_records)
+        seq, off = self.planes(cells)
+        self.m.sequence_async(self.pat, self.off, self.max_records, seq, off, cells, info, seg_start=self.d_st,
+                              segments=self.nseg, lead_begin=lead_begin, text_end=self.n, workspace=ws)
+        self._advance(seq, off, cells, _lib.REPORT_HEAD)
+
+    def rule(self, cells, info):
+        """the current planes become (rule, offset); returns the third, the text of every record"""
+        ws = self.workspace(self.m.lib.acm_rule_workspace_bytes, self.m.dfa, self.max_records)
+        rule, text, off = self.planes(cells, 3)
+        self.m.rule_async(self.pat, self.off, self.max_records, rule, text, off, cells, info, seg_start=self.d_st,
+                          segments=self.nseg, workspace=ws)
+        self._advance(rule, off, cells, _lib.REPORT_HEAD)
+        return text
+
+    # ---- results
+
+    def count(self):
+        """the records in the current planes, from the header cell: the host waits for the stream here"""
+        n = int(self.pat.to_numpy(np.int32, 1, stream=self.stream)[0])
+        if n > self.room - 2:
+            raise AcmError(_lib.ACM_ERR_CAPACITY, self.where, "%d records but planes hold %d" % (n, self.room - 2))
+        return n
+
+    def download(self, n, *more):
+        """(offsets uint32, cells int32, trailer) of the n records of the current planes, then the cells of
+        every further plane given"""
+        p, o = (x.to_numpy(np.int32, n + 2, stream=self.stream) for x in (self.pat, self.off))
+        return (o[1:1 + n].astype(np.uint32), p[1:1 + n].copy(), int(p[n + 1])) + \
+            tuple(x.to_numpy(np.int32, n + 2, stream=self.stream)[1:1 + n].copy() for x in more)
+
+
 class Matcher:
     """Device DFA + scratch + result planes for texts up to max_text bytes."""
 
@@ -536,28 +693,20 @@ class Matcher:
         record_after_walk: hipEvent_t handles chaining the walk kernels of batches that are in
         flight on different streams (acm_scan_batch_async).
         """
-        if wait_before_walk is not None or record_after_walk is not None or report:
-            if workspace is None and n > self.max_text:
-                raise ValueError("text of %d bytes exceeds reserved %d" % (n, self.max_text))
-            st = stream if stream is not None else self.stream
-            ws_ptr, ws_bytes = workspace if workspace is not None else (self.ws.ptr, self.ws_bytes)
-            b = _lib.ScanBatch(_ptr(d_text), n, halo, offset_shift, init_state, _ptr(ws_ptr), ws_bytes,
-                               _ptr(pat_plane) if pat_plane is not None else self.pat_plane.ptr,
-                               _ptr(off_plane) if off_plane is not None else self.off_plane.ptr,
-                               plane_capacity if plane_capacity is not None else self.plane_capacity,
-                               st, wait_before_walk, record_after_walk, report)
-            check(self.lib.acm_scan_batch_async(self.dfa, C.byref(b)), "acm_scan_batch_async")
-            return
         if workspace is None and n > self.max_text:
             raise ValueError("text of %d bytes exceeds reserved %d" % (n, self.max_text))
         st = stream if stream is not None else self.stream
         ws_ptr, ws_bytes = workspace if workspace is not None else (self.ws.ptr, self.ws_bytes)
-        check(self.lib.acm_scan_shard_async(self.dfa, _ptr(d_text), n, halo, offset_shift, init_state,
-                                      _ptr(ws_ptr), ws_bytes,
-                                      _ptr(pat_plane) if pat_plane is not None else self.pat_plane.ptr,
-                                      _ptr(off_plane) if off_plane is not None else self.off_plane.ptr,
-                                      plane_capacity if plane_capacity is not None
-                                      else self.plane_capacity, st), "acm_scan_async")
+        pat = _ptr(pat_plane) if pat_plane is not None else self.pat_plane.ptr
+        off = _ptr(off_plane) if off_plane is not None else self.off_plane.ptr
+        cap = plane_capacity if plane_capacity is not None else self.plane_capacity
+        if wait_before_walk is not None or record_after_walk is not None or report:
+            b = _lib.ScanBatch(_ptr(d_text), n, halo, offset_shift, init_state, _ptr(ws_ptr), ws_bytes, pat, off, cap,
+                               st, wait_before_walk, record_after_walk, report)
+            check(self.lib.acm_scan_batch_async(self.dfa, C.byref(b)), "acm_scan_batch_async")
+            return
+        check(self.lib.acm_scan_shard_async(self.dfa, _ptr(d_text), n, halo, offset_shift, init_state, _ptr(ws_ptr),
+                                            ws_bytes, pat, off, cap, st), "acm_scan_async")
 
     def make_batch(self, d_text, n, stream, pat_plane, off_plane, plane_capacity, workspace, init_state=0, halo=0,
                    offset_shift=0, report=0, profile=False, init_plane=None, init_plane_capacity=0):
@@ -601,28 +750,26 @@ class Matcher:
         """All-patterns reporting: scan with the final states in the pattern
         plane, expand every state's match list on the device (acm_expand_matches_async), download.
         Returns (offsets, patterns, last_state) with one record per pattern ending at each offset."""
-        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
-            else np.ascontiguousarray(text, dtype=np.uint8)
-        self.reserve(max(t.size, 1))
-        d = DeviceArray.from_numpy(t, stream=self.stream)
-        cap = out_capacity if out_capacity is not None else 8 * self.plane_capacity
-        max_records = self.plane_capacity - 2
-        ws_bytes = self.lib.acm_expand_workspace_bytes(max_records)
-        ws, pat, off = DeviceArray(ws_bytes), DeviceArray(cap * 4), DeviceArray(cap * 4)
+        with _Pipeline(self, "Matcher.scan_all", text) as p:
+            ws = p.workspace(self.lib.acm_expand_workspace_bytes, p.max_records)
+            p.scan(init_state)
+            p.expand(out_capacity if out_capacity is not None else 8 * p.cap, ws)
+            return p.download(p.count())
+
+    @contextlib.contextmanager
+    def _workspace(self, workspace, stream, query, *args):
+        """(ptr, nbytes) for one pass: the caller's, or with None a temporary block of query(*args) bytes that
+        lives until the stream has passed it: on the way out, raised or not, the stream is synchronised"""
+        if workspace is not None:
+            yield workspace
+            return
+        nb = query(*args)
+        tmp = DeviceArray(max(nb, 16))
         try:
-            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
-            check(self.lib.acm_expand_matches_async(self.dfa, self.pat_plane.ptr, self.off_plane.ptr, max_records,
-                                                    pat.ptr, off.ptr, cap, ws.ptr, ws_bytes, self.stream),
-                  "acm_expand_matches_async")
-            m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
-            if m > cap - 2:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_all", "%d records but planes hold %d" % (m, cap - 2))
-            p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
-            o = off.to_numpy(np.int32, m + 2, stream=self.stream)
-            return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1])
+            yield tmp.ptr, nb
         finally:
-            for b in (d, ws, pat, off):
-                b.free()
+            check(self.lib.acm_rt_stream_sync(stream), "acm_rt_stream_sync")
+            tmp.free()
 
     def segment_async(self, state_plane, off_plane, max_records, seg_start, segments, text_end, pat_out, off_out,
                       out_capacity, seg_out=None, seg_counts=None, report=0, workspace=None, stream=None):
@@ -631,20 +778,11 @@ class Matcher:
         [segments] (None when segments == 0).  workspace: (ptr, nbytes), or None for a temporary one
         that lives until the stream has passed it (the call then synchronises)."""
         st = stream if stream is not None else self.stream
-        tmp = None
-        if workspace is None:
-            nb = self.lib.acm_segment_workspace_bytes(max_records)
-            tmp = DeviceArray(max(nb, 16))
-            workspace = (tmp.ptr, nb)
-        try:
+        with self._workspace(workspace, st, self.lib.acm_segment_workspace_bytes, max_records) as (ws, nb):
             check(self.lib.acm_segment_matches_async(
                 self.dfa, _ptr(state_plane), _ptr(off_plane), max_records, _ptr(seg_start), segments, text_end,
                 report, _ptr(pat_out), _ptr(off_out), _ptr(seg_out), out_capacity, _ptr(seg_counts),
-                _ptr(workspace[0]), workspace[1], st), "acm_segment_matches_async")
-        finally:
-            if tmp is not None:
-                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
-                tmp.free()
+                _ptr(ws), nb, st), "acm_segment_matches_async")
 
     @staticmethod
     def pack_segments(texts):
@@ -667,57 +805,28 @@ class Matcher:
         offsets in the coordinates of the concatenation; with counts=True also the records per text.
         Records before the first start continue a text that init_state was in (segment -1).
         all_patterns: every pattern of each record's clamped state (acm_expand_matches_async)."""
-        t, starts = self.pack_segments(texts)
-        self.reserve(max(t.size, 1))
-        d = DeviceArray.from_numpy(t, stream=self.stream)
-        nseg = int(starts.size)
-        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
-        max_records = self.plane_capacity - 2
-        cap = self.plane_capacity
-        seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
-        bufs = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4), DeviceArray(cap * 4),
-                DeviceArray(max(nseg, 1) * 4)]
-        ws, pat, off, seg, cnt = bufs
-        bufs += [d] + ([d_st] if d_st is not None else [])
-        try:
-            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
-            self.segment_async(self.pat_plane, self.off_plane, max_records, d_st, nseg, t.size, pat, off, cap,
-                               seg_out=seg, seg_counts=cnt if nseg else None,
-                               report=_lib.REPORT_STATE if all_patterns else _lib.REPORT_HEAD,
-                               workspace=(ws.ptr, seg_ws))
-            m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
-            if m > cap - 2:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_segments", "%d records but planes hold %d"
-                               % (m, cap - 2))
+        with _Pipeline(self, "Matcher.scan_segments", texts=texts) as p:
+            nseg = p.nseg
+            ws = p.workspace(self.lib.acm_segment_workspace_bytes, p.max_records)
+            seg, cnt = p.alloc(p.cap * 4), p.alloc(max(nseg, 1) * 4)
+            p.scan(init_state)
+            p.segment(_lib.REPORT_STATE if all_patterns else _lib.REPORT_HEAD, seg_out=seg,
+                      seg_counts=cnt if nseg else None, ws=ws)
+            m = p.count()
             if not all_patterns:
-                p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
-                o = off.to_numpy(np.int32, m + 2, stream=self.stream)
-                sg = seg.to_numpy(np.int32, m + 2, stream=self.stream)
-                res = (o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), sg[1:1 + m].copy(), int(p[m + 1]))
+                offs, pats, last, sg = p.download(m, seg)
+                res = (offs, pats, sg, last)
                 if counts:
                     res += (cnt.to_numpy(np.int32, nseg, stream=self.stream),)
                 return res
-            acap = out_capacity if out_capacity is not None else 8 * cap
-            ex_ws = self.lib.acm_expand_workspace_bytes(max(m, 1))
-            xb = [DeviceArray(ex_ws), DeviceArray(acap * 4), DeviceArray(acap * 4)]
-            bufs += xb
-            check(self.lib.acm_expand_matches_async(self.dfa, pat.ptr, off.ptr, max(m, 1), xb[1].ptr, xb[2].ptr,
-                                                    acap, xb[0].ptr, ex_ws, self.stream), "acm_expand_matches_async")
-            n = int(xb[1].to_numpy(np.int32, 1, stream=self.stream)[0])
-            if n > acap - 2:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_segments", "%d records but planes hold %d"
-                               % (n, acap - 2))
-            p = xb[1].to_numpy(np.int32, n + 2, stream=self.stream)
-            o = xb[2].to_numpy(np.int32, n + 2, stream=self.stream)
-            offs = o[1:1 + n].astype(np.uint32)
-            sg = (np.searchsorted(starts, offs.astype(np.int64), side="right") - 1).astype(np.int32)
-            res = (offs, p[1:1 + n].copy(), sg, int(p[n + 1]))
+            p.max_records = max(m, 1)
+            p.expand(out_capacity if out_capacity is not None else 8 * p.cap)
+            offs, pats, last = p.download(p.count())
+            sg = (np.searchsorted(p.starts, offs.astype(np.int64), side="right") - 1).astype(np.int32)
+            res = (offs, pats, sg, last)
             if counts:
                 res += (np.bincount(sg[sg >= 0], minlength=nseg).astype(np.int32)[:nseg],)
             return res
-        finally:
-            for b in bufs:
-                b.free()
 
     @staticmethod
     def word_mask(word_set):
@@ -740,26 +849,17 @@ class Matcher:
         word_mask: 32 bytes (Matcher.word_mask) or None for [0-9A-Za-z_].  workspace: (ptr, nbytes), or
         None for a temporary one that lives until the stream has passed it (the call then synchronises)."""
         st = stream if stream is not None else self.stream
-        tmp = None
-        if workspace is None:
-            nb = self.lib.acm_word_workspace_bytes(max_records)
-            tmp = DeviceArray(max(nb, 16))
-            workspace = (tmp.ptr, nb)
         mask = None
         if word_mask is not None:
             if len(word_mask) != 32:
                 raise ValueError("word_mask must be 32 bytes")
             mask = C.create_string_buffer(bytes(word_mask), 32)
-        try:
+        with self._workspace(workspace, st, self.lib.acm_word_workspace_bytes, max_records) as (ws, nb):
             check(self.lib.acm_word_matches_async(
                 self.dfa, _ptr(state_plane), _ptr(off_plane), max_records, _ptr(d_text), text_origin, text_end,
                 _ptr(before), before_len, next_byte, _ptr(seg_start), segments, mask, 1 if all_patterns else 0,
-                _ptr(pat_out), _ptr(off_out), out_capacity, _ptr(tail_out), _ptr(workspace[0]), workspace[1], st),
+                _ptr(pat_out), _ptr(off_out), out_capacity, _ptr(tail_out), _ptr(ws), nb, st),
                 "acm_word_matches_async")
-        finally:
-            if tmp is not None:
-                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
-                tmp.free()
 
     def scan_words(self, text, all_patterns=False, word_set=None, segments=None, init_state=0, before=b"",
                    next_byte=-1, out_capacity=None):
@@ -770,46 +870,14 @@ class Matcher:
         stream's previous piece; further back is a text start); next_byte: the byte after text, or -1.
         all_patterns: every word-bounded pattern, else the first in list order.  Returns
         (offsets, patterns, last_state)."""
-        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
-            else np.ascontiguousarray(text, dtype=np.uint8)
-        bf = np.frombuffer(bytes(before), dtype=np.uint8)
-        self.reserve(max(t.size, 1))
-        d = DeviceArray.from_numpy(t, stream=self.stream)
-        d_bf = DeviceArray.from_numpy(bf, stream=self.stream) if bf.size else None
-        starts = np.ascontiguousarray(segments if segments is not None else [], dtype=np.int32)
-        nseg = int(starts.size)
-        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
-        max_records = self.plane_capacity - 2
-        cap = self.plane_capacity
-        ocap = out_capacity if out_capacity is not None else (8 * cap if all_patterns else cap)
-        ws_bytes = self.lib.acm_word_workspace_bytes(max_records)
-        bufs = [DeviceArray(max(ws_bytes, 16)), DeviceArray(ocap * 4), DeviceArray(ocap * 4)]
-        ws, pat, off = bufs
-        bufs += [b for b in (d, d_bf, d_st) if b is not None]
-        try:
-            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
-            sp, so = self.pat_plane, self.off_plane
-            if nseg:
-                sb = [DeviceArray(max(self.lib.acm_segment_workspace_bytes(max_records), 16)),
-                      DeviceArray(cap * 4), DeviceArray(cap * 4)]
-                bufs += sb
-                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
-                                   report=_lib.REPORT_STATE,
-                                   workspace=(sb[0].ptr, self.lib.acm_segment_workspace_bytes(max_records)))
-                sp, so = sb[1], sb[2]
-            self.word_async(sp, so, max_records, d, 0, t.size, pat, off, ocap, before=d_bf, before_len=int(bf.size),
-                            next_byte=next_byte, seg_start=d_st, segments=nseg, word_mask=self.word_mask(word_set),
-                            all_patterns=all_patterns, workspace=(ws.ptr, ws_bytes))
-            m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
-            if m > ocap - 2:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_words", "%d records but planes hold %d"
-                               % (m, ocap - 2))
-            p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
-            o = off.to_numpy(np.int32, m + 2, stream=self.stream)
-            return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1])
-        finally:
-            for b in bufs:
-                b.free()
+        with _Pipeline(self, "Matcher.scan_words", text, segments=segments, before=before) as p:
+            ocap = out_capacity if out_capacity is not None else (8 * p.cap if all_patterns else p.cap)
+            ws = p.workspace(self.lib.acm_word_workspace_bytes, p.max_records)
+            p.scan(init_state)
+            if p.nseg:
+                p.segment()
+            p.word(ocap, all_patterns, next_byte=next_byte, word_mask=self.word_mask(word_set), ws=ws)
+            return p.download(p.count())
 
     def case_async(self, state_plane, off_plane, max_records, d_text, text_origin, text_end, pat_out, off_out,
                    out_capacity, before=None, before_len=0, all_patterns=False, tail_out=None, workspace=None,
@@ -819,20 +887,11 @@ class Matcher:
         kept only where the text equals its bytes as added.  workspace: (ptr, nbytes), or None for a
         temporary one that lives until the stream has passed it (the call then synchronises)."""
         st = stream if stream is not None else self.stream
-        tmp = None
-        if workspace is None:
-            nb = self.lib.acm_case_workspace_bytes(max_records)
-            tmp = DeviceArray(max(nb, 16))
-            workspace = (tmp.ptr, nb)
-        try:
+        with self._workspace(workspace, st, self.lib.acm_case_workspace_bytes, max_records) as (ws, nb):
             check(self.lib.acm_case_matches_async(
                 self.dfa, _ptr(state_plane), _ptr(off_plane), max_records, _ptr(d_text), text_origin, text_end,
                 _ptr(before), before_len, 1 if all_patterns else 0, _ptr(pat_out), _ptr(off_out), out_capacity,
-                _ptr(tail_out), _ptr(workspace[0]), workspace[1], st), "acm_case_matches_async")
-        finally:
-            if tmp is not None:
-                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
-                tmp.free()
+                _ptr(tail_out), _ptr(ws), nb, st), "acm_case_matches_async")
 
     def scan_case(self, text, all_patterns=False, texts=None, init_state=0, before=b"", out_capacity=None):
         """Matches of an automaton with case sensitivity per pattern (Automaton.add(..., nocase=True)):
@@ -841,47 +900,14 @@ class Matcher:
         a (uint8 array, int32 starts) pair, each matched as if scanned alone.  before: the bytes in
         front of text (a stream's previous piece).  all_patterns: every kept pattern, else the first
         in list order.  Returns (offsets, patterns, last_state) as scan_all does."""
-        if texts is not None:
-            t, starts = self.pack_segments(texts)
-        else:
-            t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
-                else np.ascontiguousarray(text, dtype=np.uint8)
-            starts = np.zeros(0, dtype=np.int32)
-        bf = np.frombuffer(bytes(before), dtype=np.uint8)
-        self.reserve(max(t.size, 1))
-        d = DeviceArray.from_numpy(t, stream=self.stream)
-        d_bf = DeviceArray.from_numpy(bf, stream=self.stream) if bf.size else None
-        nseg = int(starts.size)
-        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
-        max_records = self.plane_capacity - 2
-        cap = self.plane_capacity
-        ocap = out_capacity if out_capacity is not None else (8 * cap if all_patterns else cap)
-        ws_bytes = self.lib.acm_case_workspace_bytes(max_records)
-        bufs = [DeviceArray(max(ws_bytes, 16)), DeviceArray(ocap * 4), DeviceArray(ocap * 4)]
-        ws, pat, off = bufs
-        bufs += [b for b in (d, d_bf, d_st) if b is not None]
-        try:
-            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
-            sp, so = self.pat_plane, self.off_plane
-            if nseg:
-                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
-                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
-                bufs += sb
-                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
-                                   report=_lib.REPORT_STATE, workspace=(sb[0].ptr, seg_ws))
-                sp, so = sb[1], sb[2]
-            self.case_async(sp, so, max_records, d, 0, t.size, pat, off, ocap, before=d_bf, before_len=int(bf.size),
-                            all_patterns=all_patterns, workspace=(ws.ptr, ws_bytes))
-            m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
-            if m > ocap - 2:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_case", "%d records but planes hold %d"
-                               % (m, ocap - 2))
-            p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
-            o = off.to_numpy(np.int32, m + 2, stream=self.stream)
-            return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1])
-        finally:
-            for b in bufs:
-                b.free()
+        with _Pipeline(self, "Matcher.scan_case", text, texts, before=before) as p:
+            ocap = out_capacity if out_capacity is not None else (8 * p.cap if all_patterns else p.cap)
+            ws = p.workspace(self.lib.acm_case_workspace_bytes, p.max_records)
+            p.scan(init_state)
+            if p.nseg:
+                p.segment()
+            p.case(ocap, all_patterns, ws=ws)
+            return p.download(p.count())
 
     def position_async(self, pat_plane, off_plane, max_records, pat_out, off_out, out_capacity, info, report=0,
                        seg_start=None, segments=0, lead_begin=0, text_end=0, open_end=-1, all_patterns=False,
@@ -892,20 +918,11 @@ class Matcher:
         int32[4].  workspace: (ptr, nbytes), or None for a temporary one that lives until the stream has
         passed it (the call then synchronises)."""
         st = stream if stream is not None else self.stream
-        tmp = None
-        if workspace is None:
-            nb = self.lib.acm_position_workspace_bytes(max_records)
-            tmp = DeviceArray(max(nb, 16))
-            workspace = (tmp.ptr, nb)
-        try:
+        with self._workspace(workspace, st, self.lib.acm_position_workspace_bytes, max_records) as (ws, nb):
             check(self.lib.acm_position_matches_async(
                 self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, report, _ptr(seg_start), segments, lead_begin,
                 text_end, open_end, 1 if all_patterns else 0, _ptr(pat_out), _ptr(off_out), out_capacity, _ptr(info),
-                _ptr(workspace[0]), workspace[1], st), "acm_position_matches_async")
-        finally:
-            if tmp is not None:
-                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
-                tmp.free()
+                _ptr(ws), nb, st), "acm_position_matches_async")
 
     def scan_positions(self, text=None, texts=None, all_patterns=False, then=None, lead_begin=0, open_end="end",
                        init_state=0, before=b"", out_capacity=None):
@@ -920,67 +937,20 @@ class Matcher:
         Returns (offsets, patterns, last_state, undecided)."""
         if then not in (None, "case", "words"):
             raise ValueError("then must be None, 'case' or 'words'")
-        if texts is not None:
-            t, starts = self.pack_segments(texts)
-        else:
-            t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
-                else np.ascontiguousarray(text, dtype=np.uint8)
-            starts = np.zeros(0, dtype=np.int32)
-        end = -1 if open_end is None else int(t.size) if isinstance(open_end, str) else int(open_end)
-        bf = np.frombuffer(bytes(before), dtype=np.uint8)
-        self.reserve(max(t.size, 1))
-        d = DeviceArray.from_numpy(t, stream=self.stream)
-        d_bf = DeviceArray.from_numpy(bf, stream=self.stream) if bf.size else None
-        nseg = int(starts.size)
-        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
-        max_records = self.plane_capacity - 2
-        cap = self.plane_capacity
-        ocap = out_capacity if out_capacity is not None else (8 * cap if all_patterns or then else cap)
-        ws_bytes = self.lib.acm_position_workspace_bytes(max(max_records, 8 * cap))
-        bufs = [DeviceArray(max(ws_bytes, 16)), DeviceArray(ocap * 4), DeviceArray(ocap * 4), DeviceArray(16)]
-        ws, pat, off, info = bufs
-        bufs += [b for b in (d, d_bf, d_st) if b is not None]
-        try:
-            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
-            sp, so, report = self.pat_plane, self.off_plane, _lib.REPORT_STATE
-            if nseg:
-                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
-                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
-                bufs += sb
-                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
-                                   report=_lib.REPORT_STATE, workspace=(sb[0].ptr, seg_ws))
-                sp, so = sb[1], sb[2]
+        with _Pipeline(self, "Matcher.scan_positions", text, texts, before=before) as p:
+            end = -1 if open_end is None else p.n if isinstance(open_end, str) else int(open_end)
+            ocap = out_capacity if out_capacity is not None else (8 * p.cap if all_patterns or then else p.cap)
+            # one workspace, sized before the scan for either input: the scan's records, or the pass in between's
+            ws = p.workspace(self.lib.acm_position_workspace_bytes, max(p.max_records, 8 * p.cap))
+            info = p.alloc(16)
+            p.scan(init_state)
+            if p.nseg:
+                p.segment()
             if then:
-                icap = 8 * cap
-                nb = (self.lib.acm_case_workspace_bytes if then == "case" else self.lib.acm_word_workspace_bytes)(max_records)
-                tb = [DeviceArray(max(nb, 16)), DeviceArray(icap * 4), DeviceArray(icap * 4)]
-                bufs += tb
-                if then == "case":
-                    self.case_async(sp, so, max_records, d, 0, t.size, tb[1], tb[2], icap, before=d_bf,
-                                    before_len=int(bf.size), all_patterns=True, workspace=(tb[0].ptr, nb))
-                else:
-                    self.word_async(sp, so, max_records, d, 0, t.size, tb[1], tb[2], icap, before=d_bf,
-                                    before_len=int(bf.size), seg_start=d_st, segments=nseg, all_patterns=True,
-                                    workspace=(tb[0].ptr, nb))
-                n = int(tb[1].to_numpy(np.int32, 1, stream=self.stream)[0])
-                if n > icap - 2:
-                    raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_positions", "%d records but planes hold %d"
-                                   % (n, icap - 2))
-                sp, so, report, max_records = tb[1], tb[2], _lib.REPORT_HEAD, icap - 2
-            self.position_async(sp, so, max_records, pat, off, ocap, info, report=report, seg_start=d_st, segments=nseg,
-                                lead_begin=int(lead_begin), text_end=int(t.size), open_end=end, all_patterns=all_patterns,
-                                workspace=(ws.ptr, ws_bytes))
-            m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
-            if m > ocap - 2:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_positions", "%d records but planes hold %d"
-                               % (m, ocap - 2))
-            p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
-            o = off.to_numpy(np.int32, m + 2, stream=self.stream)
-            und = int(info.to_numpy(np.int32, 4, stream=self.stream)[0])
-            return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1]), und
-        finally:
-            for b in bufs:
-                b.free()
+                (p.case if then == "case" else p.word)(8 * p.cap, True)
+                p.count()                      # (checked only: the position pass takes the whole planes)
+            p.position(ocap, info, all_patterns, int(lead_begin), end, ws=ws)
+            return p.download(p.count()) + (int(info.to_numpy(np.int32, 4, stream=self.stream)[0]),)
 
     def wildcard_async(self, pat_plane, off_plane, max_records, d_text, text_origin, text_end, pat_out, off_out,
                        out_capacity, info, report=0, before=None, before_len=0, seg_start=None, segments=0, lead_begin=0,
@@ -991,21 +961,12 @@ class Matcher:
         workspace: (ptr, nbytes), or None for a temporary one that lives until the stream has passed it (the
         call then synchronises)."""
         st = stream if stream is not None else self.stream
-        tmp = None
-        if workspace is None:
-            nb = self.lib.acm_wildcard_workspace_bytes(max_records)
-            tmp = DeviceArray(max(nb, 16))
-            workspace = (tmp.ptr, nb)
-        try:
+        with self._workspace(workspace, st, self.lib.acm_wildcard_workspace_bytes, max_records) as (ws, nb):
             check(self.lib.acm_wildcard_matches_async(
                 self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, report, _ptr(d_text), text_origin, text_end,
                 _ptr(before), before_len, _ptr(seg_start), segments, lead_begin, open_end, 1 if all_patterns else 0,
-                _ptr(pat_out), _ptr(off_out), out_capacity, _ptr(info), _ptr(workspace[0]), workspace[1], st),
+                _ptr(pat_out), _ptr(off_out), out_capacity, _ptr(info), _ptr(ws), nb, st),
                 "acm_wildcard_matches_async")
-        finally:
-            if tmp is not None:
-                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
-                tmp.free()
 
     def scan_wildcards(self, text=None, texts=None, all_patterns=False, before=b"", init_state=0, out_capacity=None):
         """Matches of an automaton with wildcard patterns (Automaton.add_wildcard): a REPORT_STATE scan, the
@@ -1017,73 +978,23 @@ class Matcher:
         text ends with the bytes given.  Returns (offsets, patterns, last_state, info): the offsets are the
         ANCHORS' ends (a match ends Automaton.wildcard_lengths(p)[1] bytes behind), info[0] the undecided
         entries."""
-        if texts is not None:
-            t, starts = self.pack_segments(texts)
-        else:
-            t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
-                else np.ascontiguousarray(text, dtype=np.uint8)
-            starts = np.zeros(0, dtype=np.int32)
-        bf = np.frombuffer(bytes(before), dtype=np.uint8)
-        self.reserve(max(t.size, 1))
-        d = DeviceArray.from_numpy(t, stream=self.stream)
-        d_bf = DeviceArray.from_numpy(bf, stream=self.stream) if bf.size else None
-        nseg = int(starts.size)
-        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
-        max_records = self.plane_capacity - 2
-        cap = self.plane_capacity
-        ocap = out_capacity if out_capacity is not None else (8 * cap if all_patterns or self.mixed else cap)
-        info = DeviceArray(16)
-        bufs = [info] + [b for b in (d, d_bf, d_st) if b is not None]
-
-        def count_of(plane, room):
-            n = int(plane.to_numpy(np.int32, 1, stream=self.stream)[0])
-            if n > room - 2:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_wildcards", "%d records but planes hold %d" % (n, room - 2))
-            return n
-        where = dict(before=d_bf, before_len=int(bf.size), seg_start=d_st, segments=nseg, lead_begin=-int(bf.size),
-                     open_end=int(t.size))
-        try:
-            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
-            sp, so, report = self.pat_plane, self.off_plane, _lib.REPORT_STATE
-            if nseg:
-                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
-                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
-                bufs += sb
-                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
-                                   report=_lib.REPORT_STATE, workspace=(sb[0].ptr, seg_ws))
-                sp, so = sb[1], sb[2]
+        with _Pipeline(self, "Matcher.scan_wildcards", text, texts, before=before) as p:
+            ocap = out_capacity if out_capacity is not None else (8 * p.cap if all_patterns or self.mixed else p.cap)
+            info = p.alloc(16)
+            p.scan(init_state)
+            if p.nseg:
+                p.segment()
             if self.mixed:
-                icap = 8 * cap
-                nb = self.lib.acm_case_workspace_bytes(max_records)
-                tb = [DeviceArray(max(nb, 16)), DeviceArray(icap * 4), DeviceArray(icap * 4)]
-                bufs += tb
-                self.case_async(sp, so, max_records, d, 0, t.size, tb[1], tb[2], icap, before=d_bf,
-                                before_len=int(bf.size), all_patterns=True, workspace=(tb[0].ptr, nb))
-                max_records = count_of(tb[1], icap)
-                sp, so, report = tb[1], tb[2], _lib.REPORT_HEAD
-            nb = self.lib.acm_wildcard_workspace_bytes(max_records)
-            wb = [DeviceArray(max(nb, 16)), DeviceArray(ocap * 4), DeviceArray(ocap * 4)]
-            bufs += wb
-            self.wildcard_async(sp, so, max_records, d, 0, t.size, wb[1], wb[2], ocap, info, report=report,
-                                all_patterns=all_patterns or report == _lib.REPORT_HEAD, workspace=(wb[0].ptr, nb), **where)
-            m = count_of(wb[1], ocap)
-            pat, off = wb[1], wb[2]
+                p.case(8 * p.cap, True)
+                p.max_records = p.count()
+            p.wildcard(ocap, info, all_patterns or self.mixed, -p.before_len)
+            m = p.count()
             und = info.to_numpy(np.int32, 4, stream=self.stream)
-            if report == _lib.REPORT_HEAD and not all_patterns:
-                nb = self.lib.acm_position_workspace_bytes(m)
-                pb = [DeviceArray(max(nb, 16)), DeviceArray((m + 2) * 4), DeviceArray((m + 2) * 4), DeviceArray(16)]
-                bufs += pb
-                self.position_async(pat, off, m, pb[1], pb[2], m + 2, pb[3], report=_lib.REPORT_HEAD, seg_start=d_st,
-                                    segments=nseg, lead_begin=-int(bf.size), text_end=int(t.size), open_end=int(t.size),
-                                    all_patterns=False, workspace=(pb[0].ptr, nb))
-                m = count_of(pb[1], m + 2)
-                pat, off = pb[1], pb[2]
-            p = pat.to_numpy(np.int32, m + 2, stream=self.stream)
-            o = off.to_numpy(np.int32, m + 2, stream=self.stream)
-            return o[1:1 + m].astype(np.uint32), p[1:1 + m].copy(), int(p[m + 1]), und
-        finally:
-            for b in bufs:
-                b.free()
+            if self.mixed and not all_patterns:        # the first entry of every offset: the position pass in head form
+                p.max_records = m
+                p.position(m + 2, p.alloc(16), False, -p.before_len, p.n)
+                m = p.count()
+            return p.download(m) + (und,)
 
     def sequence_async(self, pat_plane, off_plane, max_records, seq_out, off_out, out_capacity, info, seg_start=None,
                        segments=0, lead_begin=0, text_end=0, workspace=None, stream=None):
@@ -1094,20 +1005,11 @@ class Matcher:
         nbytes), or None for a temporary one that lives until the stream has passed it (the call then
         synchronises)."""
         st = stream if stream is not None else self.stream
-        tmp = None
-        if workspace is None:
-            nb = self.lib.acm_sequence_workspace_bytes(self.dfa, max_records)
-            tmp = DeviceArray(max(nb, 16))
-            workspace = (tmp.ptr, nb)
-        try:
+        with self._workspace(workspace, st, self.lib.acm_sequence_workspace_bytes, self.dfa, max_records) as (ws, nb):
             check(self.lib.acm_sequence_matches_async(
                 self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, _ptr(seg_start), segments, lead_begin, text_end,
-                _ptr(seq_out), _ptr(off_out), out_capacity, _ptr(info), _ptr(workspace[0]), workspace[1], st),
+                _ptr(seq_out), _ptr(off_out), out_capacity, _ptr(info), _ptr(ws), nb, st),
                 "acm_sequence_matches_async")
-        finally:
-            if tmp is not None:
-                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
-                tmp.free()
 
     def scan_sequences(self, text=None, texts=None, lead_begin=0, init_state=0, before=b"", out_capacity=None):
         """Matches of the automaton's sequences (Automaton.add_sequence, add_signature): a REPORT_STATE scan,
@@ -1126,98 +1028,30 @@ class Matcher:
 
     def _sequences(self, text, texts, lead_begin, init_state, before, out_capacity, rules):
         """scan_sequences, and with rules scan_rules: the rule pass over the sequence pass's planes"""
-        if texts is not None:
-            t, starts = self.pack_segments(texts)
-        else:
-            t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
-                else np.ascontiguousarray(text, dtype=np.uint8)
-            starts = np.zeros(0, dtype=np.int32)
-        bf = np.frombuffer(bytes(before), dtype=np.uint8)
-        self.reserve(max(t.size, 1))
-        d = DeviceArray.from_numpy(t, stream=self.stream)
-        d_bf = DeviceArray.from_numpy(bf, stream=self.stream) if bf.size else None
-        nseg = int(starts.size)
-        d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream) if nseg else None
-        max_records = self.plane_capacity - 2
-        cap = self.plane_capacity
-        icap = 8 * cap
-        bufs = [b for b in (d, d_bf, d_st) if b is not None]
-
-        def count_of(plane, room):
-            n = int(plane.to_numpy(np.int32, 1, stream=self.stream)[0])
-            if n > room - 2:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_sequences", "%d records but planes hold %d" % (n, room - 2))
-            return n
-        try:
-            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
-            sp, so = self.pat_plane, self.off_plane
-            if nseg:
-                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
-                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
-                bufs += sb
-                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
-                                   report=_lib.REPORT_STATE, workspace=(sb[0].ptr, seg_ws))
-                sp, so = sb[1], sb[2]
-            mixed = self.mixed
-            nb = (self.lib.acm_case_workspace_bytes if mixed else self.lib.acm_expand_workspace_bytes)(max_records)
-            tb = [DeviceArray(max(nb, 16)), DeviceArray(icap * 4), DeviceArray(icap * 4)]
-            bufs += tb
-            if mixed:
-                self.case_async(sp, so, max_records, d, 0, t.size, tb[1], tb[2], icap, before=d_bf,
-                                before_len=int(bf.size), all_patterns=True, workspace=(tb[0].ptr, nb))
-            else:
-                check(self.lib.acm_expand_matches_async(self.dfa, _ptr(sp), _ptr(so), max_records, tb[1].ptr, tb[2].ptr,
-                                                        icap, tb[0].ptr, nb, self.stream), "acm_expand_matches_async")
-            n = count_of(tb[1], icap)
-            sp, so = tb[1], tb[2]
-            info = DeviceArray(16)
-            bufs.append(info)
+        lead_begin = int(lead_begin)
+        with _Pipeline(self, "Matcher.scan_sequences", text, texts, before=before) as p:
+            p.scan(init_state)
+            if p.nseg:
+                p.segment()
+            p.every_pattern(8 * p.cap)
+            p.max_records = n = p.count()          # from here on every stage is sized by the count in front of it
+            info = p.alloc(16)
             if self.wild:
-                nb = self.lib.acm_wildcard_workspace_bytes(n)
-                wb = [DeviceArray(max(nb, 16)), DeviceArray((n + 2) * 4), DeviceArray((n + 2) * 4)]
-                bufs += wb
-                self.wildcard_async(sp, so, n, d, 0, t.size, wb[1], wb[2], n + 2, info, report=_lib.REPORT_HEAD,
-                                    before=d_bf, before_len=int(bf.size), seg_start=d_st, segments=nseg,
-                                    lead_begin=int(lead_begin), open_end=int(t.size), all_patterns=True,
-                                    workspace=(wb[0].ptr, nb))
-                n = count_of(wb[1], n + 2)
-                sp, so = wb[1], wb[2]
+                p.wildcard(n + 2, info, True, lead_begin)
+                p.max_records = n = p.count()
             if self.positioned:
-                nb = self.lib.acm_position_workspace_bytes(n)
-                pb = [DeviceArray(max(nb, 16)), DeviceArray((n + 2) * 4), DeviceArray((n + 2) * 4)]
-                bufs += pb
-                self.position_async(sp, so, n, pb[1], pb[2], n + 2, info, report=_lib.REPORT_HEAD, seg_start=d_st,
-                                    segments=nseg, lead_begin=int(lead_begin), text_end=int(t.size), open_end=int(t.size),
-                                    all_patterns=True, workspace=(pb[0].ptr, nb))
-                n = count_of(pb[1], n + 2)
-                sp, so = pb[1], pb[2]
-            ocap = out_capacity if out_capacity is not None and not rules else n + 2
-            nb = self.lib.acm_sequence_workspace_bytes(self.dfa, n)
-            qb = [DeviceArray(max(nb, 16)), DeviceArray(ocap * 4), DeviceArray(ocap * 4)]
-            bufs += qb
-            self.sequence_async(sp, so, n, qb[1], qb[2], ocap, info, seg_start=d_st, segments=nseg,
-                                lead_begin=int(lead_begin), text_end=int(t.size), workspace=(qb[0].ptr, nb))
-            m = count_of(qb[1], ocap)
+                p.position(n + 2, info, True, lead_begin, p.n)
+                p.max_records = n = p.count()
+            p.sequence(out_capacity if out_capacity is not None and not rules else n + 2, info, lead_begin)
+            p.max_records = m = p.count()
             if rules:
-                rcap = out_capacity if out_capacity is not None else m + 2
-                nb = self.lib.acm_rule_workspace_bytes(self.dfa, m)
-                rb = [DeviceArray(max(nb, 16))] + [DeviceArray(rcap * 4) for _ in range(3)]
-                bufs += rb
-                self.rule_async(qb[1], qb[2], m, rb[1], rb[2], rb[3], rcap, info, seg_start=d_st, segments=nseg,
-                                workspace=(rb[0].ptr, nb))
-                k = count_of(rb[1], rcap)
-                r, x, o = (b.to_numpy(np.int32, k + 2, stream=self.stream) for b in rb[1:])
-                return r[1:1 + k].copy(), x[1:1 + k].copy(), o[1:1 + k].astype(np.uint32), \
-                    info.to_numpy(np.int32, 4, stream=self.stream)
-            q = qb[1].to_numpy(np.int32, m + 2, stream=self.stream)
-            o = qb[2].to_numpy(np.int32, m + 2, stream=self.stream)
-            ends = o[1:1 + m].astype(np.uint32)
+                text_plane = p.rule(out_capacity if out_capacity is not None else m + 2, info)
+                offs, fired, _, of_text = p.download(p.count(), text_plane)
+                return fired, of_text, offs, info.to_numpy(np.int32, 4, stream=self.stream)
+            ends, seqs, last = p.download(m)
             if self.wild:   # the pass reports the end of the last part's anchor: the match ends post bytes behind it
-                ends = (ends.astype(np.int64) + self.seq_post[q[1:1 + m]]).astype(np.uint32)
-            return ends, q[1:1 + m].copy(), int(q[m + 1]), info.to_numpy(np.int32, 4, stream=self.stream)
-        finally:
-            for b in bufs:
-                b.free()
+                ends = (ends.astype(np.int64) + self.seq_post[seqs]).astype(np.uint32)
+            return ends, seqs, last, info.to_numpy(np.int32, 4, stream=self.stream)
 
     def rule_async(self, seq_plane, off_plane, max_records, rule_out, text_out, off_out, out_capacity, info, seg_start=None,
                    segments=0, workspace=None, stream=None):
@@ -1227,20 +1061,11 @@ class Matcher:
         int32[4].  The pass orders max_records cells: size it to the planes.  workspace: (ptr, nbytes), or None
         for a temporary one that lives until the stream has passed it (the call then synchronises)."""
         st = stream if stream is not None else self.stream
-        tmp = None
-        if workspace is None:
-            nb = self.lib.acm_rule_workspace_bytes(self.dfa, max_records)
-            tmp = DeviceArray(max(nb, 16))
-            workspace = (tmp.ptr, nb)
-        try:
+        with self._workspace(workspace, st, self.lib.acm_rule_workspace_bytes, self.dfa, max_records) as (ws, nb):
             check(self.lib.acm_rule_matches_async(
                 self.dfa, _ptr(seq_plane), _ptr(off_plane), max_records, _ptr(seg_start), segments, _ptr(rule_out),
-                _ptr(text_out), _ptr(off_out), out_capacity, _ptr(info), _ptr(workspace[0]), workspace[1], st),
+                _ptr(text_out), _ptr(off_out), out_capacity, _ptr(info), _ptr(ws), nb, st),
                 "acm_rule_matches_async")
-        finally:
-            if tmp is not None:
-                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
-                tmp.free()
 
     def scan_rules(self, text=None, texts=None, lead_begin=0, init_state=0, before=b"", out_capacity=None):
         """The automaton's rules that hold (Automaton.add_rule, add_logical_signature): everything scan_sequences
@@ -1266,21 +1091,12 @@ class Matcher:
             if class_of is not None:
                 raise ValueError("num_classes is needed with a class map")
             num_classes = self.num_patterns
-        tmp = None
-        if workspace is None:
-            nb = self.lib.acm_tally_workspace_bytes(max_records, num_classes)
-            tmp = DeviceArray(max(nb, 16))
-            workspace = (tmp.ptr, nb)
         flags = (_lib.TALLY_ACCUMULATE if accumulate else 0) | (_lib.TALLY_ALL_PATTERNS if all_patterns else 0)
-        try:
+        with self._workspace(workspace, st, self.lib.acm_tally_workspace_bytes, max_records, num_classes) as (ws, nb):
             check(self.lib.acm_tally_matches_async(
                 self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, report, flags, _ptr(class_of), num_classes,
-                _ptr(seg_start), segments, _ptr(class_total), _ptr(seg_class), _ptr(lead), _ptr(workspace[0]),
-                workspace[1], st), "acm_tally_matches_async")
-        finally:
-            if tmp is not None:
-                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
-                tmp.free()
+                _ptr(seg_start), segments, _ptr(class_total), _ptr(seg_class), _ptr(lead), _ptr(ws), nb, st),
+                "acm_tally_matches_async")
 
     def scan_tally(self, texts, class_of=None, num_classes=None, all_patterns=False, per_text=True, init_state=0):
         """Count instead of list: scan, clamp every record to its own text when there are several
@@ -1291,13 +1107,6 @@ class Matcher:
         max(class_of) + 1.  all_patterns: count every pattern that ends at an offset, else the one the
         scan reports.  Returns (class_total uint64[C], seg_class int32[S, C] or None, lead int32[C],
         last_state); seg_class is None without segments or with per_text=False."""
-        if isinstance(texts, (list, tuple)):
-            t, starts = self.pack_segments(texts)
-        else:
-            t = np.frombuffer(texts, dtype=np.uint8) if isinstance(texts, (bytes, bytearray, memoryview)) \
-                else np.ascontiguousarray(texts, dtype=np.uint8)
-            starts = np.zeros(0, dtype=np.int32)
-        nseg = int(starts.size)
         cmap = None
         if class_of is not None:
             cmap = np.ascontiguousarray(class_of, dtype=np.int32)
@@ -1308,49 +1117,28 @@ class Matcher:
         elif num_classes is None:
             num_classes = self.num_patterns
         ncls = int(num_classes)
-        self.reserve(max(t.size, 1))
-        max_records = self.plane_capacity - 2
-        cap = self.plane_capacity
-        want_rows = bool(per_text and nseg)
-        tally_ws = self.lib.acm_tally_workspace_bytes(max_records, ncls)
-        bufs = [DeviceArray.from_numpy(t, stream=self.stream), DeviceArray(max(tally_ws, 16)),
-                DeviceArray(max(ncls * 8, 16)), DeviceArray(max(ncls * 4, 16))]
-        d, ws, tot, lead = bufs
-        d_map = d_st = rows = None
-        if cmap is not None:
-            d_map = DeviceArray.from_numpy(cmap, pad_to=0, stream=self.stream) if cmap.size else DeviceArray(16)
-            bufs.append(d_map)
-        if nseg:
-            d_st = DeviceArray.from_numpy(starts, pad_to=0, stream=self.stream)
-            bufs.append(d_st)
-        if want_rows:
-            rows = DeviceArray(max(nseg * ncls * 4, 16))
-            bufs.append(rows)
-        try:
-            self.scan_async(d, t.size, init_state, report=_lib.REPORT_STATE)
-            sp, so = self.pat_plane, self.off_plane
+        several = isinstance(texts, (list, tuple))
+        with _Pipeline(self, "Matcher.scan_tally", None if several else texts, texts if several else None) as p:
+            nseg = p.nseg
+            ws = p.workspace(self.lib.acm_tally_workspace_bytes, p.max_records, ncls)
+            tot, lead = p.alloc(max(ncls * 8, 16)), p.alloc(max(ncls * 4, 16))
+            d_map = rows = None
+            if cmap is not None:
+                d_map = p.upload(cmap, pad_to=0) if cmap.size else p.alloc(16)
+            if per_text and nseg:
+                rows = p.alloc(max(nseg * ncls * 4, 16))
+            p.scan(init_state)
             if nseg:
-                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
-                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
-                bufs += sb
-                self.segment_async(sp, so, max_records, d_st, nseg, t.size, sb[1], sb[2], cap,
-                                   report=_lib.REPORT_STATE, workspace=(sb[0].ptr, seg_ws))
-                sp, so = sb[1], sb[2]
-            self.tally_async(sp, so, max_records, tot, report=_lib.REPORT_STATE, all_patterns=all_patterns,
-                             class_of=d_map, num_classes=ncls, seg_start=d_st, segments=nseg, seg_class=rows,
-                             lead=lead, workspace=(ws.ptr, tally_ws))
-            m = int(sp.to_numpy(np.int32, 1, stream=self.stream)[0])
-            if m > cap - 2:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_tally", "%d records but planes hold %d"
-                               % (m, cap - 2))
-            last = int(sp.to_numpy(np.int32, 1, offset_bytes=4 * (m + 1), stream=self.stream)[0])
+                p.segment()
+            self.tally_async(p.pat, p.off, p.max_records, tot, report=_lib.REPORT_STATE, all_patterns=all_patterns,
+                             class_of=d_map, num_classes=ncls, seg_start=p.d_st, segments=nseg, seg_class=rows,
+                             lead=lead, workspace=ws)
+            m = p.count()
+            last = int(p.pat.to_numpy(np.int32, 1, offset_bytes=4 * (m + 1), stream=self.stream)[0])
             seg_class = rows.to_numpy(np.int32, nseg * ncls, stream=self.stream).reshape(nseg, ncls) \
-                if want_rows else None
+                if rows is not None else None
             return (tot.to_numpy(np.uint64, ncls, stream=self.stream), seg_class,
                     lead.to_numpy(np.int32, ncls, stream=self.stream), last)
-        finally:
-            for b in bufs:
-                b.free()
 
     def line_index_async(self, d_text, n, line_start, capacity, info, text_origin=0, delimiter=b"\n", prev_byte=-1,
                          prev_info=None, workspace=None, stream=None):
@@ -1360,19 +1148,10 @@ class Matcher:
         device.  workspace: (ptr, nbytes), or None for a temporary one (the call then synchronises)."""
         st = stream if stream is not None else self.stream
         d = delimiter[0] if isinstance(delimiter, (bytes, bytearray)) else int(delimiter)
-        tmp = None
-        if workspace is None:
-            nb = self.lib.acm_line_index_workspace_bytes(n)
-            tmp = DeviceArray(max(nb, 16))
-            workspace = (tmp.ptr, nb)
-        try:
+        with self._workspace(workspace, st, self.lib.acm_line_index_workspace_bytes, n) as (ws, nb):
             check(self.lib.acm_line_index_async(_ptr(d_text), n, text_origin, d, prev_byte, _ptr(prev_info),
-                                                _ptr(line_start), capacity, _ptr(info), _ptr(workspace[0]), workspace[1],
-                                                st), "acm_line_index_async")
-        finally:
-            if tmp is not None:
-                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
-                tmp.free()
+                                                _ptr(line_start), capacity, _ptr(info), _ptr(ws), nb, st),
+                  "acm_line_index_async")
 
     def line_number_async(self, line_start, capacity, info, offsets, count, line_out, d_count=None, stream=None):
         """Enqueue acm_line_number_async: delimiters in front of each of count device offsets (of at most
@@ -1387,20 +1166,11 @@ class Matcher:
         none) as (delimiters in front, first byte, first byte behind) planes in the scan's cell layout.
         workspace: (ptr, nbytes), or None for a temporary one (the call then synchronises)."""
         st = stream if stream is not None else self.stream
-        tmp = None
-        if workspace is None:
-            nb = self.lib.acm_line_select_workspace_bytes(capacity)
-            tmp = DeviceArray(max(nb, 16))
-            workspace = (tmp.ptr, nb)
-        try:
+        with self._workspace(workspace, st, self.lib.acm_line_select_workspace_bytes, capacity) as (ws, nb):
             check(self.lib.acm_line_select_async(_ptr(line_start), capacity, _ptr(info), text_origin, text_end,
                                                  _ptr(off_plane), max_records, 1 if invert else 0, _ptr(rel_out),
-                                                 _ptr(begin_out), _ptr(next_out), out_capacity, _ptr(workspace[0]),
-                                                 workspace[1], st), "acm_line_select_async")
-        finally:
-            if tmp is not None:
-                check(self.lib.acm_rt_stream_sync(st), "acm_rt_stream_sync")
-                tmp.free()
+                                                 _ptr(begin_out), _ptr(next_out), out_capacity, _ptr(ws), nb, st),
+                  "acm_line_select_async")
 
     def scan_lines(self, text, delimiter=b"\n", per_line=False, all_patterns=False, invert=False, init_state=0):
         """grep -n: scan host bytes, find the lines on the device (acm_line_index_async), number every
@@ -1413,49 +1183,23 @@ class Matcher:
         its lines uses the three *_async calls with its own buffers.  Returns (patterns int32[], offsets
         uint32[], lines int64[] 1-based,
         selected int64[k, 3] of (1-based line, first byte, first byte behind), number of lines)."""
-        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) \
-            else np.ascontiguousarray(text, dtype=np.uint8)
-        n = int(t.size)
-        self.reserve(max(n, 1))
-        cap = self.plane_capacity
-        max_records = cap - 2
-        lcap = n + 1
-        states = per_line or all_patterns
-        idx_ws = self.lib.acm_line_index_workspace_bytes(n)
-        sel_ws = self.lib.acm_line_select_workspace_bytes(lcap)
-        bufs = [DeviceArray.from_numpy(t, stream=self.stream), DeviceArray(lcap * 4), DeviceArray(32),
-                DeviceArray(max(idx_ws, sel_ws))]
-        d, starts, info, ws = bufs
-        try:
-            self.scan_async(d, n, init_state, report=_lib.REPORT_STATE if states else _lib.REPORT_HEAD)
-            self.line_index_async(d, n, starts, lcap, info, delimiter=delimiter, workspace=(ws.ptr, idx_ws))
-            pat, off, rcap = self.pat_plane, self.off_plane, cap
+        with _Pipeline(self, "Matcher.scan_lines", text) as pl:
+            n, lcap = pl.n, pl.n + 1
+            idx_ws = self.lib.acm_line_index_workspace_bytes(n)
+            sel_ws = self.lib.acm_line_select_workspace_bytes(lcap)
+            starts, info, ws = pl.alloc(lcap * 4), pl.alloc(32), pl.alloc(max(idx_ws, sel_ws))
+            pl.scan(init_state, _lib.REPORT_STATE if per_line or all_patterns else _lib.REPORT_HEAD)
+            self.line_index_async(pl.d, n, starts, lcap, info, delimiter=delimiter, workspace=(ws.ptr, idx_ws))
             if per_line:
-                seg_ws = self.lib.acm_segment_workspace_bytes(max_records)
-                sb = [DeviceArray(max(seg_ws, 16)), DeviceArray(cap * 4), DeviceArray(cap * 4)]
-                bufs += sb
-                self.segment_async(pat, off, max_records, starts, lcap, n, sb[1], sb[2], cap,
-                                   report=_lib.REPORT_STATE if all_patterns else _lib.REPORT_HEAD,
-                                   workspace=(sb[0].ptr, seg_ws))
-                pat, off = sb[1], sb[2]
+                pl.segment(_lib.REPORT_STATE if all_patterns else _lib.REPORT_HEAD, seg_start=starts, segments=lcap)
             if all_patterns:
-                rcap = 8 * cap
-                ex_ws = self.lib.acm_expand_workspace_bytes(max_records)
-                xb = [DeviceArray(ex_ws), DeviceArray(rcap * 4), DeviceArray(rcap * 4)]
-                bufs += xb
-                check(self.lib.acm_expand_matches_async(self.dfa, pat.ptr, off.ptr, max_records, xb[1].ptr, xb[2].ptr,
-                                                        rcap, xb[0].ptr, ex_ws, self.stream), "acm_expand_matches_async")
-                pat, off = xb[1], xb[2]
-            ob = [DeviceArray(rcap * 4)] + [DeviceArray((lcap + 2) * 4) for _ in range(3)]
-            bufs += ob
-            num, rel, beg, nxt = ob
-            self.line_number_async(starts, lcap, info, off.ptr + 4, rcap - 2, num, d_count=off)
-            self.line_select_async(starts, lcap, info, 0, n, off, rcap - 2, rel, beg, nxt, lcap + 2, invert=invert,
+                pl.expand(8 * pl.cap)
+            pat, off, records = pl.pat, pl.off, pl.max_records
+            num, rel, beg, nxt = [pl.alloc(pl.room * 4)] + pl.planes(lcap + 2, 3)
+            self.line_number_async(starts, lcap, info, off.ptr + 4, records, num, d_count=off)
+            self.line_select_async(starts, lcap, info, 0, n, off, records, rel, beg, nxt, lcap + 2, invert=invert,
                                    workspace=(ws.ptr, sel_ws))
-            m = int(pat.to_numpy(np.int32, 1, stream=self.stream)[0])
-            if m > rcap - 2:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, "Matcher.scan_lines", "%d records but planes hold %d"
-                               % (m, rcap - 2))
+            m = pl.count()
             h_info = info.to_numpy(np.int32, 8, stream=self.stream)
             first = 1 + (int(np.uint32(h_info[4])) | int(np.uint32(h_info[5])) << 32)
             p = pat.to_numpy(np.int32, m + 1, stream=self.stream)[1:]
@@ -1467,21 +1211,12 @@ class Matcher:
                             nxt.to_numpy(np.int32, k + 1, stream=self.stream)[1:].astype(np.int64)], axis=1)
             lines = int(h_info[0]) + (1 if n and not h_info[2] else 0)
             return p.copy(), o, ln, sel, lines
-        finally:
-            for b in bufs:
-                b.free()
 
     def scan(self, text, init_state=0):
         """Scan host bytes: upload, scan, download."""
-        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) \
-            else np.ascontiguousarray(text, dtype=np.uint8)
-        self.reserve(max(t.size, 1))
-        d = DeviceArray.from_numpy(t, stream=self.stream)
-        try:
-            self.scan_async(d, t.size, init_state)
+        with _Pipeline(self, "Matcher.scan", text) as p:
+            p.scan(init_state, _lib.REPORT_HEAD)
             return self.fetch()
-        finally:
-            d.free()
 
     def profile(self, enable):
         check(self.lib.acm_scan_profile_enable(self.dfa, int(enable)), "acm_scan_profile_enable")

@@ -276,6 +276,29 @@ def test_streaming(gpu):
     m.close()
 
 
+def test_scan_case_in_mid_stream(gpu):
+    """scan_case on a piece in mid-stream, init_state and before given: an exact pattern that reaches back is kept
+    as far as before lets the pass compare"""
+    m = Matcher(cm.build(FULL), 0, max_text=4096)
+    model = model_of("full")
+    text = b"..cdefabc" + b"de" + b"fabc"
+    cut = 9
+    s = model.walk(text[:cut])[2]
+    for all_patterns in (False, True):
+        sizes = []
+        for before in (text[:cut], text[cut - 3:cut], b""):
+            exp = model.records(text[cut:], all_patterns, init_state=s, before=before)
+            same(m.scan_case(text[cut:], all_patterns, init_state=s, before=before), exp, "before %r" % before)
+            sizes.append(exp[0].size)
+        assert sizes[0] > sizes[2]
+        whole = model.records(text, all_patterns)
+        first = m.scan_case(text[:cut], all_patterns)
+        second = m.scan_case(text[cut:], all_patterns, init_state=first[2], before=text[:cut])
+        same((np.concatenate([first[0], second[0] + cut]), np.concatenate([first[1], second[1]]), second[2]), whole,
+             "two calls")
+    m.close()
+
+
 def test_carry_from_an_overflowed_plane(gpu):
     """a stream in four pieces as chained() runs them, the second piece's case output in fewer cells than its
     records need: its planes are the model's for that capacity, the trailer in the last cell, and the third

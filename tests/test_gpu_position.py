@@ -415,6 +415,37 @@ def test_composition(gpu, name, then):
     m.close()
 
 
+def single(model, t, all_patterns, then, before=b""):
+    """what scan_positions(t, then=then, before=before) returns: one text that starts at offset 0 and ends with
+    its bytes, no segment pass; the pass in between sees `before` in front of it"""
+    states, offs, last = model.walk(t)
+    whole, k = bytes(before) + bytes(t), len(before)
+    ent = [(p, o) for s, o in zip(states.tolist(), offs.tolist()) for p in model.list[s, :model.list_len[s]].tolist()
+           if model.then_keeps(then, p, o + k, whole)]
+    p, o, und = model.entries([e[0] for e in ent], [e[1] for e in ent], all_patterns, (), 0, len(t), len(t))
+    return o.astype(np.uint32), p, last, und
+
+
+@pytest.mark.parametrize("then", [None, "case", "words"])
+def test_single_text(gpu, then):
+    """text instead of texts, with and without before: only the word pass looks at the byte in front of the text"""
+    pats = WITH1 if then == "case" else [p for p, _ in WITH1]
+    model = pm.PositionModel(pats, COMP_W)
+    t = b"abcd " + b" ".join(comp_texts())       # "abcd" at the text start: a word unless a word byte is in front
+    assert len(t) < 4096
+    m = Matcher(pm.build(pats, COMP_W), 0, max_text=len(t))
+    for all_patterns in (False, True):
+        alone = model.records([t], all_patterns, then=then)
+        assert alone[0].size > 15 and alone[3] == 0
+        for before in (b"", b".", b"x_"):
+            exp = single(model, t, all_patterns, then, before)
+            go, gp, last, und = m.scan_positions(t, all_patterns=all_patterns, then=then, before=before)
+            assert np.array_equal(go, exp[0]) and np.array_equal(gp, exp[1]) and (last, und) == exp[2:], (all_patterns, before)
+            as_alone = np.array_equal(exp[0], alone[0]) and np.array_equal(exp[1], alone[1])
+            assert as_alone == (then != "words" or before != b"x_"), (all_patterns, before)
+    m.close()
+
+
 # ------------------------------------------------------------------ 7. an automaton without constraints
 
 

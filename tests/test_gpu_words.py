@@ -190,6 +190,32 @@ def test_planted_boundaries(gpu):
     m.close()
 
 
+def test_bytes_around_the_text(gpu):
+    """scan_words with before and next_byte: the text is a piece of a longer one, found whole by brute force"""
+    pats = [b"cat", b"at", b"-x", b"\xe9t\xe9"]
+    a = Automaton()
+    for p in pats:
+        a.add(p)
+    a.compile()
+    m = Matcher(a, 0, max_text=4096)
+    text = b"cat bobcat at -x (cat) cat"
+    seen = set()
+    for before in (b"", b"bob", b"a ", b"x-", b"_"):
+        for nxt in (-1, ord("s"), ord("."), 0xe9):
+            whole = before + text + (bytes([nxt]) if nxt >= 0 else b"")
+            k = len(before)
+            exp = sorted((o - k, p) for o, p in wm.brute_force(pats, np.frombuffer(whole, np.uint8))
+                         if o - len(pats[p]) + 1 >= k and o < k + len(text))      # the piece's own entries
+            for all_patterns in (True, False):
+                got = m.scan_words(text, all_patterns, before=before, next_byte=nxt)
+                if not all_patterns:                   # the first in list order of every offset
+                    exp = [e for i, e in enumerate(exp) if i == 0 or exp[i - 1][0] != e[0]]
+                assert list(zip(got[0].tolist(), got[1].tolist())) == exp, (before, nxt, all_patterns)
+            seen.add(((2, 0) in exp, (len(text) - 1, 0) in exp))
+    assert len(seen) == 4                              # the first and the last "cat" come and go on their own
+    m.close()
+
+
 def test_argument_errors(gpu):
     a = Automaton()
     a.add(b"abc")
