@@ -163,6 +163,9 @@ NATIVE_API = {
     "acm_rule_workspace_bytes": (C.c_size_t, [_vp, C.c_size_t]),
     "acm_rule_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp,
                                          C.c_size_t, _vp]),
+    "acm_select_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "acm_select_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_long, C.c_uint, _vp, _vp, _vp, C.c_size_t, _vp,
+                                           _vp, C.c_size_t, _vp]),
     "acm_tally_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_tally_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t,
                                           _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

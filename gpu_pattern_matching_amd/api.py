@@ -580,6 +580,15 @@ class _Pipeline:
         self._advance(rule, off, cells, _lib.REPORT_HEAD)
         return text
 
+    def select(self, cells, info, min_start=0):
+        """the current planes become the selected (pattern, offset); returns the third, the start of every match"""
+        ws = self.workspace(self.m.lib.acm_select_workspace_bytes, self.max_records)
+        pat, off, start = self.planes(cells, 3)
+        self.m.select_async(self.pat, self.off, self.max_records, pat, off, cells, info, start_out=start,
+                            min_start=min_start, workspace=ws)
+        self._advance(pat, off, cells, _lib.REPORT_HEAD)
+        return start
+
     # ---- results
 
     def count(self):
@@ -1076,6 +1085,51 @@ class Matcher:
         signatures: the end of its last part's anchor); info: [records that are an operand, (operand, text)
         pairs, (rule, text) pairs evaluated, 0].  Counts are not carried across calls: scan whole texts."""
         return self._sequences(text, texts, lead_begin, init_state, before, out_capacity, True)
+
+    def select_async(self, pat_plane, off_plane, max_records, pat_out, off_out, out_capacity, info, start_out=None,
+                     min_start=0, workspace=None, stream=None):
+        """Enqueue the select pass (acm_select_matches_async) over caller-owned device planes of pattern indices,
+        one record per occurrence (the all-patterns output of the expand, word, case, position or wildcard pass):
+        the leftmost-longest non-overlapping matches, a record (pattern, offset of the anchor's end) each and in
+        start_out, when given, where the match starts.  info: device int32[4]: eligible entries, entries that
+        start in front of min_start, the cursor behind the last match (int64).  The pass orders max_records
+        cells: size it to the planes.  workspace: (ptr, nbytes), or None for a temporary one that lives until
+        the stream has passed it (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        with self._workspace(workspace, st, self.lib.acm_select_workspace_bytes, max_records) as (ws, nb):
+            check(self.lib.acm_select_matches_async(
+                self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, min_start, 0, _ptr(pat_out), _ptr(off_out),
+                _ptr(start_out), out_capacity, _ptr(info), _ptr(ws), nb, st), "acm_select_matches_async")
+
+    def scan_select(self, text=None, texts=None, before=b"", init_state=0, out_capacity=None):
+        """The leftmost-longest non-overlapping matches of the pattern set, what grep -o prints for a list of
+        fixed strings: a REPORT_STATE scan, the segment pass when texts is given (each text matched alone), every
+        pattern of every record (the case pass when the automaton is mixed, else acm_expand_matches_async), the
+        wildcard pass when the automaton has wildcard contexts, the position pass in its all form when it is
+        positioned, then the select pass (acm_select_matches_async).  text: host bytes; or None with texts: a
+        list of bytes-like objects or a (uint8 array, int32 starts) pair.  before: the bytes in front of text,
+        part of the same text: a match may start in them.  Returns (offsets, patterns, starts, info): a record
+        per match, the offset its anchor ends at (a wildcard match ends Automaton.wildcard_lengths(p)[1] bytes
+        behind), its pattern and where it starts (int32: negative inside before); info: [eligible entries,
+        entries that start in front of before, cursor lo, cursor hi].  A selection is not continued across
+        calls: scan whole texts."""
+        with _Pipeline(self, "Matcher.scan_select", text, texts, before=before) as p:
+            lead = -p.before_len
+            p.scan(init_state)
+            if p.nseg:
+                p.segment()
+            p.every_pattern(8 * p.cap)
+            p.max_records = n = p.count()          # from here on every stage is sized by the count in front of it
+            info = p.alloc(16)
+            if self.wild:
+                p.wildcard(n + 2, info, True, lead)
+                p.max_records = n = p.count()
+            if self.positioned:
+                p.position(n + 2, info, True, lead, p.n)
+                p.max_records = n = p.count()
+            start = p.select(out_capacity if out_capacity is not None else n + 2, info, lead)
+            offs, pats, _, starts = p.download(p.count(), start)
+            return offs, pats, starts, info.to_numpy(np.int32, 4, stream=self.stream)
 
     def tally_async(self, pat_plane, off_plane, max_records, class_total, report=0, all_patterns=False,
                     accumulate=False, class_of=None, num_classes=None, seg_start=None, segments=0, seg_class=None,

@@ -53,7 +53,7 @@ double now_us()
 	printf("\nUsage:\n"
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
-	       "             [-w cpu_threads] [-R max] [-I file] [-P file] [-tvxFMAiSWcn]\n"
+	       "             [-w cpu_threads] [-R max] [-I file] [-P file] [-tvxFMAiSWcno]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -136,6 +136,13 @@ double now_us()
 	       "                 found on the device, the -v line becomes \"... found in file '<path>' at line <l>\n"
 	       "                 offset <o> [relative: <r>]\" with the 1-based line number of the match's last byte\n"
 	       "                 in its file, and STATS gains \"Processed lines\", the newlines counted on the device\n"
+	       "  -o             only the leftmost-longest non-overlapping matches (grep -o over the pattern list): of\n"
+	       "                 every pattern that ends somewhere -- the records -A would print -- the one that starts\n"
+	       "                 first, the longest of those, the first added of equals, then the next behind its end;\n"
+	       "                 selected on the device, one -v line per selected match, and the matches counted are the\n"
+	       "                 selected ones.  A match that began in the buffer in front is no candidate: such entries\n"
+	       "                 are counted and reported on stderr at exit; use a larger -G/-B.  Composes with -i, -S,\n"
+	       "                 -W, -I and -P (extension; not with -A, -c, -n, -Q, -K, -E or -F)\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -184,6 +191,7 @@ struct Config {
 	int ext = 0;             // -E: the signatures of -Q and the bodies of -K are read in the extended syntax
 	int rules = 0;           // -K: the sequence pass's records go through the rule pass; its records are reported (seq is set too)
 	int wild = 0;            // -E and some part has a context: the parts' records go through the wildcard pass
+	int only = 0;            // -o: every pattern of the records goes through the select pass (all_patterns is set too)
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
 	long global_ws = -1, local_ws = -1, chunk = -1;
@@ -246,6 +254,10 @@ struct Buffer {   // one of the two staging buffers of a worker
 	void *d_wild_pat = nullptr, *d_wild_off = nullptr, *d_wild_ws = nullptr, *d_wild_info = nullptr;
 	int32_t *h_wild_info = nullptr;
 	size_t wild_ws_bytes = 0;
+	// -o only: the select pass's planes, workspace and info (pinned twin: [1] = entries that began in front of the buffer)
+	void *d_sel_pat = nullptr, *d_sel_off = nullptr, *d_sel_ws = nullptr, *d_sel_info = nullptr;
+	int32_t *h_sel_info = nullptr;
+	size_t sel_ws_bytes = 0;
 	long lead_begin = 0;         // -P, -Q: where the text that goes on into this buffer began, in its stream's coordinates (<= 0)
 	bool end_known = false;      // -P: the stream's last text ends with the stream (its file, or with -t its line, is finished)
 	bool last_of_input = false;  // -P: nothing of the worker's input follows this buffer
@@ -292,6 +304,7 @@ struct Worker {
 	uint64_t undecided = 0;   // -P: end-anchored entries dropped because their text went on in the next buffer
 	uint64_t wild_undecided = 0;   // -E: candidates whose positions reach over a buffer border
 	uint64_t cut_texts = 0;   // -K: texts that go on in the next buffer: not evaluated
+	uint64_t sel_dropped = 0; // -o: entries that began in the buffer in front: no candidates
 	long file_pos = 0;        // -K: bytes of the file being read that the buffers filled so far hold
 	void *d_tail[2] = { nullptr, nullptr };   // -W, -I: the last max_pattern_len bytes of the stream so far, ping-pong
 	int tail_cur = 0;
@@ -398,6 +411,15 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 		CK(acm_rt_malloc(&b.d_pat_all, b.all_cap * 4));
 		CK(acm_rt_malloc(&b.d_off_all, b.all_cap * 4));
 		CK(acm_rt_malloc(&b.d_expand_ws, b.expand_ws_bytes));
+	}
+	if (c.only) {   // (the planes in front hold all_cap cells, the position pass's as many)
+		b.sel_ws_bytes = acm_select_workspace_bytes(b.all_cap - 2);
+		CK(acm_rt_malloc(&b.d_sel_pat, b.all_cap * 4));
+		CK(acm_rt_malloc(&b.d_sel_off, b.all_cap * 4));
+		CK(acm_rt_malloc(&b.d_sel_ws, b.sel_ws_bytes));
+		CK(acm_rt_malloc(&b.d_sel_info, 16));
+		CK(acm_rt_host_alloc((void **)&b.h_sel_info, 64));
+		b.h_sel_info[1] = 0;
 	}
 }
 
@@ -680,6 +702,16 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		off = (int32_t *)b.d_seq_off;
 		cap = b.seq_max + 2;
 	}
+	if (c.only) {
+		// the leftmost-longest non-overlapping matches of every pattern's records, whatever pass wrote them.  The
+		// buffer begins at stream offset 0: an entry that starts in front of it is dropped and counted.
+		CK(acm_select_matches_async(w.dfa, pat, off, cap - 2, 0, 0, (int32_t *)b.d_sel_pat, (int32_t *)b.d_sel_off, nullptr,
+		    b.all_cap, (int32_t *)b.d_sel_info, b.d_sel_ws, b.sel_ws_bytes, s));
+		pat = (int32_t *)b.d_sel_pat;
+		off = (int32_t *)b.d_sel_off;
+		cap = b.all_cap;
+		CK(acm_rt_memcpy_d2h(b.h_sel_info, b.d_sel_info, 16, s));
+	}
 	if (c.rules) {
 		// the rules: the signatures' records counted per text and the conditions evaluated on the device.  Only the
 		// count comes back here; collect() fetches that many records.  (The bucket planes below keep carrying the
@@ -787,7 +819,7 @@ void collect(Worker &w, Buffer &b)
 	CK(acm_rt_event_sync(b.done));   // (this buffer's copies; the next buffer's scan may still be running)
 	if (b.h_all_count && (size_t)*b.h_all_count > b.all_cap - 2) {
 		fprintf(stderr, "ERROR: %s produced %d records for one buffer, the planes hold %zu; use a smaller -G/-B\n",
-		    c.seq ? "-Q" : c.all_patterns ? "-A" : "-P", *b.h_all_count, b.all_cap - 2);
+		    c.seq ? "-Q" : c.only ? "-o" : c.all_patterns ? "-A" : "-P", *b.h_all_count, b.all_cap - 2);
 		exit(1);
 	}
 	if (c.seq && (size_t)*b.h_all_count > b.seq_max) {
@@ -799,6 +831,8 @@ void collect(Worker &w, Buffer &b)
 		w.undecided += (uint64_t)b.h_pos_info[0];
 	if (c.wild)
 		w.wild_undecided += (uint64_t)b.h_wild_info[0];
+	if (c.only)
+		w.sel_dropped += (uint64_t)b.h_sel_info[1];
 	if (c.count && !w.sh->pat_iid.empty()) {
 		if (b.cnt_starts.empty()) {   // the whole buffer goes on with the file in front of it
 			if (b.cnt_prev_file >= 0)
@@ -1039,7 +1073,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:X")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xo")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -1076,6 +1110,7 @@ int main(int argc, char **argv)
 		case 'Q': c.seq_path = optarg; break;
 		case 'E': c.ext = 1; break;
 		case 'X': c.grp = 1; break;
+		case 'o': c.only = 1; break;
 		case 'K': c.rule_path = optarg; break;
 		default: usage();
 		}
@@ -1157,8 +1192,14 @@ int main(int argc, char **argv)
 		printf("ERROR: -n needs binary mode: -t already makes every line a chunk\n");
 		err++;
 	}
+	if (c.only && (c.all_patterns || c.count || c.lineno || c.seq || c.ext || c.follow)) {   // the records are a selection of -A's
+		printf("ERROR: -o cannot be combined with -A, -c, -n, -Q, -K, -E or -F: the records of -o are the selected matches\n");
+		err++;
+	}
 	if (err)
 		usage();
+	if (c.only)   // the select pass takes every pattern of every record: the planes -A would have printed
+		c.all_patterns = 1;
 	auto align16 = [](long &v, const char *what) {   // align_parameters, ocl_aho_grep.c:316-346
 		if (v % 16) {
 			printf("WARNING: %s '%ld' is not 16B aligned. ", what, v);
@@ -1287,12 +1328,13 @@ int main(int argc, char **argv)
 	pthread_barrier_wait(&sh.ready);
 	const double t0 = now_us();
 	size_t matches = 0, reported = 0, bytes = 0, lines = 0, rounds = 0;
-	uint64_t undecided = 0, wild_undecided = 0, cut_texts = 0;
+	uint64_t undecided = 0, wild_undecided = 0, cut_texts = 0, sel_dropped = 0;
 	for (auto &w : workers) {
 		pthread_join(w.thread, nullptr);
 		undecided += w.undecided;
 		wild_undecided += w.wild_undecided;
 		cut_texts += w.cut_texts;
+		sel_dropped += w.sel_dropped;
 		matches += w.matches;
 		reported += w.reported;
 		bytes += w.bytes;
@@ -1335,6 +1377,9 @@ int main(int argc, char **argv)
 	if (cut_texts)   // no silent loss: the rules of these texts were not evaluated
 		fprintf(stderr, "NOTE: %lu texts are cut by a buffer border and their rules were not evaluated (use a larger -G/-B)\n",
 		    (unsigned long)cut_texts);
+	if (sel_dropped)   // no silent loss: a match that began in the buffer in front could have been the leftmost
+		fprintf(stderr, "NOTE: %lu matches began in the buffer in front and were not candidates of -o (use a larger -G/-B)\n",
+		    (unsigned long)sel_dropped);
 	if (undecided) {   // no silent loss: the counts and records above are without them
 		printf("ERROR: %lu end-anchored candidates lie in files that span buffers (raise -B/-G)\n", (unsigned long)undecided);
 		return 1;

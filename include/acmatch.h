@@ -859,6 +859,51 @@ int acm_rule_matches_async(const acm_dfa *, const int32_t *d_seq_plane, const in
     int32_t *d_text_out, int32_t *d_off_out, size_t out_capacity, int32_t *d_info, void *d_workspace,
     size_t workspace_bytes, void *stream);
 
+/* Leftmost-longest non-overlapping selection on the device: the records of a pass in, the matches a
+ * tokenizer, a redactor, a highlighter or grep -o wants out.  No text is read.
+ * Input: planes in the scan's cell layout whose cells are pattern indices, one record per occurrence: the
+ * all-patterns output of acm_expand_matches_async or of the word, case, position or wildcard pass (a HEAD
+ * scan's planes also work: its one pattern per offset).  Offsets non-decreasing.  At most min([0],
+ * max_records) records are looked at.  No segment argument: behind the segment pass no entry crosses a text
+ * start, so the selection over the whole call is the selection per text.
+ * The span of entry (p, o) with L = len(p) and pre, post its wildcard context (both 0 without one) is
+ * [s, e] = [o - L + 1 - pre, o + post], int64 arithmetic: the starts the position and sequence passes use for
+ * a wildcard pattern.  An entry is ELIGIBLE iff its cell is a pattern index, L >= 1 and s >= min_start.  A
+ * cell that is no pattern index, and a pattern of length 0, take part in nothing; an entry with s < min_start
+ * began in front of what the caller has: it is dropped and counted.
+ * The rule: cursor c = min_start; among the eligible entries with s >= c take the smallest s, among those the
+ * largest e, among those the first in the input; emit it, c = e + 1, repeat until none is left.  That is POSIX
+ * leftmost-longest over the pattern set: what grep -o prints for a -F pattern list.
+ * Output, the scan's cell layout and overflow contract ([0] = full count, records, trailer -- the input
+ * trailer unchanged -- at min(count + 1, out_capacity - 1)), in selection order (ascending s, hence ascending
+ * offset):
+ *   d_pat_out    the pattern
+ *   d_off_out    o, unchanged: as everywhere the end of the anchor (a match ends post bytes behind it)
+ *   d_start_out  s; may be NULL (not wanted), else a third plane under the same contract, its trailer cell 0
+ *   d_info       int32[4], required, written whole: [0] eligible entries, [1] entries dropped for
+ *                s < min_start, [2..3] int64 (lo, hi): the cursor behind the last selected entry, min_start
+ *                when nothing was selected
+ * flags must be 0 (room for a second rule).  min_start lies in [INT32_MIN + 1, INT32_MAX].  Results are the
+ * same bytes on every run (integers; no order decided by atomics).  No read leaves the inputs and the
+ * library's tables and no write leaves the outputs and the workspace, whatever the planes hold; offsets out
+ * of order give unspecified records, nothing worse.  The outputs must not overlap the inputs.  Stream-ordered,
+ * no host sync, no allocation, no host read of device data; argument errors (a NULL plane, output or d_info,
+ * out_capacity < 2, flags != 0, min_start out of range, a short workspace) return ACM_ERR_ARG before anything
+ * is enqueued.  The entries are ordered by s with a stable radix sort over max_records cells (cost per
+ * max_records, not per record: size it to the planes), the first entry of every run of equal s walks its run
+ * for the largest e (bounded by the entries that begin at one byte: patterns that are prefixes of one
+ * another, duplicates, contexts), and pointer doubling marks the chosen path (csrc/select.hip):
+ * 16 + ceil(log2(max_records + 1)) launches, whatever the planes hold.  It adds no upload table.  The
+ * workspace query is monotone and a multiple of 256.
+ * Not provided: a selection that continues across calls (an entry that ends in the next piece can beat one
+ * chosen here: select over whole texts; d_info[1] shows the entries lost at the front); leftmost-first
+ * (priority) selection; sequence or rule records as input (they carry no start). */
+size_t acm_select_workspace_bytes(size_t max_records);
+int acm_select_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
+    const int32_t *d_off_plane, size_t max_records, long min_start, unsigned flags,
+    int32_t *d_pat_out, int32_t *d_off_out, int32_t *d_start_out, size_t out_capacity,
+    int32_t *d_info, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* Match tallies: counts of the records of any pass, reduced on the device, so a caller who only counts
  * (a classifier, grep -c, "which signatures hit which file") copies back the counts, not the records.
  * Input: planes in the scan's cell layout; at most min([0], max_records) records are looked at, as in
