@@ -38,6 +38,8 @@ TALLY_ACCUMULATE, TALLY_ALL_PATTERNS = 1, 2
 PATTERN_NOCASE = 1
 POS_FROM_END = 1
 POS_UNBOUNDED = 0x7FFFFFFF
+REPL_FILL = 1
+REPLACEMENT_MAX_LEN = 65535
 SEQ_MAX_PARTS = 32
 GAP_UNBOUNDED = 0x7FFFFFFF
 WILDCARD_MAX_POSITIONS = 4096
@@ -83,6 +85,13 @@ NATIVE_API = {
                                                  C.POINTER(C.c_uint)]),
     "acm_automaton_positioned": (C.c_int, [_vp]),
     "acm_automaton_load_position_file": (C.c_int, [_vp, C.c_char_p]),
+    "acm_automaton_set_replacement": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_int, C.c_uint]),
+    "acm_automaton_clear_replacement": (C.c_int, [_vp, C.c_int]),
+    "acm_automaton_pattern_replacement": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_int),
+                                                    C.POINTER(C.c_uint)]),
+    "acm_automaton_has_replacements": (C.c_int, [_vp]),
+    "acm_automaton_max_replacement_len": (C.c_int, [_vp]),
+    "acm_automaton_load_replacement_file": (C.c_int, [_vp, C.c_char_p]),
     "acm_automaton_add_sequence": (C.c_int, [_vp, _i32p, _i32p, _i32p, C.c_int, C.c_int]),
     "acm_automaton_num_sequences": (C.c_int, [_vp]),
     "acm_automaton_sequence": (C.c_int, [_vp, C.c_int, _i32p, _i32p, C.POINTER(_i32p), C.POINTER(_i32p),
@@ -166,6 +175,9 @@ NATIVE_API = {
     "acm_select_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "acm_select_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_long, C.c_uint, _vp, _vp, _vp, C.c_size_t, _vp,
                                            _vp, C.c_size_t, _vp]),
+    "acm_rewrite_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "acm_rewrite_async": (C.c_int, [_vp, _vp, C.c_size_t, C.c_long, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t,
+                                    _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp]),
     "acm_tally_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_tally_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t,
                                           _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -155,6 +155,46 @@ class Automaton:
             check(n, "acm_automaton_load_position_file")
         return n
 
+    def set_replacement(self, i, data=None, fill=None):
+        """What a match of pattern i becomes in a rewrite (acm_automaton_set_replacement): data, bytes that take
+        the place of the whole span (b"": the span is deleted), or fill, one byte (an int or bytes of length 1) that
+        every byte of the span becomes.  Before or after compile(), but before the Matcher is made: the upload
+        copies the replacements."""
+        if (data is None) == (fill is None):
+            raise ValueError("set_replacement takes data or fill")
+        if fill is not None:
+            b, flags = bytes([fill]) if isinstance(fill, int) else bytes(fill), _lib.REPL_FILL
+        else:
+            b, flags = bytes(data), 0
+        check(self.lib.acm_automaton_set_replacement(self.h, i, b, len(b), flags), "acm_automaton_set_replacement")
+
+    def clear_replacement(self, i):
+        """back to the default: a match of pattern i is copied as it is (acm_automaton_clear_replacement)"""
+        check(self.lib.acm_automaton_clear_replacement(self.h, i), "acm_automaton_clear_replacement")
+
+    def replacement(self, i):
+        """None when pattern i has no replacement, else (bytes, is_fill) as set (acm_automaton_pattern_replacement)"""
+        p, n, fl = C.c_void_p(), C.c_int(), C.c_uint()
+        rc = self.lib.acm_automaton_pattern_replacement(self.h, i, C.byref(p), C.byref(n), C.byref(fl))
+        if rc < 0:
+            check(rc, "acm_automaton_pattern_replacement")
+        if rc == 0:
+            return None
+        return C.string_at(p.value, n.value) if n.value else b"", bool(fl.value & _lib.REPL_FILL)
+
+    @property
+    def has_replacements(self):
+        """some pattern has a replacement (acm_automaton_has_replacements)"""
+        return bool(self.lib.acm_automaton_has_replacements(self.h))
+
+    def load_replacement_file(self, path):
+        """replacements from a file of "<pattern index> <hex bytes or empty>" and "<pattern index> fill <hh>"
+        lines; returns how many"""
+        n = self.lib.acm_automaton_load_replacement_file(self.h, str(path).encode())
+        if n < 0:
+            check(n, "acm_automaton_load_replacement_file")
+        return n
+
     def add_sequence(self, parts, gaps=(), iid=0):
         """An ordered multi-part signature (acm_automaton_add_sequence): parts are pattern indices, gaps one
         (lo, hi) per part but the first, the bytes between that part and the one in front; hi None: no upper
@@ -589,6 +629,19 @@ class _Pipeline:
         self._advance(pat, off, cells, _lib.REPORT_HEAD)
         return start
 
+    def rewrite(self, info, out_capacity, d_text=None, n=None, text_origin=0, at_cells=None):
+        """the rewrite over the current planes (the select pass's); returns (out, at, seg_out): the output bytes, the
+        plane of where every match's replacement begins, and where every text begins (None without texts)"""
+        ws = self.workspace(self.m.lib.acm_rewrite_workspace_bytes, self.max_records, self.nseg)
+        out = self.alloc(max((out_capacity + 15) // 16 * 16, 16))
+        at = self.alloc((at_cells if at_cells is not None else self.max_records + 2) * 4)
+        seg = self.alloc(self.nseg * 4) if self.nseg else None
+        self.m.rewrite_async(self.d if d_text is None else d_text, self.n if n is None else n, self.pat, self.off,
+                             self.max_records, out, out_capacity, info, text_origin=text_origin, at_out=at,
+                             at_capacity=at.nbytes // 4, seg_start=self.d_st, segments=self.nseg, seg_out=seg,
+                             workspace=ws)
+        return out, at, seg
+
     # ---- results
 
     def count(self):
@@ -619,6 +672,8 @@ class Matcher:
         self.num_patterns = automaton.num_patterns
         self.mixed, self.positioned = automaton.mixed_case, automaton.positioned     # as uploaded (scan_sequences)
         self.wild = automaton.has_wildcards
+        # the most bytes one match can add to a rewrite: the longest replacement against a span of one byte
+        self.max_growth = max(self.lib.acm_automaton_max_replacement_len(automaton.h) - 1, 0)
         # post context of every sequence's last part: a match ends that far behind the offset the sequence pass reports
         self.seq_post = np.array([automaton.wildcard_lengths(automaton.sequence(q)[0][-1])[1]
                                   for q in range(automaton.num_sequences)] if self.wild else [], dtype=np.int64)
@@ -1101,6 +1156,23 @@ class Matcher:
                 self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, min_start, 0, _ptr(pat_out), _ptr(off_out),
                 _ptr(start_out), out_capacity, _ptr(info), _ptr(ws), nb, st), "acm_select_matches_async")
 
+    def _select_stages(self, p, init_state, info, out_capacity):
+        """the stages of scan_select on the pipeline p, up to and with the select pass into planes of out_capacity
+        cells (None: what the entries in front of it need); returns the plane of the matches' starts"""
+        lead = -p.before_len
+        p.scan(init_state)
+        if p.nseg:
+            p.segment()
+        p.every_pattern(8 * p.cap)
+        p.max_records = n = p.count()          # from here on every stage is sized by the count in front of it
+        if self.wild:
+            p.wildcard(n + 2, info, True, lead)
+            p.max_records = n = p.count()
+        if self.positioned:
+            p.position(n + 2, info, True, lead, p.n)
+            p.max_records = n = p.count()
+        return p.select(out_capacity if out_capacity is not None else n + 2, info, lead)
+
     def scan_select(self, text=None, texts=None, before=b"", init_state=0, out_capacity=None):
         """The leftmost-longest non-overlapping matches of the pattern set, what grep -o prints for a list of
         fixed strings: a REPORT_STATE scan, the segment pass when texts is given (each text matched alone), every
@@ -1114,22 +1186,57 @@ class Matcher:
         entries that start in front of before, cursor lo, cursor hi].  A selection is not continued across
         calls: scan whole texts."""
         with _Pipeline(self, "Matcher.scan_select", text, texts, before=before) as p:
-            lead = -p.before_len
-            p.scan(init_state)
-            if p.nseg:
-                p.segment()
-            p.every_pattern(8 * p.cap)
-            p.max_records = n = p.count()          # from here on every stage is sized by the count in front of it
             info = p.alloc(16)
-            if self.wild:
-                p.wildcard(n + 2, info, True, lead)
-                p.max_records = n = p.count()
-            if self.positioned:
-                p.position(n + 2, info, True, lead, p.n)
-                p.max_records = n = p.count()
-            start = p.select(out_capacity if out_capacity is not None else n + 2, info, lead)
+            start = self._select_stages(p, init_state, info, out_capacity)
             offs, pats, _, starts = p.download(p.count(), start)
             return offs, pats, starts, info.to_numpy(np.int32, 4, stream=self.stream)
+
+    def rewrite_async(self, d_text, n, pat_plane, off_plane, max_records, out, out_capacity, info, text_origin=0,
+                      at_out=None, at_capacity=0, seg_start=None, segments=0, seg_out=None, workspace=None, stream=None):
+        """Enqueue the rewrite pass (acm_rewrite_async): the device text d_text[0, n) (the byte at offset
+        text_origin + i in d_text[i]) with the span of every record of the select pass's planes replaced by its
+        pattern's replacement (Automaton.set_replacement), into out (16-byte aligned, out_capacity bytes; None
+        with 0: only the figures).  info: device int32[8]: used and skipped records, the output's length (int64),
+        the input bytes inside used spans (int64), 1 if the output was cut at out_capacity, 0.  at_out: a plane
+        of at_capacity cells: where every used record's replacement begins in the output; seg_start and seg_out,
+        int32[segments] each: where every start lies in the output.  workspace: (ptr, nbytes), or None for a
+        temporary one that lives until the stream has passed it (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        with self._workspace(workspace, st, self.lib.acm_rewrite_workspace_bytes, max_records, segments) as (ws, nb):
+            check(self.lib.acm_rewrite_async(
+                self.dfa, _ptr(d_text), n, text_origin, _ptr(pat_plane), _ptr(off_plane), max_records, _ptr(out),
+                out_capacity, _ptr(at_out), at_capacity, _ptr(seg_start), segments, _ptr(seg_out), _ptr(info), _ptr(ws),
+                nb, st), "acm_rewrite_async")
+
+    def scan_rewrite(self, text=None, texts=None, before=b"", init_state=0, out_capacity=None):
+        """The text with every leftmost-longest non-overlapping match replaced by its pattern's replacement
+        (Automaton.set_replacement; a pattern without one: the match as it is): exactly the stages of scan_select,
+        then the rewrite pass (acm_rewrite_async) over before + text.  Returns (out_bytes, info, at, seg_out): the
+        rewritten before + text; info int32[8] as rewrite_async leaves it; at: per match, where its replacement
+        begins in the output; seg_out: per text, where it begins in the output (None without texts).  out_capacity:
+        the room for the output in bytes; by default the text's length plus the growth of the longest replacement
+        for every selected match.  An output that does not fit is ACM_ERR_CAPACITY, never cut silently."""
+        with _Pipeline(self, "Matcher.scan_rewrite", text, texts, before=before) as p:
+            lead = -p.before_len
+            info = p.alloc(32)
+            self._select_stages(p, init_state, info, None)
+            p.max_records = n = p.count()
+            whole, total = p.d, p.n
+            if p.before_len:                                   # the rewrite reads one text: before and text, joined
+                total = p.before_len + p.n
+                whole = p.upload(np.concatenate([p.bf, p.t]))
+            cap = out_capacity if out_capacity is not None else min(total + n * self.max_growth, 2 ** 31 - 17)
+            out, at, seg = p.rewrite(info, cap, whole, total, lead, n + 2)
+            res = info.to_numpy(np.int32, 8, stream=self.stream)
+            if res[6]:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, p.where, "the output has %d bytes but the buffer holds %d" % (
+                    (int(res[3]) << 32) | (int(res[2]) & 0xFFFFFFFF), cap))
+            m = min((int(res[3]) << 32) | (int(res[2]) & 0xFFFFFFFF), cap)
+            data = out.to_numpy(np.uint8, m, stream=self.stream).tobytes()
+            used = int(res[0])
+            at_cells = at.to_numpy(np.int32, used + 2, stream=self.stream)[1:1 + used].copy()
+            seg_cells = seg.to_numpy(np.int32, p.nseg, stream=self.stream) if seg is not None else None
+            return data, res, at_cells, seg_cells
 
     def tally_async(self, pat_plane, off_plane, max_records, class_total, report=0, all_patterns=False,
                     accumulate=False, class_of=None, num_classes=None, seg_start=None, segments=0, seg_class=None,

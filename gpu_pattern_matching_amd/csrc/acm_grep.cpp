@@ -28,10 +28,15 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <set>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "acmatch.h"
@@ -54,6 +59,7 @@ double now_us()
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
 	       "             [-w cpu_threads] [-R max] [-I file] [-P file] [-tvxFMAiSWcno]\n"
+	       "             [-r file -O dir]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -143,6 +149,18 @@ double now_us()
 	       "                 selected ones.  A match that began in the buffer in front is no candidate: such entries\n"
 	       "                 are counted and reported on stderr at exit; use a larger -G/-B.  Composes with -i, -S,\n"
 	       "                 -W, -I and -P (extension; not with -A, -c, -n, -Q, -K, -E or -F)\n"
+	       "  -r file        rewrite: replacements, one per line: '<pattern index> <hex bytes or empty>' -- a match of the\n"
+	       "                 pattern becomes those bytes (none: it is deleted) -- or '<pattern index> fill <hh>' -- every\n"
+	       "                 byte of the match becomes hh (a mask).  Indices count the patterns of -p, then those of -I; a\n"
+	       "                 pattern without a line is matched and left as it is.  Runs what -o runs (-o is implied: the\n"
+	       "                 same matches, lines and counts), then splices every buffer on the device and writes each\n"
+	       "                 input file, rewritten, under the directory of -O.  A file cut by -G is rewritten piece by\n"
+	       "                 piece: a match across the cut is not rewritten (the NOTE of -o counts those).  A buffer whose\n"
+	       "                 output outgrows twice its input is an error.  Composes as -o does (extension; needs -O; not\n"
+	       "                 with -t, -A, -c, -n, -Q, -K, -E or -F)\n"
+	       "  -O dir         with -r: where the rewritten files go: dir/<name> for every file of a directory or list\n"
+	       "                 given with -f; directories are made as needed.  Two inputs of one name, and an output that\n"
+	       "                 is one of the inputs, are refused\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -182,6 +200,8 @@ std::vector<std::string> regular_files_in(std::string dir)
 
 struct Config {
 	std::string pat_path, data_path, loose_path, pos_path, seq_path, rule_path;   // loose_path: -I, pos_path: -P, seq_path: -Q, rule_path: -K
+	std::string repl_path, out_dir;   // -r, -O
+	int rewrite = 0;         // -r: the selected matches are replaced on the device and the rewritten files written (only is set too)
 	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0,
 	    words = 0, count = 0, lineno = 0;
 	int cased = 0;           // -I without -i: the records go through the case pass
@@ -207,6 +227,8 @@ struct Shared {
 	std::vector<int> seq_iid;             // -Q: the id of every sequence, for the -v line
 	std::vector<int> seq_post;            // -E: the post context of every sequence's last part: a match ends that far behind its record
 	std::vector<int> rule_iid;            // -K: the id of every rule, for the -v line
+	std::vector<std::string> out_paths;   // -r: where every input file's rewrite goes
+	std::vector<char> out_begun;          // -r: the file has been created in this run (a file belongs to one worker)
 	int max_pattern_len = 0;
 	pthread_mutex_t print_lock = PTHREAD_MUTEX_INITIALIZER;
 	pthread_barrier_t ready;   // workers have their buffers; the clock starts (the reference
@@ -258,6 +280,13 @@ struct Buffer {   // one of the two staging buffers of a worker
 	void *d_sel_pat = nullptr, *d_sel_off = nullptr, *d_sel_ws = nullptr, *d_sel_info = nullptr;
 	int32_t *h_sel_info = nullptr;
 	size_t sel_ws_bytes = 0;
+	// -r only: the rewrite pass's output, workspace and info, the stream offsets where another file begins and where
+	// those lie in the output; pinned twins.  rw_cap: the bytes the output may have
+	void *d_rw_out = nullptr, *d_rw_ws = nullptr, *d_rw_info = nullptr, *d_rw_start = nullptr, *d_rw_seg = nullptr;
+	int32_t *h_rw_info = nullptr, *h_rw_seg = nullptr;
+	unsigned char *h_rw_out = nullptr;
+	size_t rw_ws_bytes = 0, rw_cap = 0, rw_max = 0;
+	std::vector<int32_t> rw_starts, rw_files;
 	long lead_begin = 0;         // -P, -Q: where the text that goes on into this buffer began, in its stream's coordinates (<= 0)
 	bool end_known = false;      // -P: the stream's last text ends with the stream (its file, or with -t its line, is finished)
 	bool last_of_input = false;  // -P: nothing of the worker's input follows this buffer
@@ -421,6 +450,19 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 		CK(acm_rt_host_alloc((void **)&b.h_sel_info, 64));
 		b.h_sel_info[1] = 0;
 	}
+	if (c.rewrite) {   // (disjoint matches of a byte or more: no more of them than text bytes)
+		b.rw_max = std::min(b.all_cap - 2, size);
+		b.rw_cap = std::min(2 * size + 65536 + 16, (size_t)0x7FFFFFE0ul);
+		b.rw_ws_bytes = acm_rewrite_workspace_bytes(b.rw_max, G);
+		CK(acm_rt_malloc(&b.d_rw_out, b.rw_cap + 16));
+		CK(acm_rt_malloc(&b.d_rw_ws, b.rw_ws_bytes));
+		CK(acm_rt_malloc(&b.d_rw_info, 32));
+		CK(acm_rt_malloc(&b.d_rw_start, (G + 1) * 4));
+		CK(acm_rt_malloc(&b.d_rw_seg, (G + 1) * 4));
+		CK(acm_rt_host_alloc((void **)&b.h_rw_out, b.rw_cap + 16));
+		CK(acm_rt_host_alloc((void **)&b.h_rw_info, 64));
+		CK(acm_rt_host_alloc((void **)&b.h_rw_seg, (G + 1) * 4));
+	}
 }
 
 // binary mode: fixed chunks, a short tail chunk per file (databuf.c:326-407)
@@ -507,6 +549,15 @@ void prepare(Worker &w, Buffer &b)
 			}
 			w.cnt_file = b.file_ids[i];
 		}
+	}
+	if (c.rewrite) {   // the first chunk, and every chunk of another file than the chunk before it
+		b.rw_starts.clear();
+		b.rw_files.clear();
+		for (int i = 0; i < chunks; i++)
+			if (i == 0 || b.file_ids[i] != b.file_ids[i - 1]) {
+				b.rw_starts.push_back(b.starts[i]);
+				b.rw_files.push_back(b.file_ids[i]);
+			}
 	}
 	if (c.segmented) {
 		// a text begins at every chunk of another file than the chunk before it (-t: and at every chunk
@@ -712,6 +763,17 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		cap = b.all_cap;
 		CK(acm_rt_memcpy_d2h(b.h_sel_info, b.d_sel_info, 16, s));
 	}
+	if (c.rewrite) {
+		// the buffer's stream with every selected match replaced, and where every file's bytes begin in it.  Only the
+		// figures come back here; collect() fetches the output once it knows its length.  (In front of the remap below:
+		// the offsets are still the stream's.)
+		const size_t ns = b.rw_starts.size();
+		CK(acm_rt_memcpy_h2d(b.d_rw_start, b.rw_starts.data(), ns * 4, s));
+		CK(acm_rewrite_async(w.dfa, b.text, b.stream_len, 0, pat, off, b.rw_max, b.d_rw_out, b.rw_cap, nullptr, 0,
+		    (const int32_t *)b.d_rw_start, ns, (int32_t *)b.d_rw_seg, (int32_t *)b.d_rw_info, b.d_rw_ws, b.rw_ws_bytes, s));
+		CK(acm_rt_memcpy_d2h(b.h_rw_info, b.d_rw_info, 32, s));
+		CK(acm_rt_memcpy_d2h(b.h_rw_seg, b.d_rw_seg, ns * 4, s));
+	}
 	if (c.rules) {
 		// the rules: the signatures' records counted per text and the conditions evaluated on the device.  Only the
 		// count comes back here; collect() fetches that many records.  (The bucket planes below keep carrying the
@@ -812,6 +874,44 @@ void collect_rules(Worker &w, Buffer &b)
 	}
 }
 
+// mkdir -p of the directories a path lies in
+void make_parents(const std::string &path)
+{
+	for (size_t at = path.find('/', 1); at != std::string::npos; at = path.find('/', at + 1))
+		mkdir(path.substr(0, at).c_str(), 0777);   // (an error shows when the file is opened)
+}
+
+// -r: the rewritten stream of the buffer copied back -- its length came with the buffer -- and every file's piece of
+// it appended to that file's output
+void collect_rewrite(Worker &w, Buffer &b)
+{
+	Shared &sh = *w.sh;
+	const size_t ns = b.rw_starts.size();
+	const int64_t m = (int64_t)(((uint64_t)(uint32_t)b.h_rw_info[3] << 32) | (uint32_t)b.h_rw_info[2]);
+	if (b.h_rw_info[6] || m < 0 || (size_t)m > b.rw_cap) {
+		fprintf(stderr, "ERROR: -r: the rewrite of a buffer of '%s' has %ld bytes, the output buffer holds %zu; use a smaller -G/-B\n",
+		    ns ? sh.files[(size_t)b.rw_files[0]].c_str() : "?", (long)m, b.rw_cap);
+		exit(1);
+	}
+	if (m > 0) {
+		CK(acm_rt_memcpy_d2h(b.h_rw_out, b.d_rw_out, (size_t)m, w.stream));
+		CK(acm_rt_stream_sync(w.stream));
+	}
+	for (size_t k = 0; k < ns; k++) {
+		const size_t f = (size_t)b.rw_files[k];
+		const int64_t lo = std::min<int64_t>(std::max(b.h_rw_seg[k], 0), m);
+		const int64_t hi = k + 1 < ns ? std::min<int64_t>(std::max<int64_t>(b.h_rw_seg[k + 1], lo), m) : m;
+		if (!sh.out_begun[f])
+			make_parents(sh.out_paths[f]);
+		FILE *fp = fopen(sh.out_paths[f].c_str(), sh.out_begun[f] ? "ab" : "wb");
+		if (!fp || fwrite(b.h_rw_out + lo, 1, (size_t)(hi - lo), fp) != (size_t)(hi - lo) || fclose(fp) != 0) {
+			fprintf(stderr, "ERROR: -O: cannot write '%s': %s\n", sh.out_paths[f].c_str(), strerror(errno));
+			exit(1);
+		}
+		sh.out_begun[f] = 1;
+	}
+}
+
 // wait for the buffer, walk the bucket planes (databuf.c:747-782), print -v lines
 void collect(Worker &w, Buffer &b)
 {
@@ -833,6 +933,8 @@ void collect(Worker &w, Buffer &b)
 		w.wild_undecided += (uint64_t)b.h_wild_info[0];
 	if (c.only)
 		w.sel_dropped += (uint64_t)b.h_sel_info[1];
+	if (c.rewrite)
+		collect_rewrite(w, b);
 	if (c.count && !w.sh->pat_iid.empty()) {
 		if (b.cnt_starts.empty()) {   // the whole buffer goes on with the file in front of it
 			if (b.cnt_prev_file >= 0)
@@ -1073,7 +1175,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xo")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xor:O:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o, r, O
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -1111,6 +1213,8 @@ int main(int argc, char **argv)
 		case 'E': c.ext = 1; break;
 		case 'X': c.grp = 1; break;
 		case 'o': c.only = 1; break;
+		case 'r': c.repl_path = optarg; break;
+		case 'O': c.out_dir = optarg; break;
 		case 'K': c.rule_path = optarg; break;
 		default: usage();
 		}
@@ -1191,6 +1295,25 @@ int main(int argc, char **argv)
 	if (c.lineno && c.text_mode) {
 		printf("ERROR: -n needs binary mode: -t already makes every line a chunk\n");
 		err++;
+	}
+	if (!c.repl_path.empty() && c.out_dir.empty()) {
+		printf("ERROR: -r needs -O: the directory the rewritten files go to\n");
+		err++;
+	}
+	if (c.repl_path.empty() && !c.out_dir.empty()) {
+		printf("ERROR: -O needs -r: the replacements\n");
+		err++;
+	}
+	if (!c.repl_path.empty() && access(c.repl_path.c_str(), R_OK) != 0) {
+		printf("ERROR: File '%s' does not exist\n", c.repl_path.c_str()); err++;
+	}
+	c.rewrite = !c.repl_path.empty() && !c.out_dir.empty();
+	if ((!c.repl_path.empty() || !c.out_dir.empty()) &&
+	    (c.text_mode || c.all_patterns || c.count || c.lineno || c.seq || c.ext || c.follow)) {   // the rewrite is of -o's matches, of whole buffers
+		printf("ERROR: -r cannot be combined with -t, -A, -c, -n, -Q, -K, -E or -F: it rewrites the matches -o selects\n");
+		err++;
+	} else if (c.rewrite) {
+		c.only = 1;
 	}
 	if (c.only && (c.all_patterns || c.count || c.lineno || c.seq || c.ext || c.follow)) {   // the records are a selection of -A's
 		printf("ERROR: -o cannot be combined with -A, -c, -n, -Q, -K, -E or -F: the records of -o are the selected matches\n");
@@ -1290,6 +1413,39 @@ int main(int argc, char **argv)
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}
+	if (c.rewrite && acm_automaton_load_replacement_file(aut, c.repl_path.c_str()) < 0) {
+		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
+		return 1;
+	}
+	if (c.rewrite) {   // a file of a directory or a list goes to <-O>/<its name>
+		for (const std::string &f : sh.files) {
+			const size_t slash = f.rfind('/');
+			sh.out_paths.push_back(c.out_dir + "/" + (slash == std::string::npos ? f : f.substr(slash + 1)));
+		}
+		sh.out_begun.assign(sh.files.size(), 0);
+		// two inputs of one name (a list over several directories) would share an output, and an output that is an
+		// input (-O names the directory of -f) would be truncated while it is read: both are refused before anything runs
+		std::map<std::string, size_t> seen;
+		std::set<std::pair<dev_t, ino_t>> inputs;
+		for (size_t f = 0; f < sh.files.size(); f++) {
+			auto at = seen.emplace(sh.out_paths[f], f);
+			if (!at.second) {
+				fprintf(stderr, "ERROR: -O: '%s' and '%s' would both be written to '%s'\n", sh.files[at.first->second].c_str(),
+				    sh.files[f].c_str(), sh.out_paths[f].c_str());
+				return 1;
+			}
+			struct stat st;
+			if (fstat(sh.fds[f], &st) == 0)
+				inputs.insert({ st.st_dev, st.st_ino });
+		}
+		for (size_t f = 0; f < sh.files.size(); f++) {
+			struct stat st;
+			if (stat(sh.out_paths[f].c_str(), &st) == 0 && inputs.count({ st.st_dev, st.st_ino })) {
+				fprintf(stderr, "ERROR: -O: the output '%s' is an input file; give -O another directory\n", sh.out_paths[f].c_str());
+				return 1;
+			}
+		}
+	}
 	CK(acm_automaton_compile(aut));
 	const int states = acm_automaton_num_states(aut);
 	const int np = acm_automaton_num_patterns(aut);
@@ -1342,6 +1498,12 @@ int main(int argc, char **argv)
 		rounds += w.rounds;
 	}
 	const double secs = (now_us() - t0) / 1e6;
+	for (size_t f = 0; c.rewrite && f < sh.files.size(); f++)
+		if (!sh.out_begun[f]) {   // a file of no bytes: no buffer held a piece of it
+			make_parents(sh.out_paths[f]);
+			if (FILE *fp = fopen(sh.out_paths[f].c_str(), "wb"))
+				fclose(fp);
+		}
 	if (c.count) {
 		std::vector<uint64_t> per_file(sh.files.size(), 0), per_pat(sh.pat_iid.size(), 0);
 		for (auto &w : workers) {

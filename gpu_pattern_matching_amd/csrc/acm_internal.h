@@ -45,6 +45,13 @@ enum RuleOp : int32_t {
 };
 constexpr int kRuleStack = ACM_RULE_MAX_NESTING + 2;
 
+// a pattern's replacement (acm_automaton_set_replacement), host and acm_dfa::d_repl_ent
+enum ReplKind : int {
+	kReplNone = 0,    // the span is copied as it is
+	kReplBytes = 1,   // the span becomes the replacement's bytes
+	kReplFill = 2,    // every byte of the span becomes the fill byte
+};
+
 }  // namespace acm
 
 // Host automaton.  States carry two numberings:
@@ -85,6 +92,11 @@ struct acm_automaton {
 			std::vector<uint8_t> bytes;
 		};
 		std::vector<Group> wild_groups;
+		// what a match of this pattern becomes in a rewrite (acm_automaton_set_replacement); the default is none:
+		// the span is copied.  compile never reads these: acm_dfa_upload copies them for the rewrite pass
+		// (rewrite.hip)
+		int repl_kind = acm::kReplNone;
+		std::vector<unsigned char> repl;       // kReplBytes: the bytes (none: delete); kReplFill: the one fill byte
 	};
 	// the distinct context sets of two or more bytes, interned: at most 256
 	std::vector<std::array<uint8_t, 32>> wild_classes;

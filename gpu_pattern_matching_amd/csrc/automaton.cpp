@@ -242,6 +242,135 @@ static int hex_nibble(unsigned char c)
 	return -1;
 }
 
+// ---- replacements ---------------------------------------------------------------
+
+extern "C" int acm_automaton_set_replacement(acm_automaton *a, int index, const unsigned char *bytes, int n, unsigned flags)
+{
+	if (!a || index < 0 || index >= (int)a->patterns.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_set_replacement: index out of range");
+	if (flags & ~(unsigned)ACM_REPL_FILL)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_set_replacement: unknown flag bits 0x%x", flags & ~(unsigned)ACM_REPL_FILL);
+	if (n < 0 || (n > 0 && !bytes))
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_set_replacement: bad bytes (n = %d)", n);
+	if ((flags & ACM_REPL_FILL) && n != 1)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_set_replacement: a fill takes one byte, not %d", n);
+	if (n > ACM_REPLACEMENT_MAX_LEN)
+		return acm::fail(ACM_ERR_LIMIT, "acm_automaton_set_replacement: %d bytes, at most %d", n, ACM_REPLACEMENT_MAX_LEN);
+	acm_automaton::Pattern &p = a->patterns[index];
+	p.repl_kind = (flags & ACM_REPL_FILL) ? acm::kReplFill : acm::kReplBytes;
+	p.repl.assign(bytes, bytes + n);
+	return ACM_OK;
+}
+
+extern "C" int acm_automaton_clear_replacement(acm_automaton *a, int index)
+{
+	if (!a || index < 0 || index >= (int)a->patterns.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_clear_replacement: index out of range");
+	a->patterns[index].repl_kind = acm::kReplNone;
+	a->patterns[index].repl.clear();
+	return ACM_OK;
+}
+
+extern "C" int acm_automaton_pattern_replacement(const acm_automaton *a, int index, const unsigned char **bytes, int *n,
+    unsigned *flags)
+{
+	if (!a || index < 0 || index >= (int)a->patterns.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_pattern_replacement: index out of range");
+	const acm_automaton::Pattern &p = a->patterns[index];
+	if (bytes) *bytes = p.repl.data();
+	if (n) *n = (int)p.repl.size();
+	if (flags) *flags = p.repl_kind == acm::kReplFill ? (unsigned)ACM_REPL_FILL : 0u;
+	return p.repl_kind != acm::kReplNone ? 1 : 0;
+}
+
+extern "C" int acm_automaton_has_replacements(const acm_automaton *a)
+{
+	if (a)
+		for (auto &p : a->patterns)
+			if (p.repl_kind != acm::kReplNone)
+				return 1;
+	return 0;
+}
+
+extern "C" int acm_automaton_max_replacement_len(const acm_automaton *a)
+{
+	int longest = 0;
+	if (a)
+		for (auto &p : a->patterns)
+			if (p.repl_kind == acm::kReplBytes)
+				longest = std::max(longest, (int)p.repl.size());
+	return longest;
+}
+
+extern "C" int acm_automaton_load_replacement_file(acm_automaton *a, const char *path)
+{
+	if (!a || !path)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_load_replacement_file: bad arguments");
+	FILE *fp = fopen(path, "r");
+	if (!fp)
+		return acm::fail(ACM_ERR_IO, "cannot open replacement file '%s': %s", path, strerror(errno));
+	struct Line {
+		int32_t index;
+		unsigned flags;
+		std::vector<unsigned char> bytes;
+	};
+	std::vector<Line> lines;   // applied only when the whole file has parsed
+	std::vector<char> buf(2 * (size_t)ACM_REPLACEMENT_MAX_LEN + 64);   // the longest legal line and its index
+	int line_no = 0, rc = ACM_OK;
+	while (rc == ACM_OK && fgets(buf.data(), (int)buf.size(), fp)) {
+		line_no++;
+		std::string line(buf.data());
+		const bool whole = !line.empty() && line.back() == '\n';
+		while (!line.empty() && (line.back() == '\n' || line.back() == '\r' || line.back() == ' ' || line.back() == '\t'))
+			line.pop_back();
+		const char *s = line.c_str();
+		while (*s == ' ' || *s == '\t')
+			s++;
+		if (!*s || *s == '#')
+			continue;
+		Line l{ 0, 0, {} };
+		bool ok = (whole || feof(fp)) && pos_field(s, l.index);
+		if (ok) {
+			while (*s == ' ' || *s == '\t')
+				s++;
+			if (!strncmp(s, "fill", 4) && (s[4] == ' ' || s[4] == '\t')) {
+				s += 4;
+				while (*s == ' ' || *s == '\t')
+					s++;
+				const int hi = hex_nibble((unsigned char)s[0]), lo = hi < 0 ? -1 : hex_nibble((unsigned char)s[1]);
+				ok = lo >= 0 && !s[2];
+				if (ok) {
+					l.flags = ACM_REPL_FILL;
+					l.bytes.push_back((unsigned char)(hi << 4 | lo));
+				}
+			} else {
+				for (; ok && *s; s += 2) {
+					const int hi = hex_nibble((unsigned char)s[0]), lo = hi < 0 ? -1 : hex_nibble((unsigned char)s[1]);
+					ok = lo >= 0;
+					if (ok)
+						l.bytes.push_back((unsigned char)(hi << 4 | lo));
+				}
+				ok = ok && l.bytes.size() <= (size_t)ACM_REPLACEMENT_MAX_LEN;
+			}
+		}
+		if (!ok)
+			rc = acm::fail(ACM_ERR_PARSE, "%s:%d: not '<pattern index> <hex bytes or empty>' or '<pattern index> fill <hh>'", path,
+			    line_no);
+		else if (l.index >= (int)a->patterns.size())
+			rc = acm::fail(ACM_ERR_PARSE, "%s:%d: pattern index %d out of range (%zu patterns)", path, line_no, l.index,
+			    a->patterns.size());
+		else
+			lines.push_back(std::move(l));
+	}
+	fclose(fp);
+	if (rc != ACM_OK)
+		return rc;
+	for (const Line &l : lines)
+		if ((rc = acm_automaton_set_replacement(a, l.index, l.bytes.data(), (int)l.bytes.size(), l.flags)) != ACM_OK)
+			return rc;
+	return (int)lines.size();
+}
+
 // ---- sequences -----------------------------------------------------------------
 
 extern "C" int acm_automaton_add_sequence(acm_automaton *a, const int32_t *parts, const int32_t *gap_lo, const int32_t *gap_hi,

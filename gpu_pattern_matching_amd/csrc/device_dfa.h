@@ -146,4 +146,10 @@ struct acm_dfa {
 	int32_t *d_grp_ent = nullptr;        // [patterns][2] {first group in d_grp, groups}
 	int32_t *d_grp = nullptr;            // [groups][4] {first byte counted from the span's, width, count | negated << 31, word index in d_grp_pool}
 	uint32_t *d_grp_pool = nullptr;      // the strings, each zero-padded to whole words
+
+	// an automaton with replacements only (acm_automaton_has_replacements at upload), for the rewrite pass
+	// (rewrite.hip); null otherwise: every span is then copied as it is
+	bool replacements = false;
+	int32_t *d_repl_ent = nullptr;       // [patterns][4] {acm::ReplKind, bytes of the replacement, where they begin in d_repl_blob, the fill byte}
+	uint8_t *d_repl_blob = nullptr;      // the replacements' bytes, back to back
 };

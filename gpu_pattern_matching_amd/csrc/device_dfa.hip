@@ -392,6 +392,24 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 			if (rc == ACM_OK) rc = upload(&d->d_grp, grp.data(), grp.size(), &d->device_bytes);
 			if (rc == ACM_OK) rc = upload(&d->d_grp_pool, pool.data(), pool.size(), &d->device_bytes);
 		}
+		// an automaton with replacements (acm_automaton_has_replacements): per pattern what a match becomes, and
+		// the replacements' bytes in one blob (rewrite.hip).  Allocations of their own, as above.
+		d->replacements = acm_automaton_has_replacements(a) != 0;
+		if (rc == ACM_OK && d->replacements) {
+			std::vector<int32_t> ent(4 * a->patterns.size());
+			std::vector<uint8_t> blob;
+			for (size_t i = 0; i < a->patterns.size(); i++) {
+				const acm_automaton::Pattern &p = a->patterns[i];
+				ent[4 * i] = p.repl_kind;
+				ent[4 * i + 1] = p.repl_kind == acm::kReplBytes ? (int32_t)p.repl.size() : 0;
+				ent[4 * i + 2] = (int32_t)blob.size();
+				ent[4 * i + 3] = p.repl_kind == acm::kReplFill ? (int32_t)p.repl[0] : 0;
+				if (p.repl_kind == acm::kReplBytes)
+					blob.insert(blob.end(), p.repl.begin(), p.repl.end());
+			}
+			rc = upload(&d->d_repl_ent, ent.data(), ent.size(), &d->device_bytes);
+			if (rc == ACM_OK) rc = upload(&d->d_repl_blob, blob.data(), blob.size(), &d->device_bytes);
+		}
 	} catch (const std::bad_alloc &) {
 		rc = acm::fail(ACM_ERR_NOMEM, "acm_dfa_upload: out of host memory");
 	}
@@ -462,6 +480,8 @@ extern "C" void acm_dfa_release(acm_dfa *d)
 		hipFree(d->d_grp_ent);
 		hipFree(d->d_grp);
 		hipFree(d->d_grp_pool);
+		hipFree(d->d_repl_ent);
+		hipFree(d->d_repl_blob);
 		free_small(d, d->d_depth);
 		free_small(d, d->d_class);
 		free_small(d, d->d_sv_bloom);

@@ -1,5 +1,5 @@
 // The record-pass core: what the passes that run behind a scan (segment.hip, tally.hip, lines.hip, sequence.hip,
-// rule.hip, expand in post.hip, and through entry_pass.h word.hip, case.hip, position.hip and wildcard.hip) share.  Internal to the
+// rule.hip, select.hip, rewrite.hip, expand in post.hip, and through entry_pass.h word.hip, case.hip, position.hip and wildcard.hip) share.  Internal to the
 // library, gfx950 only.  DESIGN.md 6f.
 //
 // A pass runs a fixed grid of at most kMaxBlocks blocks of kThreads threads.  Every block owns a
@@ -250,6 +250,37 @@ __device__ __forceinline__ uint32_t tile_row(const uint32_t *wave_cnt, int q, ui
 		tile_total += wave_cnt[q * kWaves + w];
 	}
 	return before;
+}
+
+// ---- the span of a record ----
+
+// What a record (p, o) of a pattern plane covers in the text, for the passes that need where a match begins and ends
+// (select.hip, rewrite.hip; the contract is acm_select_matches_async's): [s, e] = [o - L + 1 - pre, o + post], int64,
+// L the pattern's length and pre, post its wildcard context (both 0 without one).  ok: p is a pattern index and
+// L >= 1.  pat_len: [patterns]; wild_ent: [patterns] {cell index, pre, post, length}, or null for a set without contexts.
+struct Span {
+	int64_t s, e;
+	bool ok;
+};
+
+__device__ __forceinline__ Span span_of(const uint32_t *pat_len, const int4 *wild_ent, uint32_t num_patterns, uint32_t p, int32_t o)
+{
+	Span sp{ 0, 0, false };
+	if (p >= num_patterns)   // (a cell may hold anything)
+		return sp;
+	int64_t L, pre = 0, post = 0;
+	if (wild_ent) {
+		const int4 w = wild_ent[p];
+		pre = w.y;
+		post = w.z;
+		L = w.w;
+	} else {
+		L = pat_len[p];
+	}
+	sp.ok = L >= 1;
+	sp.s = (int64_t)o - L + 1 - pre;
+	sp.e = (int64_t)o + post;
+	return sp;
 }
 
 // ---- output planes ----

@@ -58,31 +58,11 @@ struct SelArgs {
 	int32_t *info;
 };
 
-struct Span {
-	int64_t s, e;
-	bool ok;   // a pattern of length >= 1
-};
-
 __device__ __forceinline__ uint32_t records_of(const SelArgs &g) { return min((uint32_t)g.pat_plane[0], g.n); }
 
 __device__ __forceinline__ Span span_of(const SelArgs &g, uint32_t p, int32_t o)
 {
-	Span sp{ 0, 0, false };
-	if (p >= g.num_patterns)   // (a cell may hold anything)
-		return sp;
-	int64_t L, pre = 0, post = 0;
-	if (g.wild_ent) {
-		const int4 w = g.wild_ent[p];
-		pre = w.y;
-		post = w.z;
-		L = w.w;
-	} else {
-		L = g.pat_len[p];
-	}
-	sp.ok = L >= 1;
-	sp.s = (int64_t)o - L + 1 - pre;
-	sp.e = (int64_t)o + post;
-	return sp;
+	return acm_rp::span_of(g.pat_len, g.wild_ent, g.num_patterns, p, o);
 }
 
 // the span of input cell at < m

@@ -148,6 +148,38 @@ int acm_automaton_pattern_position(const acm_automaton *, int index, int32_t *lo
 int acm_automaton_positioned(const acm_automaton *);
 int acm_automaton_load_position_file(acm_automaton *, const char *path);
 
+/* Replacements: what a match of a pattern becomes in a rewrite (acm_rewrite_async).  The span [s, e] of a
+ * match is the select pass's: wildcard contexts included.
+ *   flags 0          the whole span becomes bytes[0, n); n == 0 (bytes may then be NULL) deletes it.  n up to
+ *                    ACM_REPLACEMENT_MAX_LEN, above it ACM_ERR_LIMIT
+ *   ACM_REPL_FILL    n must be 1: every byte of the span becomes bytes[0] and the length is kept (a mask)
+ *   none set         the default: the span is copied as it is (the pattern still takes part in the selection);
+ *                    acm_automaton_clear_replacement returns to it
+ * A bad index, unknown flag bits, n < 0, a NULL bytes with n > 0 or a fill with n != 1 are ACM_ERR_ARG.
+ * acm_automaton_pattern_replacement returns 1 if pattern `index` has a replacement, else 0 (negative: a bad
+ * index), and the replacement as set: a borrowed pointer, its length and flags (any pointer may be NULL).
+ * acm_automaton_has_replacements is 1 if some pattern has one; acm_automaton_max_replacement_len is the length of
+ * the longest replacement that is no fill (0 without one): less one, the most bytes a match can add to a rewrite.
+ * Replacements do not enter acm_automaton_compile: tables, digests, self-tests and acm_dfa_device_bytes of an
+ * automaton without replacements are what they were, and no scan looks at one.  They may be set before or
+ * after compile; acm_dfa_upload takes a copy (an entry per pattern and one blob of bytes, only when at least
+ * one is set), so one set later does not reach that acm_dfa.
+ * acm_automaton_load_replacement_file reads one replacement per line: "<pattern index> <hex bytes or empty>"
+ * or "<pattern index> fill <hh>" (decimal index; hex digit pairs without blanks between them).  A line whose
+ * first non-blank byte is '#' and blank lines are skipped.  A malformed line or an index out of range is
+ * ACM_ERR_PARSE and acm_last_error names the line; nothing is applied then.  Returns the number applied.
+ * Not provided: replacements that refer to the matched bytes (case-preserving, back-references). */
+enum { ACM_REPL_FILL = 1 };
+#define ACM_REPLACEMENT_MAX_LEN 65535
+int acm_automaton_set_replacement(acm_automaton *, int index, const unsigned char *bytes, int n,
+    unsigned flags);
+int acm_automaton_clear_replacement(acm_automaton *, int index);
+int acm_automaton_pattern_replacement(const acm_automaton *, int index, const unsigned char **bytes,
+    int *n, unsigned *flags);
+int acm_automaton_has_replacements(const acm_automaton *);
+int acm_automaton_max_replacement_len(const acm_automaton *);
+int acm_automaton_load_replacement_file(acm_automaton *, const char *path);
+
 /* Ordered multi-part signatures: the relation BETWEEN patterns.  A SEQUENCE is k parts, 1 <= k <=
  * ACM_SEQ_MAX_PARTS: pattern indices p_0 .. p_{k-1}, k - 1 gaps (lo_j, hi_j), j = 1 .. k-1, and a user id
  * iid.  A gap has lo >= 0 and hi >= 0, or hi == ACM_GAP_UNBOUNDED; lo > hi is legal and never matches (as
@@ -903,6 +935,54 @@ int acm_select_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
     const int32_t *d_off_plane, size_t max_records, long min_start, unsigned flags,
     int32_t *d_pat_out, int32_t *d_off_out, int32_t *d_start_out, size_t out_capacity,
     int32_t *d_info, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Match rewriting on the device: the text and the selected matches in, the text with every match replaced
+ * (acm_automaton_set_replacement: replaced, masked or deleted) out.  What a redactor or a normaliser wants,
+ * without copying records and text back to splice on the host.
+ * Text: the scan's contract (16-byte aligned, readable up to n rounded up to 16, n <= 2^31 - 17); d_text[i] is
+ * the byte at offset text_origin + i, text_end = text_origin + n, as in acm_line_index_async.  text_origin
+ * lies in [INT32_MIN, INT32_MAX].
+ * Input records: the pattern and offset planes acm_select_matches_async wrote: spans disjoint and ascending.
+ * At most min([0], max_records) records are looked at.  The span [s, e] of a record is the select pass's
+ * (int64).  A record is USED iff its cell is a pattern index, L >= 1 and text_origin <= s <= e < text_end;
+ * any other record is skipped and counted.  Spans that overlap or descend (planes that did not come from
+ * select) give unspecified output bytes, nothing worse.
+ * Output: the text with every used span replaced by its pattern's replacement (a pattern without one: the
+ * span as it is), m bytes (int64).  d_out receives the first min(m, out_capacity) bytes; no byte of d_out at
+ * or behind min(m, out_capacity) is written.  d_out == NULL with out_capacity == 0 is legal: only d_info,
+ * d_at_out and d_seg_out are produced.  d_out is 16-byte aligned and overlaps neither the text nor the planes.
+ *   d_at_out     may be NULL (not wanted), else the scan's cell layout and overflow contract over at_capacity
+ *                cells: [0] the used records, then for each used record, in input order, the output offset
+ *                (from 0, saturated to INT32_MAX) at which its replacement begins, then a trailer cell 0
+ *   d_seg_out    with d_seg_start, both or neither (segments == 0): int32[segments]; for each start x the output
+ *                offset of the first output byte that comes from an offset >= x: clamp(x, text_origin,
+ *                text_end) - text_origin + the sum over the used records with s < x of (replacement length -
+ *                span length), saturated to int32.  Where each packed text begins after the rewrite.
+ *   d_info       int32[8], required, written whole: [0] used records, [1] skipped records, [2..3] m as (lo,
+ *                hi), [4..5] the input bytes inside used spans (lo, hi), [6] 1 iff m > out_capacity and d_out
+ *                is not NULL (the output was cut: never silently), [7] 0
+ * An uploaded set without replacements is legal: the output equals the text.  Results are the same bytes on
+ * every run (no order decided by atomics).  Whatever the planes hold, no read leaves the inputs and the
+ * library's tables and no write leaves the outputs and the workspace.  Stream-ordered, no host sync, no
+ * allocation, no host read of device data; argument errors (a NULL text with n > 0, NULL planes or d_info, a
+ * misaligned d_text or d_out, n or out_capacity over 2^31 - 17, d_out == NULL with out_capacity > 0,
+ * at_capacity < 2 with d_at_out, segments without both arrays, text_origin out of range, a short workspace)
+ * return ACM_ERR_ARG before anything is enqueued.
+ * Two launches over max_records cells give every used record its place in the output (64-bit sums), one
+ * more the segment offsets, and the copy kernel runs on a grid over out_capacity: a workgroup owns 16 KiB of
+ * OUTPUT, finds the records that put a byte into it by a search on the records' output ends, and streams
+ * everything between them in 16-byte pieces (csrc/rewrite.hip).  The launch count and the grids depend on
+ * max_records, segments and out_capacity only -- m lives on the device -- and tiles behind m leave at once:
+ * size out_capacity to what is expected, not to the worst case.  The workspace query is monotone in both
+ * arguments and a multiple of 256.
+ * Not provided: rewriting in place; a rewrite that continues across calls (rewrite whole texts);
+ * replacements that refer to the matched bytes; sequence or rule records as input (they carry no start). */
+size_t acm_rewrite_workspace_bytes(size_t max_records, size_t segments);
+int acm_rewrite_async(const acm_dfa *, const void *d_text, size_t n, long text_origin,
+    const int32_t *d_pat_plane, const int32_t *d_off_plane, size_t max_records, void *d_out,
+    size_t out_capacity, int32_t *d_at_out, size_t at_capacity, const int32_t *d_seg_start,
+    size_t segments, int32_t *d_seg_out, int32_t *d_info, void *d_workspace, size_t workspace_bytes,
+    void *stream);
 
 /* Match tallies: counts of the records of any pass, reduced on the device, so a caller who only counts
  * (a classifier, grep -c, "which signatures hit which file") copies back the counts, not the records.
