@@ -40,6 +40,8 @@ POS_FROM_END = 1
 POS_UNBOUNDED = 0x7FFFFFFF
 REPL_FILL = 1
 REPLACEMENT_MAX_LEN = 65535
+EXTRACT_END_INCLUSIVE = 1
+EXTRACT_MAX_GLUE = 16
 SEQ_MAX_PARTS = 32
 GAP_UNBOUNDED = 0x7FFFFFFF
 WILDCARD_MAX_POSITIONS = 4096
@@ -178,6 +180,9 @@ NATIVE_API = {
     "acm_rewrite_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_rewrite_async": (C.c_int, [_vp, _vp, C.c_size_t, C.c_long, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t,
                                     _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "acm_extract_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "acm_extract_async": (C.c_int, [_vp, C.c_size_t, C.c_long, _vp, _vp, C.c_size_t, C.c_uint, C.c_char_p, C.c_int, C.c_int,
+                                    _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp]),
     "acm_tally_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_tally_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t,
                                           _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
@@ -188,6 +193,9 @@ NATIVE_API = {
     "acm_line_select_workspace_bytes": (C.c_size_t, [C.c_size_t]),
     "acm_line_select_async": (C.c_int, [_vp, C.c_size_t, _vp, C.c_long, C.c_long, _vp, C.c_size_t, C.c_int, _vp, _vp, _vp,
                                         C.c_size_t, _vp, C.c_size_t, _vp]),
+    "acm_line_context_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "acm_line_context_async": (C.c_int, [_vp, C.c_size_t, _vp, C.c_long, C.c_long, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                         _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
     "acm_scan_set_mode": (C.c_int, [_vp, C.c_int]),
     "acm_scan_set_graphs": (C.c_int, [_vp, C.c_int]),
     "acm_scan_graph_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

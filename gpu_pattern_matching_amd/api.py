@@ -642,6 +642,27 @@ class _Pipeline:
                              workspace=ws)
         return out, at, seg
 
+    def line_context(self, starts, lcap, linfo, cinfo, before, after, invert, ws):
+        """the context pass over the current planes' offsets and the device-made starts; returns the planes (rel,
+        begin, next, lines) of the groups, lcap + 2 cells each.  ws: (buffer, nbytes)"""
+        rel, beg, nxt, cnt = self.planes(lcap + 2, 4)
+        self.m.line_context_async(starts, lcap, linfo, 0, self.n, self.off, self.max_records, rel, beg, nxt, lcap + 2, cinfo,
+                                  before=before, after=after, invert=invert, lines_out=cnt, seg_start=self.d_st,
+                                  segments=self.nseg, workspace=ws)
+        return rel, beg, nxt, cnt
+
+    def extract(self, begin, end, ranges, info, out_capacity, glue, terminator, end_inclusive=False):
+        """the extract over the text and two planes of ranges; returns (out, at, seg_out): the output bytes, the plane
+        of where every range's bytes begin, and the output in front of every text (None without texts)"""
+        ws = self.workspace(self.m.lib.acm_extract_workspace_bytes, ranges, self.nseg)
+        out = self.alloc(max((out_capacity + 15) // 16 * 16, 16))
+        at = self.alloc((ranges + 2) * 4)
+        seg = self.alloc(self.nseg * 4) if self.nseg else None
+        self.m.extract_async(self.d, self.n, begin, end, ranges, out, out_capacity, info, end_inclusive=end_inclusive,
+                             glue=glue, terminator=terminator, at_out=at, at_capacity=ranges + 2, seg_start=self.d_st,
+                             segments=self.nseg, seg_out=seg, workspace=ws)
+        return out, at, seg
+
     # ---- results
 
     def count(self):
@@ -1372,6 +1393,120 @@ class Matcher:
                             nxt.to_numpy(np.int32, k + 1, stream=self.stream)[1:].astype(np.int64)], axis=1)
             lines = int(h_info[0]) + (1 if n and not h_info[2] else 0)
             return p.copy(), o, ln, sel, lines
+
+    def line_context_async(self, line_start, capacity, info, text_origin, text_end, off_plane, max_records, rel_out,
+                           begin_out, next_out, out_capacity, ctx_info, before=0, after=0, invert=False, lines_out=None,
+                           seg_start=None, segments=0, workspace=None, stream=None):
+        """Enqueue acm_line_context_async: the lines that hold a record of off_plane (invert: that hold none)
+        with before lines in front of and after lines behind each, merged into groups that never cross a start
+        of seg_start: (delimiters in front, first byte, first byte behind, lines) planes in the scan's cell
+        layout, and ctx_info (int32[4]: selected lines, kept lines, groups, 0).  workspace: (ptr, nbytes), or
+        None for a temporary one (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        with self._workspace(workspace, st, self.lib.acm_line_context_workspace_bytes, capacity, segments) as (ws, nb):
+            check(self.lib.acm_line_context_async(
+                _ptr(line_start), capacity, _ptr(info), text_origin, text_end, _ptr(off_plane), max_records,
+                1 if invert else 0, before, after, _ptr(seg_start), segments, _ptr(rel_out), _ptr(begin_out),
+                _ptr(next_out), _ptr(lines_out), out_capacity, _ptr(ctx_info), _ptr(ws), nb, st), "acm_line_context_async")
+
+    def extract_async(self, d_text, n, begin_plane, end_plane, max_ranges, out, out_capacity, info, text_origin=0,
+                      end_inclusive=False, glue=b"", terminator=-1, at_out=None, at_capacity=0, seg_start=None, segments=0,
+                      seg_out=None, workspace=None, stream=None):
+        """Enqueue the extract pass (acm_extract_async): the ranges [begin, end) of the two planes (end_inclusive:
+        [begin, end]) of the device text d_text[0, n), gathered in input order into out (16-byte aligned,
+        out_capacity bytes; None with 0: only the figures), glue (host bytes, at most 16) between ranges of one
+        text and terminator (a byte value, -1: none) behind a range that does not end in it.  info: device
+        int32[8]: used and skipped ranges, the output's length (int64), the text bytes copied (int64), 1 if the
+        output was cut at out_capacity, terminators appended.  at_out: a plane of at_capacity cells: where every
+        used range's bytes begin in the output; seg_start and seg_out, int32[segments] each: the output of the
+        ranges in front of every start.  workspace: (ptr, nbytes), or None for a temporary one that lives until
+        the stream has passed it (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        glue = bytes(glue)
+        term = terminator[0] if isinstance(terminator, (bytes, bytearray)) else int(terminator)
+        with self._workspace(workspace, st, self.lib.acm_extract_workspace_bytes, max_ranges, segments) as (ws, nb):
+            check(self.lib.acm_extract_async(
+                _ptr(d_text), n, text_origin, _ptr(begin_plane), _ptr(end_plane), max_ranges,
+                _lib.EXTRACT_END_INCLUSIVE if end_inclusive else 0, glue if glue else None, len(glue), term, _ptr(out),
+                out_capacity, _ptr(at_out), at_capacity, _ptr(seg_start), segments, _ptr(seg_out), _ptr(info), _ptr(ws),
+                nb, st), "acm_extract_async")
+
+    def scan_extract(self, text=None, texts=None, delimiter=b"\n", before=0, after=0, invert=False, per_line=False,
+                     only_matching=False, glue=None, terminator=None, init_state=0, out_capacity=None):
+        """grep's output on the device: the lines that hold a match (invert: that hold none) with before lines in
+        front of and after lines behind each, packed into one output.  The stages of scan_lines (per_line: the
+        device-made line index goes to the segment pass first), then the context pass (acm_line_context_async) and
+        the extract (acm_extract_async).  text: host bytes; or None with texts: a list of bytes-like objects or a
+        (uint8 array, int32 starts) pair: each text matched alone, context and glue never cross into another
+        text.  glue: the bytes between two groups of one text, by default b"--" + delimiter when before + after >
+        0, else none; terminator: the byte appended to a group that does not end in it, by default the delimiter
+        (-1: none).  only_matching: the stages of scan_select, then the extract over the matches themselves
+        (grep -o's bytes: no glue, the terminator behind every match that does not end in it); ValueError for an
+        automaton with wildcard contexts, whose matches end behind their offsets.
+        Returns (out_bytes, groups, at, info, seg_out): groups int64[k, 4] of (1-based line, first byte, first byte
+        behind, lines) per group (only_matching: (0, start, end, 0) per match); at: where every group's bytes
+        begin in the output; info int32[8] as extract_async leaves it; seg_out: per text, where its part of the
+        output begins (None without texts).  out_capacity: the room for the output in bytes; by default a bound
+        that always fits: every kept line costs its bytes and at most one terminator, every group at most one
+        glue, a text of n bytes has at most n + 1 lines: n + (n + 1) * (1 + len(glue)); for only_matching n + the
+        records.  A convenience call, sized for the worst case as scan_lines is; a caller who knows better uses
+        the *_async calls with its own buffers.  An output that does not fit is ACM_ERR_CAPACITY, never cut
+        silently."""
+        d = delimiter[0] if isinstance(delimiter, (bytes, bytearray)) else int(delimiter)
+        if only_matching and self.wild:
+            raise ValueError("only_matching needs an automaton without wildcard contexts: a match there ends "
+                             "behind its record's offset")
+        if before < 0 or after < 0:
+            raise ValueError("before and after are >= 0")
+        term = d if terminator is None else (terminator[0] if isinstance(terminator, (bytes, bytearray)) else int(terminator))
+        with _Pipeline(self, "Matcher.scan_extract", text, texts) as pl:
+            n, info = pl.n, pl.alloc(32)
+            if only_matching:
+                sel_info = pl.alloc(16)
+                start = self._select_stages(pl, init_state, sel_info, None)
+                pl.max_records = k = pl.count()
+                g = b""
+                cap = out_capacity if out_capacity is not None else min(n + k, 2 ** 31 - 17)
+                begin, end, ranges, incl = start, pl.off, k, True
+                grp = None
+            else:
+                g = (b"--" + bytes([d]) if before + after > 0 else b"") if glue is None else bytes(glue)
+                lcap = n + 1
+                idx_ws = self.lib.acm_line_index_workspace_bytes(n)
+                ctx_ws = self.lib.acm_line_context_workspace_bytes(lcap, pl.nseg)
+                starts, linfo, ws, cinfo = pl.alloc(lcap * 4), pl.alloc(32), pl.alloc(max(idx_ws, ctx_ws)), pl.alloc(16)
+                pl.scan(init_state, _lib.REPORT_STATE if per_line or pl.nseg else _lib.REPORT_HEAD)
+                self.line_index_async(pl.d, n, starts, lcap, linfo, delimiter=d, workspace=(ws.ptr, idx_ws))
+                if pl.nseg:
+                    pl.segment(_lib.REPORT_STATE if per_line else _lib.REPORT_HEAD)
+                if per_line:
+                    pl.segment(_lib.REPORT_HEAD, seg_start=starts, segments=lcap)
+                rel, beg, nxt, cnt = pl.line_context(starts, lcap, linfo, cinfo, before, after, invert, (ws.ptr, ctx_ws))
+                cap = out_capacity if out_capacity is not None else min(n + lcap * (1 + len(g)), 2 ** 31 - 17)
+                begin, end, ranges, incl = beg, nxt, lcap, False
+                grp = (rel, beg, nxt, cnt)
+            out, at, seg = pl.extract(begin, end, ranges, info, cap, g, term, incl)
+            res = info.to_numpy(np.int32, 8, stream=self.stream)
+            m = (int(np.uint32(res[3])) << 32) | int(np.uint32(res[2]))
+            if res[6]:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, pl.where, "the output has %d bytes but the buffer holds %d" % (m, cap))
+            data = out.to_numpy(np.uint8, m, stream=self.stream).tobytes()
+            used = int(res[0])
+            at_cells = at.to_numpy(np.int32, used + 2, stream=self.stream)[1:1 + used].copy()
+            seg_cells = seg.to_numpy(np.int32, pl.nseg, stream=self.stream) if seg is not None else None
+            if grp is None:
+                k = ranges
+                s = begin.to_numpy(np.int32, k + 1, stream=self.stream)[1:].astype(np.int64)
+                e = end.to_numpy(np.int32, k + 1, stream=self.stream)[1:].astype(np.int64) + 1
+                groups = np.stack([np.zeros(k, dtype=np.int64), s, e, np.zeros(k, dtype=np.int64)], axis=1)
+            else:
+                h = linfo.to_numpy(np.int32, 8, stream=self.stream)
+                first = 1 + (int(np.uint32(h[4])) | int(np.uint32(h[5])) << 32)
+                k = int(grp[0].to_numpy(np.int32, 1, stream=self.stream)[0])
+                cols = [x.to_numpy(np.int32, k + 1, stream=self.stream)[1:].astype(np.int64) for x in grp]
+                cols[0] = cols[0] + first
+                groups = np.stack(cols, axis=1) if k else np.zeros((0, 4), dtype=np.int64)
+            return data, groups, at_cells, res, seg_cells
 
     def scan(self, text, init_state=0):
         """Scan host bytes: upload, scan, download."""

@@ -59,7 +59,7 @@ double now_us()
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
 	       "             [-w cpu_threads] [-R max] [-I file] [-P file] [-tvxFMAiSWcno]\n"
-	       "             [-r file -O dir]\n"
+	       "             [-r file -O dir] [-C N[,M] -T dir [-V]]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -161,6 +161,19 @@ double now_us()
 	       "  -O dir         with -r: where the rewritten files go: dir/<name> for every file of a directory or list\n"
 	       "                 given with -f; directories are made as needed.  Two inputs of one name, and an output that\n"
 	       "                 is one of the inputs, are refused\n"
+	       "  -C N[,M]       extract lines (grep -C, extension; binary mode only): every line that holds a record the run\n"
+	       "                 reports, with N lines of context in front of it and M behind it (-C N: N on both sides;\n"
+	       "                 -C 0: the matching lines only).  Overlapping and adjacent contexts merge into one group, the\n"
+	       "                 groups of a file are separated by a line \"--\" when N + M > 0, and context never crosses into\n"
+	       "                 another file.  The lines of every buffer are found, selected and packed on the device; each\n"
+	       "                 input file's lines go to a file under the directory of -T (a file without a selected line\n"
+	       "                 gets an empty one), a last line without a newline gets one.  stdout is what the run without\n"
+	       "                 -C prints.  Context is not continued across buffers: a file that -G cuts is an error that\n"
+	       "                 names it; use a larger -G/-B.  Composes with -A, -i, -S, -W, -I, -P, -o, -c and -n\n"
+	       "                 (extension; needs -T; not with -t, -F, -r, -O, -Q or -K)\n"
+	       "  -V             with -C: the lines that hold NO record are the selected ones (grep -v)\n"
+	       "  -T dir         with -C: where the extracted lines go: dir/<name> for every file of a directory or list given\n"
+	       "                 with -f, named and refused as -O names and refuses them\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -201,6 +214,9 @@ std::vector<std::string> regular_files_in(std::string dir)
 struct Config {
 	std::string pat_path, data_path, loose_path, pos_path, seq_path, rule_path;   // loose_path: -I, pos_path: -P, seq_path: -Q, rule_path: -K
 	std::string repl_path, out_dir;   // -r, -O
+	std::string ext_dir;     // -T
+	int ctx = 0, ctx_before = 0, ctx_after = 0, invert = 0;   // -C N[,M], -V
+	int extract = 0;         // -C and -T: the selected lines and their context are packed on the device and the files written
 	int rewrite = 0;         // -r: the selected matches are replaced on the device and the rewritten files written (only is set too)
 	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0,
 	    words = 0, count = 0, lineno = 0;
@@ -287,6 +303,15 @@ struct Buffer {   // one of the two staging buffers of a worker
 	unsigned char *h_rw_out = nullptr;
 	size_t rw_ws_bytes = 0, rw_cap = 0, rw_max = 0;
 	std::vector<int32_t> rw_starts, rw_files;
+	// -C only: the line starts of this buffer's stream (indexed over d_ex_text when a file in it does not end in a
+	// newline: the stream with one on that file's last byte, so that every file start is a line start), the context
+	// pass's planes and figures, the extract's output, figures and the output in front of every file; pinned twins
+	void *d_ex_lines = nullptr, *d_ex_line_info = nullptr, *d_ex_ws = nullptr, *d_ex_text = nullptr, *d_ex_rel = nullptr,
+	     *d_ex_begin = nullptr, *d_ex_next = nullptr, *d_ex_ctx_info = nullptr, *d_ex_out = nullptr, *d_ex_info = nullptr,
+	     *d_ex_seg = nullptr;
+	int32_t *h_ex_info = nullptr, *h_ex_seg = nullptr;
+	unsigned char *h_ex_out = nullptr;
+	size_t ex_ws_bytes = 0, ex_cap = 0, ex_lcap = 0;
 	long lead_begin = 0;         // -P, -Q: where the text that goes on into this buffer began, in its stream's coordinates (<= 0)
 	bool end_known = false;      // -P: the stream's last text ends with the stream (its file, or with -t its line, is finished)
 	bool last_of_input = false;  // -P: nothing of the worker's input follows this buffer
@@ -339,6 +364,7 @@ struct Worker {
 	int tail_cur = 0;
 	size_t tail_len = 0;
 	int cnt_file = -1;        // -c, -n: file of the last chunk prepared
+	int ex_file = -1;         // -C: file of the last chunk prepared
 	const int32_t *line_prev_info = nullptr;   // -n: d_line_info of the buffer indexed last
 	uint64_t line_carry = 0;  // -n: newlines of the file the last collected buffer ended in, up to that buffer's end
 	void *d_pat_total = nullptr, *d_one_class = nullptr;   // -c: uint64 per pattern, summed over the buffers on the device; a map of every pattern to class 0
@@ -463,6 +489,27 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 		CK(acm_rt_host_alloc((void **)&b.h_rw_info, 64));
 		CK(acm_rt_host_alloc((void **)&b.h_rw_seg, (G + 1) * 4));
 	}
+	if (c.extract) {   // (a line a byte at most: size + 1 lines; a group costs its bytes, a glue and a terminator at most)
+		b.ex_lcap = size + 1;
+		b.ex_cap = std::min(size * 5 / 2 + 4 * G + 64, (size_t)0x7FFFFFE0ul);
+		b.ex_ws_bytes = std::max(std::max(acm_line_index_workspace_bytes(size), acm_line_context_workspace_bytes(b.ex_lcap, G + 1)),
+		    acm_extract_workspace_bytes(b.ex_lcap, G + 1));
+		CK(acm_rt_malloc(&b.d_ex_lines, b.ex_lcap * 4));
+		CK(acm_rt_malloc(&b.d_ex_line_info, 32));
+		CK(acm_rt_malloc(&b.d_ex_ws, b.ex_ws_bytes));
+		CK(acm_rt_malloc(&b.d_ex_text, size + 32));
+		CK(acm_rt_malloc(&b.d_ex_rel, (b.ex_lcap + 2) * 4));
+		CK(acm_rt_malloc(&b.d_ex_begin, (b.ex_lcap + 2) * 4));
+		CK(acm_rt_malloc(&b.d_ex_next, (b.ex_lcap + 2) * 4));
+		CK(acm_rt_malloc(&b.d_ex_ctx_info, 16));
+		CK(acm_rt_malloc(&b.d_ex_out, b.ex_cap + 16));
+		CK(acm_rt_malloc(&b.d_ex_info, 32));
+		CK(acm_rt_malloc(&b.d_rw_start, (G + 1) * 4));
+		CK(acm_rt_malloc(&b.d_ex_seg, (G + 1) * 4));
+		CK(acm_rt_host_alloc((void **)&b.h_ex_out, b.ex_cap + 16));
+		CK(acm_rt_host_alloc((void **)&b.h_ex_info, 64));
+		CK(acm_rt_host_alloc((void **)&b.h_ex_seg, (G + 1) * 4));
+	}
 }
 
 // binary mode: fixed chunks, a short tail chunk per file (databuf.c:326-407)
@@ -550,7 +597,15 @@ void prepare(Worker &w, Buffer &b)
 			w.cnt_file = b.file_ids[i];
 		}
 	}
-	if (c.rewrite) {   // the first chunk, and every chunk of another file than the chunk before it
+	if (c.extract && chunks > 0) {   // context is not continued across buffers: never silently wrong lines
+		if (b.file_ids[0] == w.ex_file) {
+			fprintf(stderr, "ERROR: -C: file '%s' is cut across two buffers and context is not continued across them; raise -G/-B\n",
+			    w.sh->files[(size_t)w.ex_file].c_str());
+			exit(1);
+		}
+		w.ex_file = b.file_ids[chunks - 1];
+	}
+	if (c.rewrite || c.extract) {   // the first chunk, and every chunk of another file than the chunk before it
 		b.rw_starts.clear();
 		b.rw_files.clear();
 		for (int i = 0; i < chunks; i++)
@@ -774,6 +829,38 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		CK(acm_rt_memcpy_d2h(b.h_rw_info, b.d_rw_info, 32, s));
 		CK(acm_rt_memcpy_d2h(b.h_rw_seg, b.d_rw_seg, ns * 4, s));
 	}
+	if (c.extract) {
+		// the lines of this buffer's stream, the ones that hold a record as it is reported (or none: -V) with their
+		// context, grouped inside every file, and the groups' bytes packed.  Only the figures come back here; collect()
+		// fetches the output once it knows its length.  (In front of the remap below: the offsets are still the stream's.)
+		const size_t ns = b.rw_starts.size();
+		const void *lines_of = b.text;
+		bool open_end = false;   // some file in front of another does not end in a newline
+		for (size_t k = 1; k < ns && !open_end; k++) {
+			const size_t i = (size_t)(std::lower_bound(b.starts.begin(), b.starts.begin() + chunks, b.rw_starts[k]) - b.starts.begin());
+			open_end = i > 0 && b.h_sizes[i - 1] > 0 && b.h_data[b.h_indices[i - 1] + b.h_sizes[i - 1] - 1] != '\n';
+		}
+		if (open_end) {   // the index runs over a copy with a newline on such a file's last byte; the extract reads the text
+			CK(acm_rt_memcpy_d2d(b.d_ex_text, b.text, (b.stream_len + 15) & ~(size_t)15, s));
+			for (size_t k = 1; k < ns; k++)
+				if (b.rw_starts[k] > 0)
+					CK(acm_rt_memset((char *)b.d_ex_text + b.rw_starts[k] - 1, '\n', 1, s));
+			lines_of = b.d_ex_text;
+		}
+		CK(acm_rt_memcpy_h2d(b.d_rw_start, b.rw_starts.data(), ns * 4, s));
+		CK(acm_line_index_async(lines_of, b.stream_len, 0, '\n', -1, nullptr, (int32_t *)b.d_ex_lines, b.ex_lcap,
+		    (int32_t *)b.d_ex_line_info, b.d_ex_ws, b.ex_ws_bytes, s));
+		CK(acm_line_context_async((const int32_t *)b.d_ex_lines, b.ex_lcap, (const int32_t *)b.d_ex_line_info, 0, (long)b.stream_len,
+		    off, cap - 2, c.invert, c.ctx_before, c.ctx_after, (const int32_t *)b.d_rw_start, ns, (int32_t *)b.d_ex_rel,
+		    (int32_t *)b.d_ex_begin, (int32_t *)b.d_ex_next, nullptr, b.ex_lcap + 2, (int32_t *)b.d_ex_ctx_info, b.d_ex_ws,
+		    b.ex_ws_bytes, s));
+		const bool sep = c.ctx_before + c.ctx_after > 0;
+		CK(acm_extract_async(b.text, b.stream_len, 0, (const int32_t *)b.d_ex_begin, (const int32_t *)b.d_ex_next, b.ex_lcap, 0,
+		    (const uint8_t *)"--\n", sep ? 3 : 0, '\n', b.d_ex_out, b.ex_cap, nullptr, 0, (const int32_t *)b.d_rw_start, ns,
+		    (int32_t *)b.d_ex_seg, (int32_t *)b.d_ex_info, b.d_ex_ws, b.ex_ws_bytes, s));
+		CK(acm_rt_memcpy_d2h(b.h_ex_info, b.d_ex_info, 32, s));
+		CK(acm_rt_memcpy_d2h(b.h_ex_seg, b.d_ex_seg, ns * 4, s));
+	}
 	if (c.rules) {
 		// the rules: the signatures' records counted per text and the conditions evaluated on the device.  Only the
 		// count comes back here; collect() fetches that many records.  (The bucket planes below keep carrying the
@@ -912,6 +999,37 @@ void collect_rewrite(Worker &w, Buffer &b)
 	}
 }
 
+// -C: the packed lines of the buffer copied back -- their length came with the buffer -- and every file's piece of
+// them appended to that file's output
+void collect_extract(Worker &w, Buffer &b)
+{
+	Shared &sh = *w.sh;
+	const size_t ns = b.rw_starts.size();
+	const int64_t m = (int64_t)(((uint64_t)(uint32_t)b.h_ex_info[3] << 32) | (uint32_t)b.h_ex_info[2]);
+	if (b.h_ex_info[6] || m < 0 || (size_t)m > b.ex_cap) {
+		fprintf(stderr, "ERROR: -C: the lines of a buffer of '%s' have %ld bytes, the output buffer holds %zu; use a smaller -G/-B\n",
+		    ns ? sh.files[(size_t)b.rw_files[0]].c_str() : "?", (long)m, b.ex_cap);
+		exit(1);
+	}
+	if (m > 0) {
+		CK(acm_rt_memcpy_d2h(b.h_ex_out, b.d_ex_out, (size_t)m, w.stream));
+		CK(acm_rt_stream_sync(w.stream));
+	}
+	for (size_t k = 0; k < ns; k++) {
+		const size_t f = (size_t)b.rw_files[k];
+		const int64_t lo = std::min<int64_t>(std::max(b.h_ex_seg[k], 0), m);
+		const int64_t hi = k + 1 < ns ? std::min<int64_t>(std::max<int64_t>(b.h_ex_seg[k + 1], lo), m) : m;
+		if (!sh.out_begun[f])
+			make_parents(sh.out_paths[f]);
+		FILE *fp = fopen(sh.out_paths[f].c_str(), sh.out_begun[f] ? "ab" : "wb");
+		if (!fp || fwrite(b.h_ex_out + lo, 1, (size_t)(hi - lo), fp) != (size_t)(hi - lo) || fclose(fp) != 0) {
+			fprintf(stderr, "ERROR: -T: cannot write '%s': %s\n", sh.out_paths[f].c_str(), strerror(errno));
+			exit(1);
+		}
+		sh.out_begun[f] = 1;
+	}
+}
+
 // wait for the buffer, walk the bucket planes (databuf.c:747-782), print -v lines
 void collect(Worker &w, Buffer &b)
 {
@@ -935,6 +1053,8 @@ void collect(Worker &w, Buffer &b)
 		w.sel_dropped += (uint64_t)b.h_sel_info[1];
 	if (c.rewrite)
 		collect_rewrite(w, b);
+	if (c.extract)
+		collect_extract(w, b);
 	if (c.count && !w.sh->pat_iid.empty()) {
 		if (b.cnt_starts.empty()) {   // the whole buffer goes on with the file in front of it
 			if (b.cnt_prev_file >= 0)
@@ -1175,7 +1295,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xor:O:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o, r, O
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xor:O:C:VT:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o, r, O, C, V, T
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -1216,6 +1336,20 @@ int main(int argc, char **argv)
 		case 'r': c.repl_path = optarg; break;
 		case 'O': c.out_dir = optarg; break;
 		case 'K': c.rule_path = optarg; break;
+		case 'C': {   // N or N,M: decimal digits only
+			const std::string v = optarg;
+			const size_t comma = v.find(',');
+			const std::string a = v.substr(0, comma), z = comma == std::string::npos ? a : v.substr(comma + 1);
+			auto digits = [](const std::string &x) { return !x.empty() && x.size() <= 9 && x.find_first_not_of("0123456789") == std::string::npos; };
+			c.ctx = digits(a) && digits(z) ? 1 : -1;
+			if (c.ctx == 1) {
+				c.ctx_before = atoi(a.c_str());
+				c.ctx_after = atoi(z.c_str());
+			}
+			break;
+		}
+		case 'V': c.invert = 1; break;
+		case 'T': c.ext_dir = optarg; break;
 		default: usage();
 		}
 	}
@@ -1319,6 +1453,29 @@ int main(int argc, char **argv)
 		printf("ERROR: -o cannot be combined with -A, -c, -n, -Q, -K, -E or -F: the records of -o are the selected matches\n");
 		err++;
 	}
+	if (c.ctx < 0) {
+		printf("ERROR: -C takes N or N,M: the lines in front and behind, both >= 0\n");
+		err++;
+	}
+	if (c.ctx && c.ext_dir.empty()) {
+		printf("ERROR: -C needs -T: the directory the extracted lines go to\n");
+		err++;
+	}
+	if (c.invert && (!c.ctx || c.ext_dir.empty())) {
+		printf("ERROR: -V needs -C and -T: it inverts the selection of the lines that are extracted\n");
+		err++;
+	}
+	if (!c.ctx && !c.ext_dir.empty()) {
+		printf("ERROR: -T needs -C: the lines of context around a selected line (-C 0: none)\n");
+		err++;
+	}
+	if ((c.ctx || c.invert || !c.ext_dir.empty()) &&
+	    (c.text_mode || c.follow || !c.repl_path.empty() || !c.out_dir.empty() || c.seq)) {   // the lines of whole files, around pattern records
+		printf("ERROR: -C, -V and -T cannot be combined with -t, -F, -r, -O, -Q or -K: the lines of whole files are extracted, "
+		       "around the records of patterns\n");
+		err++;
+	}
+	c.extract = c.ctx == 1 && !c.ext_dir.empty();
 	if (err)
 		usage();
 	if (c.only)   // the select pass takes every pattern of every record: the planes -A would have printed
@@ -1417,10 +1574,11 @@ int main(int argc, char **argv)
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}
-	if (c.rewrite) {   // a file of a directory or a list goes to <-O>/<its name>
+	if (c.rewrite || c.extract) {   // a file of a directory or a list goes to <-O>/<its name> (-C: <-T>/<its name>)
+		const char *opt_name = c.rewrite ? "-O" : "-T";
 		for (const std::string &f : sh.files) {
 			const size_t slash = f.rfind('/');
-			sh.out_paths.push_back(c.out_dir + "/" + (slash == std::string::npos ? f : f.substr(slash + 1)));
+			sh.out_paths.push_back((c.rewrite ? c.out_dir : c.ext_dir) + "/" + (slash == std::string::npos ? f : f.substr(slash + 1)));
 		}
 		sh.out_begun.assign(sh.files.size(), 0);
 		// two inputs of one name (a list over several directories) would share an output, and an output that is an
@@ -1430,7 +1588,7 @@ int main(int argc, char **argv)
 		for (size_t f = 0; f < sh.files.size(); f++) {
 			auto at = seen.emplace(sh.out_paths[f], f);
 			if (!at.second) {
-				fprintf(stderr, "ERROR: -O: '%s' and '%s' would both be written to '%s'\n", sh.files[at.first->second].c_str(),
+				fprintf(stderr, "ERROR: %s: '%s' and '%s' would both be written to '%s'\n", opt_name, sh.files[at.first->second].c_str(),
 				    sh.files[f].c_str(), sh.out_paths[f].c_str());
 				return 1;
 			}
@@ -1441,7 +1599,8 @@ int main(int argc, char **argv)
 		for (size_t f = 0; f < sh.files.size(); f++) {
 			struct stat st;
 			if (stat(sh.out_paths[f].c_str(), &st) == 0 && inputs.count({ st.st_dev, st.st_ino })) {
-				fprintf(stderr, "ERROR: -O: the output '%s' is an input file; give -O another directory\n", sh.out_paths[f].c_str());
+				fprintf(stderr, "ERROR: %s: the output '%s' is an input file; give %s another directory\n", opt_name, sh.out_paths[f].c_str(),
+				    opt_name);
 				return 1;
 			}
 		}
@@ -1498,7 +1657,7 @@ int main(int argc, char **argv)
 		rounds += w.rounds;
 	}
 	const double secs = (now_us() - t0) / 1e6;
-	for (size_t f = 0; c.rewrite && f < sh.files.size(); f++)
+	for (size_t f = 0; (c.rewrite || c.extract) && f < sh.files.size(); f++)
 		if (!sh.out_begun[f]) {   // a file of no bytes: no buffer held a piece of it
 			make_parents(sh.out_paths[f]);
 			if (FILE *fp = fopen(sh.out_paths[f].c_str(), "wb"))

@@ -14,7 +14,8 @@
 // acm_line_number_async: a binary search per offset.  acm_line_select_async: a bit per line in the
 // workspace, zeroed, set by one launch over the records (atomic or, skipped where the bit is already
 // set), then the two-launch ordered write of record_pass.h over the bits.  Cost per record and per line,
-// never per text byte.
+// never per text byte.  acm_line_context_async: the same bits, a prefix of their counts, and per line a
+// window clamped to its text; heads and tails of the runs of kept lines, written in order (see "context").
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -267,6 +268,256 @@ __global__ __launch_bounds__(kThreads) void k_line_select(SelectArgs g)
 	}
 }
 
+// ------------------------------------------------------------------ context
+
+// The select pass's lines and flags (k_line_mark), then per line: kept iff a selected line of its text lies in
+// [j - after, j + before].  Launches over the fixed grid, a block owning a run of flag words:
+//   k_ctx_count   the flags become the SELECTED bits (inverted if asked, cut at the last line); per block their count
+//   k_ctx_rank    rank[w] = the selected lines in front of word w
+//   k_ctx_keep    a lane per line: the line's text [lo, hi) in lines by two searches (no segments: every line), the
+//                 window clamped to it, kept iff the rank difference over the window is > 0; head = kept and (first
+//                 line of its text or the line in front not kept), tail likewise: a bit per line each, per block
+//                 the kept lines, heads and tails
+//   k_ctx_heads   the ordered write over the head bits: rel, begin, and the head's line for the next launch
+//   k_ctx_tails   the same over the tail bits (group k ends at tail k): next, lines
+// Nothing depends on before or after but the two clamps.
+struct CtxArgs {
+	SelectArgs s;
+	int64_t before, after;
+	const int32_t *seg_start;
+	uint32_t segments;
+	int32_t *lines_out, *ctx_info;
+	uint32_t *rank, *head, *tail;             // per flag word
+	int32_t *blk_kept, *blk_head, *blk_tail;  // per block (s.block_counts: the selected lines)
+	int32_t *head_line;                       // [capacity + 1] the first line of group k
+};
+
+__device__ __forceinline__ uint32_t lower_bound_i32(const int32_t *a, uint32_t n, int64_t key)
+{
+	uint32_t lo = 0, hi = n;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if ((int64_t)a[mid] < key)
+			lo = mid + 1;
+		else
+			hi = mid;
+	}
+	return lo;
+}
+
+__device__ __forceinline__ uint32_t selected_word(const SelectArgs &g, uint32_t w, uint32_t lines)
+{
+	uint32_t bits = g.invert ? ~g.flags[w] : g.flags[w];
+	const uint32_t left = lines - w * 32;   // >= 1
+	if (left < 32)
+		bits &= (1u << left) - 1;
+	return bits;
+}
+
+__global__ __launch_bounds__(kThreads) void k_ctx_count(CtxArgs c)
+{
+	__shared__ uint32_t red[kWaves];
+	uint32_t L, lead;
+	const uint32_t lines = lines_of(c.s, L, lead);
+	const Words sh = words_of((lines + 31) / 32);
+	uint32_t count = 0;
+	for (uint32_t w = sh.w_begin + threadIdx.x; w < sh.w_end; w += kTileWords) {
+		const uint32_t bits = selected_word(c.s, w, lines);
+		c.s.flags[w] = bits;
+		count += (uint32_t)__popc(bits);
+	}
+	count = block_sum(count, red);
+	if (threadIdx.x == 0)
+		c.s.block_counts[blockIdx.x] = (int32_t)count;
+}
+
+__global__ __launch_bounds__(kThreads) void k_ctx_rank(CtxArgs c)
+{
+	__shared__ uint32_t red[2 * kWaves];
+	uint32_t L, lead;
+	const uint32_t lines = lines_of(c.s, L, lead);
+	const Words sh = words_of((lines + 31) / 32);
+	uint32_t total;
+	uint32_t base = blocks_before(c.s.block_counts, red, total);
+	for (uint32_t w0 = sh.w_begin; w0 < sh.w_end; w0 += kTileWords) {
+		const uint32_t w = w0 + threadIdx.x;
+		const uint32_t cnt = w < sh.w_end ? (uint32_t)__popc(c.s.flags[w]) : 0;
+		uint32_t tile_total;
+		const uint32_t r = base + block_prefix(cnt, red, tile_total);
+		if (w < sh.w_end)
+			c.rank[w] = r;
+		base += tile_total;
+	}
+	if (blockIdx.x == 0 && threadIdx.x == 0)
+		c.ctx_info[0] = (int32_t)total;
+}
+
+// selected lines in front of line x <= lines
+__device__ __forceinline__ uint32_t selected_before(const CtxArgs &c, uint32_t x, uint32_t lines)
+{
+	if (x >= lines) {   // behind the last word's bits
+		if (lines == 0)
+			return 0;
+		const uint32_t w = (lines - 1) >> 5;
+		return c.rank[w] + (uint32_t)__popc(c.s.flags[w]);
+	}
+	const uint32_t w = x >> 5, b = x & 31;
+	return c.rank[w] + (uint32_t)__popc(c.s.flags[w] & ((1u << b) - 1));
+}
+
+struct LineCtx {
+	bool kept;
+	uint32_t lo, hi;   // the lines of the line's text: [lo, hi)
+};
+
+// line j < lines
+__device__ __forceinline__ LineCtx line_ctx(const CtxArgs &c, uint32_t j, uint32_t lines, uint32_t L, uint32_t lead)
+{
+	LineCtx r{ false, 0, lines };
+	if (c.segments) {
+		const int64_t first = j < lead ? c.s.origin : (int64_t)c.s.line_start[j - lead];
+		const uint32_t t = upper_bound_i32(c.seg_start, c.segments, first);
+		if (t > 0) {
+			const int64_t x = c.seg_start[t - 1];
+			r.lo = lead && c.s.origin >= x ? 0 : lead + lower_bound_i32(c.s.line_start, L, x);
+		}
+		if (t < c.segments)
+			r.hi = lead + lower_bound_i32(c.s.line_start, L, (int64_t)c.seg_start[t]);
+	}
+	const int64_t a = max((int64_t)r.lo, (int64_t)j - c.after), b = min((int64_t)r.hi - 1, (int64_t)j + c.before);
+	r.kept = selected_before(c, (uint32_t)b + 1, lines) > selected_before(c, (uint32_t)a, lines);
+	return r;
+}
+
+__global__ __launch_bounds__(kThreads) void k_ctx_keep(CtxArgs c)
+{
+	__shared__ uint32_t red[kWaves];
+	uint32_t L, lead;
+	const uint32_t lines = lines_of(c.s, L, lead);
+	const uint32_t words = (lines + 31) / 32;
+	const Words sh = words_of(words);
+	const uint32_t lane = lane_id();
+	uint32_t kept = 0, heads = 0, tails = 0;   // (counted by lane 0 of every wave)
+	const uint64_t j_end = min((uint64_t)sh.w_end * 32, (uint64_t)lines);
+	for (uint64_t j0 = (uint64_t)sh.w_begin * 32; j0 < j_end; j0 += kThreads) {
+		const uint64_t jj = j0 + threadIdx.x;
+		const bool valid = jj < j_end;
+		const uint32_t j = (uint32_t)jj;
+		LineCtx x{ false, 0, 0 };
+		if (valid)
+			x = line_ctx(c, j, lines, L, lead);
+		// the neighbours: the lanes beside this one, but for a wave's two ends
+		bool prev = __shfl_up((int)x.kept, 1, 64) != 0, next = __shfl_down((int)x.kept, 1, 64) != 0;
+		if (lane == 0 && x.kept && j > x.lo)
+			prev = line_ctx(c, j - 1, lines, L, lead).kept;
+		if (lane == 63 && x.kept && j + 1 < x.hi)
+			next = line_ctx(c, j + 1, lines, L, lead).kept;
+		const bool head = x.kept && (j == x.lo || !prev), tail = x.kept && (j + 1 == x.hi || !next);
+		const uint64_t kb = __ballot(x.kept), hb = __ballot(head), tb = __ballot(tail);
+		const uint32_t w = (uint32_t)((j0 + (threadIdx.x & ~63u)) >> 5);   // the wave's first word
+		if (lane == 0) {
+			kept += (uint32_t)__popcll(kb);
+			heads += (uint32_t)__popcll(hb);
+			tails += (uint32_t)__popcll(tb);
+			if (w < sh.w_end) {
+				c.head[w] = (uint32_t)hb;
+				c.tail[w] = (uint32_t)tb;
+			}
+			if (w + 1 < sh.w_end) {
+				c.head[w + 1] = (uint32_t)(hb >> 32);
+				c.tail[w + 1] = (uint32_t)(tb >> 32);
+			}
+		}
+	}
+	kept = block_sum(kept, red);
+	heads = block_sum(heads, red);
+	tails = block_sum(tails, red);
+	if (threadIdx.x == 0) {
+		c.blk_kept[blockIdx.x] = (int32_t)kept;
+		c.blk_head[blockIdx.x] = (int32_t)heads;
+		c.blk_tail[blockIdx.x] = (int32_t)tails;
+	}
+}
+
+template <bool TAILS>
+__global__ __launch_bounds__(kThreads) void k_ctx_write(CtxArgs c)
+{
+	__shared__ uint32_t red[2 * kWaves];
+	const SelectArgs &g = c.s;
+	uint32_t L, lead;
+	const uint32_t lines = lines_of(g, L, lead);
+	const Words sh = words_of((lines + 31) / 32);
+	uint32_t total;
+	uint32_t base = blocks_before(TAILS ? c.blk_tail : c.blk_head, red, total);
+	if (!TAILS) {
+		uint32_t kept_all;
+		blocks_before(c.blk_kept, red, kept_all);
+		if (blockIdx.x == 0 && threadIdx.x == 0) {
+			write_ends(g.rel_out, g.cap, total, 0);
+			write_ends(g.begin_out, g.cap, total, 0);
+			c.ctx_info[1] = (int32_t)kept_all;
+			c.ctx_info[2] = (int32_t)total;
+			c.ctx_info[3] = 0;
+		}
+	} else if (blockIdx.x == 0 && threadIdx.x == 0) {
+		write_ends(g.next_out, g.cap, total, 0);
+		if (c.lines_out)
+			write_ends(c.lines_out, g.cap, total, 0);
+	}
+	const uint32_t *plane = TAILS ? c.tail : c.head;
+	for (uint32_t w0 = sh.w_begin; w0 < sh.w_end; w0 += kTileWords) {
+		const uint32_t w = w0 + threadIdx.x;
+		uint32_t bits = w < sh.w_end ? plane[w] : 0;
+		uint32_t tile_total;
+		uint32_t d = base + block_prefix((uint32_t)__popc(bits), red, tile_total);
+		while (bits) {
+			const uint32_t line = w * 32 + (uint32_t)__ffs((int)bits) - 1;
+			bits &= bits - 1;
+			const int64_t k = (int64_t)line - lead;
+			if (!TAILS) {
+				c.head_line[d] = (int32_t)line;   // (d < lines <= capacity + 1)
+				if (d + 2 < g.cap) {
+					g.rel_out[1 + d] = (int32_t)line;
+					g.begin_out[1 + d] = k < 0 ? (int32_t)g.origin : g.line_start[k];
+				}
+			} else if (d + 2 < g.cap) {
+				g.next_out[1 + d] = k + 1 < (int64_t)L ? g.line_start[k + 1] : (int32_t)g.end;
+				if (c.lines_out)
+					c.lines_out[1 + d] = (int32_t)(line - (uint32_t)c.head_line[d] + 1);
+			}
+			d++;
+		}
+		base += tile_total;
+	}
+}
+
+size_t flag_bytes(size_t capacity) { return round256((capacity / 32 + 1) * 4); }
+
+struct CtxLayout {
+	size_t flags, rank, head, tail, blk_kept, blk_head, blk_tail, head_line, total;
+};
+
+CtxLayout ctx_layout(size_t capacity)
+{
+	CtxLayout l;
+	size_t at = kCountBytes;   // the selected lines per block, as in the select pass
+	auto take = [&](size_t bytes) {
+		const size_t here = at;
+		at += round256(bytes);
+		return here;
+	};
+	l.flags = take(flag_bytes(capacity));
+	l.rank = take(flag_bytes(capacity));
+	l.head = take(flag_bytes(capacity));
+	l.tail = take(flag_bytes(capacity));
+	l.blk_kept = take(kCountBytes);
+	l.blk_head = take(kCountBytes);
+	l.blk_tail = take(kCountBytes);
+	l.head_line = take((capacity + 1) * 4);
+	l.total = at;
+	return l;
+}
+
 size_t mask_words(size_t n) { return ((n + 15) / 16 + 3) / 4; }
 
 // blocks of the fixed grid: four per CU of the current device, kMaxBlocks at most
@@ -388,6 +639,75 @@ extern "C" int acm_line_select_async(const int32_t *d_line_start, size_t capacit
 	hipLaunchKernelGGL(k_line_select<false>, dim3(blocks), dim3(kThreads), 0, s, g);
 	ACM_HIP_TRY(hipGetLastError());
 	hipLaunchKernelGGL(k_line_select<true>, dim3(blocks), dim3(kThreads), 0, s, g);
+	ACM_HIP_TRY(hipGetLastError());
+	return ACM_OK;
+}
+
+extern "C" size_t acm_line_context_workspace_bytes(size_t capacity, size_t segments)
+{
+	(void)segments;   // (the starts are searched where they lie)
+	return ctx_layout(capacity).total;
+}
+
+extern "C" int acm_line_context_async(const int32_t *d_line_start, size_t capacity, const int32_t *d_info, long text_origin,
+    long text_end, const int32_t *d_off_plane, size_t max_records, int invert, int before, int after, const int32_t *d_seg_start,
+    size_t segments, int32_t *d_rel_out, int32_t *d_begin_out, int32_t *d_next_out, int32_t *d_lines_out, size_t out_capacity,
+    int32_t *d_ctx_info, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+	if (!d_line_start || !d_info || !d_off_plane || !d_rel_out || !d_begin_out || !d_next_out || !d_ctx_info || capacity == 0 ||
+	    capacity > 0xFFFFFFFEul || out_capacity < 2 || max_records > 0x7FFFFFFEul || text_end < text_origin || before < 0 ||
+	    after < 0 || segments > 0x7FFFFFFFul || (segments > 0) != (d_seg_start != nullptr))
+		return acm::fail(ACM_ERR_ARG, "acm_line_context_async: bad arguments");
+	const CtxLayout l = ctx_layout(capacity);
+	if (!d_workspace || workspace_bytes < l.total)
+		return acm::fail(ACM_ERR_ARG, "acm_line_context_async: workspace %zu B < required %zu B", workspace_bytes, l.total);
+	hipStream_t s = (hipStream_t)stream;
+	uint32_t blocks = 0;
+	if (int rc = fixed_grid(&blocks))
+		return rc;
+	char *ws = (char *)d_workspace;
+	CtxArgs c;
+	SelectArgs &g = c.s;
+	g.line_start = d_line_start;
+	g.capacity = (uint32_t)capacity;
+	g.info = d_info;
+	g.origin = (int64_t)text_origin;
+	g.end = (int64_t)text_end;
+	g.off_plane = d_off_plane;
+	g.max_records = (uint32_t)max_records;
+	g.invert = invert ? 1 : 0;
+	g.rel_out = d_rel_out;
+	g.begin_out = d_begin_out;
+	g.next_out = d_next_out;
+	g.cap = clamp_cap(out_capacity);
+	g.block_counts = (int32_t *)ws;
+	g.flags = (uint32_t *)(ws + l.flags);
+	c.before = before;
+	c.after = after;
+	c.seg_start = d_seg_start;
+	c.segments = (uint32_t)segments;
+	c.lines_out = d_lines_out;
+	c.ctx_info = d_ctx_info;
+	c.rank = (uint32_t *)(ws + l.rank);
+	c.head = (uint32_t *)(ws + l.head);
+	c.tail = (uint32_t *)(ws + l.tail);
+	c.blk_kept = (int32_t *)(ws + l.blk_kept);
+	c.blk_head = (int32_t *)(ws + l.blk_head);
+	c.blk_tail = (int32_t *)(ws + l.blk_tail);
+	c.head_line = (int32_t *)(ws + l.head_line);
+	ACM_HIP_TRY(hipMemsetAsync(g.flags, 0, (capacity / 32 + 1) * 4, s));
+	const uint32_t mark_blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>(blocks, (max_records + kThreads - 1) / kThreads));
+	hipLaunchKernelGGL(k_line_mark, dim3(mark_blocks), dim3(kThreads), 0, s, g);
+	ACM_HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_ctx_count, dim3(blocks), dim3(kThreads), 0, s, c);
+	ACM_HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_ctx_rank, dim3(blocks), dim3(kThreads), 0, s, c);
+	ACM_HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_ctx_keep, dim3(blocks), dim3(kThreads), 0, s, c);
+	ACM_HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_ctx_write<false>, dim3(blocks), dim3(kThreads), 0, s, c);
+	ACM_HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_ctx_write<true>, dim3(blocks), dim3(kThreads), 0, s, c);
 	ACM_HIP_TRY(hipGetLastError());
 	return ACM_OK;
 }

@@ -984,6 +984,64 @@ int acm_rewrite_async(const acm_dfa *, const void *d_text, size_t n, long text_o
     size_t segments, int32_t *d_seg_out, int32_t *d_info, void *d_workspace, size_t workspace_bytes,
     void *stream);
 
+/* Extraction: ranges of a device text gathered into one packed output -- the matching lines, the lines
+ * with their context, the matches themselves (grep -o), snippets for a report -- without copying the text
+ * and the planes back to slice on the host.  The complement of acm_rewrite_async, which keeps everything.
+ * Text: acm_rewrite_async's contract (16-byte aligned, readable up to n rounded up to 16, n <= 2^31 - 17,
+ * d_text[i] the byte at offset text_origin + i, text_end = text_origin + n, text_origin in int32).
+ * Ranges: both planes in the scan's cell layout; min(max(begin[0], 0), max_ranges) ranges are looked at.
+ * Range i is [b, e) with b = begin[1 + i] and e = end[1 + i], or with ACM_EXTRACT_END_INCLUSIVE
+ * e = end[1 + i] + 1: the form of the select pass's (d_start_out, d_off_out) for patterns without a post
+ * context (int64).  The planes may be acm_line_context_async's (begin, next), acm_line_select_async's, or
+ * the select pass's.  A range is USED iff text_origin <= b < e <= text_end; any other range, garbage
+ * cells included, is skipped and counted.  Ranges need not ascend or be disjoint: this is a gather, and
+ * the output follows input order.
+ * Output, for the used ranges in input order:
+ *   glue         in front of every used range except the first and except one whose text id differs from
+ *                the previous used range's.  The text id is the number of cells of d_seg_start that are
+ *                <= b (0 without segments): glue never joins two texts.  glue is HOST memory of glue_len
+ *                bytes, 0..ACM_EXTRACT_MAX_GLUE, passed to the kernels by value (no upload)
+ *   the bytes    of the range
+ *   terminator   (0..255; -1: none) iff the range's last byte is not that byte: grep supplies a missing
+ *                final newline this way
+ * m (int64) is the output's length.  d_out receives the first min(m, out_capacity) bytes; no byte at or
+ * behind that point is written.  d_out == NULL with out_capacity == 0 is legal: the figures only.  d_out
+ * is 16-byte aligned, out_capacity <= 2^31 - 17, and it overlaps neither the text nor the planes.
+ *   d_at_out     may be NULL, else the scan's cell layout and overflow contract over at_capacity cells:
+ *                [0] the used ranges, then per used range the output offset where its bytes begin (behind
+ *                its glue; saturated to INT32_MAX), then a trailer cell 0
+ *   d_seg_out    with d_seg_start, both or neither: int32[segments]; cell k = the sum, over the used
+ *                ranges with b < start[k], of everything those ranges put into the output (glue, bytes,
+ *                terminator), saturated to int32.  For ascending ranges: where text k's part begins
+ *   d_info       int32[8], required, written whole: [0] used ranges, [1] skipped ranges, [2..3] m as (lo,
+ *                hi), [4..5] the text bytes copied (lo, hi), [6] 1 iff m > out_capacity and d_out is not
+ *                NULL (the output was cut: never silently), [7] the terminators appended (saturated)
+ * Every run gives the same bytes (no order is decided by atomics).  Whatever the planes hold, no read
+ * leaves the inputs and no write leaves the outputs and the workspace.  Stream-ordered, no host sync, no
+ * allocation, no host read of device data; argument errors (acm_rewrite_async's list; unknown flag bits,
+ * glue_len outside 0..ACM_EXTRACT_MAX_GLUE, a NULL glue with glue_len > 0, a terminator outside -1..255)
+ * return ACM_ERR_ARG before anything is enqueued.
+ * Two launches over max_ranges cells give every used range its end in the output (64-bit sums; the "used
+ * range in front" that decides the glue is a prefix maximum), two more the segment sums, and the copy
+ * kernel runs on a grid over out_capacity: a workgroup owns 16 KiB of OUTPUT, finds its ranges by a search
+ * on the output ends, stages the tile in LDS -- a 16-byte aligned source piece per lane, shifted in
+ * registers to its place -- and streams it out in aligned 16-byte stores; a tile inside one range's
+ * bytes is copied straight (csrc/extract.hip).  The launch count and the grids depend on max_ranges,
+ * segments and out_capacity only -- m lives on the device -- and tiles behind min(m, out_capacity) leave
+ * at once.  The workspace query is monotone in both arguments and a multiple of 256.
+ * Not provided: extraction continued across calls (a range is used whole or not at all: give whole texts);
+ * lines cut at a text start that is not a line start; per-line prefixes (file:line:) in the output;
+ * wildcard post contexts in the END_INCLUSIVE (-o) form: such a match ends post bytes behind the offset. */
+enum { ACM_EXTRACT_END_INCLUSIVE = 1 };
+#define ACM_EXTRACT_MAX_GLUE 16
+size_t acm_extract_workspace_bytes(size_t max_ranges, size_t segments);
+int acm_extract_async(const void *d_text, size_t n, long text_origin,
+    const int32_t *d_begin_plane, const int32_t *d_end_plane, size_t max_ranges, unsigned flags,
+    const uint8_t *glue, int glue_len, int terminator,
+    void *d_out, size_t out_capacity, int32_t *d_at_out, size_t at_capacity,
+    const int32_t *d_seg_start, size_t segments, int32_t *d_seg_out,
+    int32_t *d_info, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* Match tallies: counts of the records of any pass, reduced on the device, so a caller who only counts
  * (a classifier, grep -c, "which signatures hit which file") copies back the counts, not the records.
  * Input: planes in the scan's cell layout; at most min([0], max_records) records are looked at, as in
@@ -1081,6 +1139,42 @@ int acm_line_select_async(const int32_t *d_line_start, size_t capacity, const in
     long text_origin, long text_end, const int32_t *d_off_plane, size_t max_records, int invert,
     int32_t *d_rel_out, int32_t *d_begin_out, int32_t *d_next_out, size_t out_capacity,
     void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* The selected lines with the lines around them, as groups: grep -A/-B/-C.  The lines of the piece and
+ * which of them are SELECTED are exactly acm_line_select_async's: the lead line, the starts, invert, a
+ * record belonging to the line that holds its offset.
+ * Text id: t(j) of line j is the number of cells of d_seg_start[0, segments) that are <= the line's first
+ * byte (0 when segments == 0; d_seg_start non-decreasing, as in the tally pass; starts at or beyond
+ * text_end are allowed and count for no line).  A line that has a start in its interior belongs to the
+ * text it begins in: that happens when a text does not end in the delimiter.
+ * KEPT: line j is kept iff some selected line i has t(i) == t(j) and j - after <= i <= j + before (int64:
+ * before or after = INT32_MAX means "to the ends of the text"; negative values are ACM_ERR_ARG).
+ * GROUP: a maximal run of consecutive kept lines with equal text id.  This is grep's rule: overlapping or
+ * adjacent contexts merge, and context never crosses into another text.
+ * Output, the scan's cell layout and overflow contract in every plane ([0] = full count of groups,
+ * entries ascending, trailer cell at min(count + 1, out_capacity - 1) = 0), per group:
+ *   d_rel_out     delimiters in front of the group's first line
+ *   d_begin_out   the group's first byte;  d_next_out: the first byte behind it
+ *   d_lines_out   the group's lines; may be NULL (not wanted)
+ *   d_ctx_info    int32[4], required, written whole: selected lines, kept lines, groups, 0
+ * With before == after == 0 and no segments the groups are the runs of adjacent selected lines: the same
+ * bytes as acm_line_select_async's entries, which stay one per line.
+ * Stream-ordered, no host sync, no allocation; argument errors (a NULL plane but d_lines_out, a NULL
+ * d_ctx_info, capacity == 0, out_capacity < 2, text_end < text_origin, a negative before or after,
+ * segments without d_seg_start or the reverse, a short workspace) return ACM_ERR_ARG before anything is
+ * enqueued.  Exact when info[0] <= capacity.  Six launches behind the zero-fill of the flags, on grids
+ * that depend on capacity and max_records only -- never on before, after or the data: a prefix of the
+ * selected bits makes "a selected line within the window" one subtraction, and two searches clamp the
+ * window to the line's text (csrc/lines.hip).  Cost per record and per line, never per text byte.  The
+ * workspace query is monotone in both arguments and a multiple of 256.
+ * Not provided: context continued across calls (a group that would reach into the next piece ends at
+ * text_end: give whole texts); lines cut at a text start that is not a line start (see the text id). */
+size_t acm_line_context_workspace_bytes(size_t capacity, size_t segments);
+int acm_line_context_async(const int32_t *d_line_start, size_t capacity, const int32_t *d_info,
+    long text_origin, long text_end, const int32_t *d_off_plane, size_t max_records, int invert,
+    int before, int after, const int32_t *d_seg_start, size_t segments,
+    int32_t *d_rel_out, int32_t *d_begin_out, int32_t *d_next_out, int32_t *d_lines_out,
+    size_t out_capacity, int32_t *d_ctx_info, void *d_workspace, size_t workspace_bytes, void *stream);
 
 int acm_scan_batch_async(const acm_dfa *, const acm_scan_batch *);
 
