@@ -42,6 +42,9 @@ REPL_FILL = 1
 REPLACEMENT_MAX_LEN = 65535
 EXTRACT_END_INCLUSIVE = 1
 EXTRACT_MAX_GLUE = 16
+FORMAT_NAME, FORMAT_NUMBER, FORMAT_OFFSET = 2, 4, 8
+FORMAT_MAX_NAME = 4096
+LINE_SELECTED, LINE_GROUP_HEAD = 1, 2
 SEQ_MAX_PARTS = 32
 GAP_UNBOUNDED = 0x7FFFFFFF
 WILDCARD_MAX_POSITIONS = 4096
@@ -183,6 +186,10 @@ NATIVE_API = {
     "acm_extract_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_extract_async": (C.c_int, [_vp, C.c_size_t, C.c_long, _vp, _vp, C.c_size_t, C.c_uint, C.c_char_p, C.c_int, C.c_int,
                                     _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "acm_format_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "acm_format_async": (C.c_int, [_vp, C.c_size_t, C.c_long, _vp, _vp, C.c_size_t, C.c_uint, _vp, _vp, _vp, C.c_long, C.c_long,
+                                   C.c_int, C.c_int, _vp, _vp, C.c_size_t, C.c_char_p, C.c_int, C.c_int, _vp, C.c_size_t, _vp,
+                                   C.c_size_t, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp]),
     "acm_tally_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_tally_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t,
                                           _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
@@ -196,6 +203,10 @@ NATIVE_API = {
     "acm_line_context_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
     "acm_line_context_async": (C.c_int, [_vp, C.c_size_t, _vp, C.c_long, C.c_long, _vp, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                          _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    "acm_line_context_lines_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "acm_line_context_lines_async": (C.c_int, [_vp, C.c_size_t, _vp, C.c_long, C.c_long, _vp, C.c_size_t, C.c_int, C.c_int,
+                                               C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t,
+                                               _vp]),
     "acm_scan_set_mode": (C.c_int, [_vp, C.c_int]),
     "acm_scan_set_graphs": (C.c_int, [_vp, C.c_int]),
     "acm_scan_graph_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -663,6 +663,28 @@ class _Pipeline:
                              segments=self.nseg, seg_out=seg, workspace=ws)
         return out, at, seg
 
+    def line_context_lines(self, starts, lcap, linfo, cinfo, before, after, invert, ws):
+        """the per-line context pass over the current planes' offsets and the device-made starts; returns the planes
+        (rel, begin, next, kind) of the kept lines, lcap + 2 cells each.  ws: (buffer, nbytes)"""
+        rel, beg, nxt, kind = self.planes(lcap + 2, 4)
+        self.m.line_context_lines_async(starts, lcap, linfo, 0, self.n, self.off, self.max_records, rel, beg, nxt, kind,
+                                        lcap + 2, cinfo, before=before, after=after, invert=invert, seg_start=self.d_st,
+                                        segments=self.nseg, workspace=ws)
+        return rel, beg, nxt, kind
+
+    def format(self, begin, end, ranges, info, out_capacity, glue, terminator, end_inclusive=False, **prefix):
+        """the format pass over the text and two planes of ranges; prefix: format_async's kind_plane, num_plane,
+        seg_num, names, name_off, names_bytes, number, offset, bases and separators.  Returns (out, at, seg_out) as
+        extract does"""
+        ws = self.workspace(self.m.lib.acm_format_workspace_bytes, ranges, self.nseg)
+        out = self.alloc(max((out_capacity + 15) // 16 * 16, 16))
+        at = self.alloc((ranges + 2) * 4)
+        seg = self.alloc(self.nseg * 4) if self.nseg else None
+        self.m.format_async(self.d, self.n, begin, end, ranges, out, out_capacity, info, end_inclusive=end_inclusive,
+                            glue=glue, terminator=terminator, at_out=at, at_capacity=ranges + 2, seg_start=self.d_st,
+                            segments=self.nseg, seg_out=seg, workspace=ws, **prefix)
+        return out, at, seg
+
     # ---- results
 
     def count(self):
@@ -1507,6 +1529,136 @@ class Matcher:
                 cols[0] = cols[0] + first
                 groups = np.stack(cols, axis=1) if k else np.zeros((0, 4), dtype=np.int64)
             return data, groups, at_cells, res, seg_cells
+
+    def line_context_lines_async(self, line_start, capacity, info, text_origin, text_end, off_plane, max_records, rel_out,
+                                 begin_out, next_out, kind_out, out_capacity, ctx_info, before=0, after=0, invert=False,
+                                 seg_start=None, segments=0, workspace=None, stream=None):
+        """Enqueue acm_line_context_lines_async: line_context_async's lines, one entry per KEPT line instead of one per
+        group: (delimiters in front, first byte, first byte behind, kind) planes in the scan's cell layout, kind
+        being LINE_SELECTED | LINE_GROUP_HEAD, and ctx_info (int32[4]: selected lines, kept lines, groups, 0).
+        workspace: (ptr, nbytes), or None for a temporary one (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        with self._workspace(workspace, st, self.lib.acm_line_context_lines_workspace_bytes, capacity, segments) as (ws, nb):
+            check(self.lib.acm_line_context_lines_async(
+                _ptr(line_start), capacity, _ptr(info), text_origin, text_end, _ptr(off_plane), max_records,
+                1 if invert else 0, before, after, _ptr(seg_start), segments, _ptr(rel_out), _ptr(begin_out),
+                _ptr(next_out), _ptr(kind_out), out_capacity, _ptr(ctx_info), _ptr(ws), nb, st),
+                "acm_line_context_lines_async")
+
+    def format_async(self, d_text, n, begin_plane, end_plane, max_ranges, out, out_capacity, info, text_origin=0,
+                     end_inclusive=False, kind_plane=None, num_plane=None, seg_num=None, number=False, offset=False,
+                     number_base=1, offset_base=0, sel_sep=b":", ctx_sep=b"-", names=None, name_off=None, names_bytes=0,
+                     glue=b"", terminator=-1, at_out=None, at_capacity=0, seg_start=None, segments=0, seg_out=None,
+                     workspace=None, stream=None):
+        """Enqueue the format pass (acm_format_async): extract_async with a prefix in front of every range's bytes.
+        names and name_off (device uint8[names_bytes] and int32[segments + 2]): the name of every text id, printed
+        when given; number: print number_base + num_plane's cell (less seg_num's cell of the range's text, device
+        int32[segments]); offset: print offset_base + the range's first byte relative to its text; behind each of
+        them sel_sep for a range whose kind_plane cell has LINE_SELECTED (no kind_plane: every range), else ctx_sep.
+        glue goes in front of a range with LINE_GROUP_HEAD that follows a range of the same text.  Everything else
+        is extract_async's."""
+        st = stream if stream is not None else self.stream
+        glue = bytes(glue)
+        byte = lambda v: v[0] if isinstance(v, (bytes, bytearray)) else int(v)
+        flags = (_lib.EXTRACT_END_INCLUSIVE if end_inclusive else 0) | (_lib.FORMAT_NAME if names is not None else 0) | \
+            (_lib.FORMAT_NUMBER if number else 0) | (_lib.FORMAT_OFFSET if offset else 0)
+        with self._workspace(workspace, st, self.lib.acm_format_workspace_bytes, max_ranges, segments) as (ws, nb):
+            check(self.lib.acm_format_async(
+                _ptr(d_text), n, text_origin, _ptr(begin_plane), _ptr(end_plane), max_ranges, flags, _ptr(kind_plane),
+                _ptr(num_plane), _ptr(seg_num), number_base, offset_base, byte(sel_sep), byte(ctx_sep), _ptr(names),
+                _ptr(name_off), names_bytes, glue if glue else None, len(glue), byte(terminator), _ptr(out), out_capacity,
+                _ptr(at_out), at_capacity, _ptr(seg_start), segments, _ptr(seg_out), _ptr(info), _ptr(ws), nb, st),
+                "acm_format_async")
+
+    def scan_format(self, text=None, texts=None, names=None, with_name=False, line_number=False, byte_offset=False,
+                    before=0, after=0, invert=False, per_line=False, only_matching=False, glue=None, terminator=None,
+                    out_capacity=None, delimiter=b"\n", init_state=0):
+        """grep -H -n -b on the device: scan_extract's output with `name:line:offset:` in front of every selected
+        line and `name-line-offset-` in front of every context line.  The stages of scan_extract with the per-line
+        context pass (acm_line_context_lines_async) and the format pass (acm_format_async) in the place of the
+        group form and the extract.  names: one bytes per text (one for text), printed with with_name;
+        line_number: the 1-based line in its text; byte_offset: the line's first byte in its text.  The glue goes
+        between two groups of one text only.  only_matching: the stages of scan_select, acm_line_number_async
+        over the matches' starts, then the format pass over the matches (grep -o -n -b: the line and the offset of
+        the match itself); ValueError for an automaton with wildcard contexts, as scan_extract.
+        Returns (out_bytes, lines, at, info, seg_out): lines int64[k, 4] of (1-based line in the call, first byte,
+        first byte behind, kind) per kept line (only_matching: (line, start, end, LINE_SELECTED) per match); at:
+        where every line's bytes begin in the output, behind its prefix; info and seg_out as extract_async leaves
+        them.  out_capacity: by default a bound that always fits: scan_extract's, and for every line the longest
+        prefix this text can have (the longest name, the digits of n + 1, a separator each).  An output that does
+        not fit is ACM_ERR_CAPACITY, never cut silently."""
+        d = delimiter[0] if isinstance(delimiter, (bytes, bytearray)) else int(delimiter)
+        if only_matching and self.wild:
+            raise ValueError("only_matching needs an automaton without wildcard contexts: a match there ends "
+                             "behind its record's offset")
+        if before < 0 or after < 0:
+            raise ValueError("before and after are >= 0")
+        term = d if terminator is None else (terminator[0] if isinstance(terminator, (bytes, bytearray)) else int(terminator))
+        with _Pipeline(self, "Matcher.scan_format", text, texts) as pl:
+            n, info, lcap = pl.n, pl.alloc(32), pl.n + 1
+            table = None
+            if with_name:
+                given = [bytes(x) for x in (names if names is not None else [])]
+                if len(given) != max(pl.nseg, 1) or any(len(x) > _lib.FORMAT_MAX_NAME for x in given):
+                    raise ValueError("with_name needs one name per text, of at most %d bytes each" % _lib.FORMAT_MAX_NAME)
+                table = ([b""] if pl.nseg else []) + given      # text id 0: what lies in front of the first start
+            widest = (max(len(x) for x in table) + 1 if table else 0) + \
+                ((len(str(n + 1)) + 1) if line_number else 0) + ((len(str(n)) + 1) if byte_offset else 0)
+            prefix = dict(number=line_number, offset=byte_offset)
+            if table:
+                off = np.concatenate([[0], np.cumsum([len(x) for x in table])]).astype(np.int32)
+                blob = np.frombuffer(b"".join(table), dtype=np.uint8)
+                prefix.update(names=pl.upload(blob if blob.size else np.zeros(1, dtype=np.uint8)), name_off=pl.upload(off, pad_to=0),
+                              names_bytes=int(blob.size))
+            idx_ws = self.lib.acm_line_index_workspace_bytes(n)
+            ctx_ws = self.lib.acm_line_context_lines_workspace_bytes(lcap, pl.nseg)
+            starts, linfo, ws, cinfo = pl.alloc(lcap * 4), pl.alloc(32), pl.alloc(max(idx_ws, ctx_ws)), pl.alloc(16)
+            self.line_index_async(pl.d, n, starts, lcap, linfo, delimiter=d, workspace=(ws.ptr, idx_ws))
+            if line_number and pl.nseg:
+                prefix["seg_num"] = pl.alloc(pl.nseg * 4)
+                self.line_number_async(starts, lcap, linfo, pl.d_st, pl.nseg, prefix["seg_num"])
+            if only_matching:
+                sel_info = pl.alloc(16)
+                start = self._select_stages(pl, init_state, sel_info, None)
+                pl.max_records = k = pl.count()
+                g = b""
+                num = pl.alloc((k + 2) * 4)
+                self.line_number_async(starts, lcap, linfo, start.ptr + 4, k, num.ptr + 4)
+                cap = out_capacity if out_capacity is not None else min(n + k * (1 + widest), 2 ** 31 - 17)
+                begin, end, ranges, incl = start, pl.off, k, True
+                planes = (num, start, pl.off, None)
+                prefix.update(num_plane=num)
+            else:
+                g = (b"--" + bytes([d]) if before + after > 0 else b"") if glue is None else bytes(glue)
+                pl.scan(init_state, _lib.REPORT_STATE if per_line or pl.nseg else _lib.REPORT_HEAD)
+                if pl.nseg:
+                    pl.segment(_lib.REPORT_STATE if per_line else _lib.REPORT_HEAD)
+                if per_line:
+                    pl.segment(_lib.REPORT_HEAD, seg_start=starts, segments=lcap)
+                rel, beg, nxt, kind = pl.line_context_lines(starts, lcap, linfo, cinfo, before, after, invert, (ws.ptr, ctx_ws))
+                cap = out_capacity if out_capacity is not None else min(n + lcap * (1 + len(g) + widest), 2 ** 31 - 17)
+                begin, end, ranges, incl = beg, nxt, lcap, False
+                planes = (rel, beg, nxt, kind)
+                prefix.update(kind_plane=kind, num_plane=rel)
+            out, at, seg = pl.format(begin, end, ranges, info, cap, g, term, incl, **prefix)
+            res = info.to_numpy(np.int32, 8, stream=self.stream)
+            m = (int(np.uint32(res[3])) << 32) | int(np.uint32(res[2]))
+            if res[6]:
+                raise AcmError(_lib.ACM_ERR_CAPACITY, pl.where, "the output has %d bytes but the buffer holds %d" % (m, cap))
+            data = out.to_numpy(np.uint8, m, stream=self.stream).tobytes()
+            used = int(res[0])
+            at_cells = at.to_numpy(np.int32, used + 2, stream=self.stream)[1:1 + used].copy()
+            seg_cells = seg.to_numpy(np.int32, pl.nseg, stream=self.stream) if seg is not None else None
+            h = linfo.to_numpy(np.int32, 8, stream=self.stream)
+            first = 1 + (int(np.uint32(h[4])) | int(np.uint32(h[5])) << 32)
+            k = ranges if only_matching else int(planes[0].to_numpy(np.int32, 1, stream=self.stream)[0])
+            cols = [x.to_numpy(np.int32, k + 1, stream=self.stream)[1:].astype(np.int64) if x is not None
+                    else np.full(k, _lib.LINE_SELECTED, dtype=np.int64) for x in planes]
+            cols[0] = cols[0] + first
+            if only_matching:
+                cols[2] = cols[2] + 1
+            lines = np.stack(cols, axis=1) if k else np.zeros((0, 4), dtype=np.int64)
+            return data, lines, at_cells, res, seg_cells
 
     def scan(self, text, init_state=0):
         """Scan host bytes: upload, scan, download."""

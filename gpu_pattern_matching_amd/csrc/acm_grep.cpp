@@ -174,6 +174,15 @@ double now_us()
 	       "  -V             with -C: the lines that hold NO record are the selected ones (grep -v)\n"
 	       "  -T dir         with -C: where the extracted lines go: dir/<name> for every file of a directory or list given\n"
 	       "                 with -f, named and refused as -O names and refuses them\n"
+	       "  -H             with -C and -T: the file's name and ':' in front of every selected line, the name and '-' in front\n"
+	       "                 of every context line (grep -H).  The name is the path of the input file as -f resolved it\n"
+	       "  -N             with -C and -T: the line's number in its file, from 1, and the same separator (grep -n; -n keeps\n"
+	       "                 its meaning here: the line of every record on stdout)\n"
+	       "  -b             with -C and -T: the offset of the line's first byte in its file and the same separator (grep -b).\n"
+	       "                 With any of the three the per-line context pass and the format pass run in the place of the\n"
+	       "                 group pass and the extract, all on the device; -H -N -b together print name:line:offset:.  The\n"
+	       "                 output buffer is sized for lines of four bytes or more on average; a buffer whose output does\n"
+	       "                 not fit is an error that says so (extensions; they work with -V; each needs -C and -T)\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -216,6 +225,9 @@ struct Config {
 	std::string repl_path, out_dir;   // -r, -O
 	std::string ext_dir;     // -T
 	int ctx = 0, ctx_before = 0, ctx_after = 0, invert = 0;   // -C N[,M], -V
+	int fmt_name = 0, fmt_num = 0, fmt_off = 0;   // -H, -N, -b
+	int fmt = 0;             // any of them: the per-line context pass and the format pass take the place of the group pass and the extract
+	size_t fmt_width = 0;    // the longest prefix a line can get: the longest input path, the digits and the separators
 	int extract = 0;         // -C and -T: the selected lines and their context are packed on the device and the files written
 	int rewrite = 0;         // -r: the selected matches are replaced on the device and the rewritten files written (only is set too)
 	int dev = -1, hex = 0, verbose = 0, text_mode = 0, follow = 0, threads = 2, all_patterns = 0, nocase = 0, segmented = 0,
@@ -309,6 +321,11 @@ struct Buffer {   // one of the two staging buffers of a worker
 	void *d_ex_lines = nullptr, *d_ex_line_info = nullptr, *d_ex_ws = nullptr, *d_ex_text = nullptr, *d_ex_rel = nullptr,
 	     *d_ex_begin = nullptr, *d_ex_next = nullptr, *d_ex_ctx_info = nullptr, *d_ex_out = nullptr, *d_ex_info = nullptr,
 	     *d_ex_seg = nullptr;
+	// -H, -N, -b: the kind of every kept line, the names of this buffer's files (text id 0, in front of the first start,
+	// has none) and where each lies, the lines in front of every file
+	void *d_ex_kind = nullptr, *d_ex_names = nullptr, *d_ex_name_off = nullptr, *d_ex_seg_num = nullptr;
+	std::vector<uint8_t> ex_names;
+	std::vector<int32_t> ex_name_off;
 	int32_t *h_ex_info = nullptr, *h_ex_seg = nullptr;
 	unsigned char *h_ex_out = nullptr;
 	size_t ex_ws_bytes = 0, ex_cap = 0, ex_lcap = 0;
@@ -494,6 +511,15 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 		b.ex_cap = std::min(size * 5 / 2 + 4 * G + 64, (size_t)0x7FFFFFE0ul);
 		b.ex_ws_bytes = std::max(std::max(acm_line_index_workspace_bytes(size), acm_line_context_workspace_bytes(b.ex_lcap, G + 1)),
 		    acm_extract_workspace_bytes(b.ex_lcap, G + 1));
+		if (c.fmt) {   // (a prefix for every line, were the lines four bytes on average; collect_extract() refuses what does not fit)
+			b.ex_cap = std::min(b.ex_cap + (size / 4 + 4096) * c.fmt_width, (size_t)0x7FFFFFE0ul);
+			b.ex_ws_bytes = std::max(b.ex_ws_bytes, std::max(acm_line_context_lines_workspace_bytes(b.ex_lcap, G + 1),
+			    acm_format_workspace_bytes(b.ex_lcap, G + 1)));
+			CK(acm_rt_malloc(&b.d_ex_kind, (b.ex_lcap + 2) * 4));
+			CK(acm_rt_malloc(&b.d_ex_names, (G + 1) * (c.fmt_width + 1) + 16));
+			CK(acm_rt_malloc(&b.d_ex_name_off, (G + 3) * 4));
+			CK(acm_rt_malloc(&b.d_ex_seg_num, (G + 1) * 4));
+		}
 		CK(acm_rt_malloc(&b.d_ex_lines, b.ex_lcap * 4));
 		CK(acm_rt_malloc(&b.d_ex_line_info, 32));
 		CK(acm_rt_malloc(&b.d_ex_ws, b.ex_ws_bytes));
@@ -850,14 +876,44 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		CK(acm_rt_memcpy_h2d(b.d_rw_start, b.rw_starts.data(), ns * 4, s));
 		CK(acm_line_index_async(lines_of, b.stream_len, 0, '\n', -1, nullptr, (int32_t *)b.d_ex_lines, b.ex_lcap,
 		    (int32_t *)b.d_ex_line_info, b.d_ex_ws, b.ex_ws_bytes, s));
-		CK(acm_line_context_async((const int32_t *)b.d_ex_lines, b.ex_lcap, (const int32_t *)b.d_ex_line_info, 0, (long)b.stream_len,
-		    off, cap - 2, c.invert, c.ctx_before, c.ctx_after, (const int32_t *)b.d_rw_start, ns, (int32_t *)b.d_ex_rel,
-		    (int32_t *)b.d_ex_begin, (int32_t *)b.d_ex_next, nullptr, b.ex_lcap + 2, (int32_t *)b.d_ex_ctx_info, b.d_ex_ws,
-		    b.ex_ws_bytes, s));
 		const bool sep = c.ctx_before + c.ctx_after > 0;
-		CK(acm_extract_async(b.text, b.stream_len, 0, (const int32_t *)b.d_ex_begin, (const int32_t *)b.d_ex_next, b.ex_lcap, 0,
-		    (const uint8_t *)"--\n", sep ? 3 : 0, '\n', b.d_ex_out, b.ex_cap, nullptr, 0, (const int32_t *)b.d_rw_start, ns,
-		    (int32_t *)b.d_ex_seg, (int32_t *)b.d_ex_info, b.d_ex_ws, b.ex_ws_bytes, s));
+		if (c.fmt) {
+			// one entry per kept line, and in front of each its file's name, its line and its offset in that file: the
+			// lines in front of every file start come from the same index (every file start is a line start there)
+			b.ex_names.clear();
+			b.ex_name_off.assign(1, 0);
+			for (size_t k = 0; k <= ns; k++) {   // text id k: file k - 1 of this buffer
+				if (k > 0 && c.fmt_name) {
+					const std::string &name = w.sh->files[(size_t)b.rw_files[k - 1]];
+					b.ex_names.insert(b.ex_names.end(), name.begin(), name.end());
+				}
+				b.ex_name_off.push_back((int32_t)b.ex_names.size());
+			}
+			if (!b.ex_names.empty())
+				CK(acm_rt_memcpy_h2d(b.d_ex_names, b.ex_names.data(), b.ex_names.size(), s));
+			CK(acm_rt_memcpy_h2d(b.d_ex_name_off, b.ex_name_off.data(), b.ex_name_off.size() * 4, s));
+			if (ns > 0)
+				CK(acm_line_number_async((const int32_t *)b.d_ex_lines, b.ex_lcap, (const int32_t *)b.d_ex_line_info,
+				    (const int32_t *)b.d_rw_start, nullptr, ns, (int32_t *)b.d_ex_seg_num, s));
+			CK(acm_line_context_lines_async((const int32_t *)b.d_ex_lines, b.ex_lcap, (const int32_t *)b.d_ex_line_info, 0,
+			    (long)b.stream_len, off, cap - 2, c.invert, c.ctx_before, c.ctx_after, (const int32_t *)b.d_rw_start, ns,
+			    (int32_t *)b.d_ex_rel, (int32_t *)b.d_ex_begin, (int32_t *)b.d_ex_next, (int32_t *)b.d_ex_kind, b.ex_lcap + 2,
+			    (int32_t *)b.d_ex_ctx_info, b.d_ex_ws, b.ex_ws_bytes, s));
+			const unsigned flags = (c.fmt_name ? ACM_FORMAT_NAME : 0) | (c.fmt_num ? ACM_FORMAT_NUMBER : 0) | (c.fmt_off ? ACM_FORMAT_OFFSET : 0);
+			CK(acm_format_async(b.text, b.stream_len, 0, (const int32_t *)b.d_ex_begin, (const int32_t *)b.d_ex_next, b.ex_lcap, flags,
+			    (const int32_t *)b.d_ex_kind, (const int32_t *)b.d_ex_rel, (const int32_t *)b.d_ex_seg_num, 1, 0, ':', '-',
+			    (const uint8_t *)b.d_ex_names, (const int32_t *)b.d_ex_name_off, b.ex_names.size(), (const uint8_t *)"--\n", sep ? 3 : 0,
+			    '\n', b.d_ex_out, b.ex_cap, nullptr, 0, (const int32_t *)b.d_rw_start, ns, (int32_t *)b.d_ex_seg,
+			    (int32_t *)b.d_ex_info, b.d_ex_ws, b.ex_ws_bytes, s));
+		} else {
+			CK(acm_line_context_async((const int32_t *)b.d_ex_lines, b.ex_lcap, (const int32_t *)b.d_ex_line_info, 0, (long)b.stream_len,
+			    off, cap - 2, c.invert, c.ctx_before, c.ctx_after, (const int32_t *)b.d_rw_start, ns, (int32_t *)b.d_ex_rel,
+			    (int32_t *)b.d_ex_begin, (int32_t *)b.d_ex_next, nullptr, b.ex_lcap + 2, (int32_t *)b.d_ex_ctx_info, b.d_ex_ws,
+			    b.ex_ws_bytes, s));
+			CK(acm_extract_async(b.text, b.stream_len, 0, (const int32_t *)b.d_ex_begin, (const int32_t *)b.d_ex_next, b.ex_lcap, 0,
+			    (const uint8_t *)"--\n", sep ? 3 : 0, '\n', b.d_ex_out, b.ex_cap, nullptr, 0, (const int32_t *)b.d_rw_start, ns,
+			    (int32_t *)b.d_ex_seg, (int32_t *)b.d_ex_info, b.d_ex_ws, b.ex_ws_bytes, s));
+		}
 		CK(acm_rt_memcpy_d2h(b.h_ex_info, b.d_ex_info, 32, s));
 		CK(acm_rt_memcpy_d2h(b.h_ex_seg, b.d_ex_seg, ns * 4, s));
 	}
@@ -1295,7 +1351,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xor:O:C:VT:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o, r, O, C, V, T
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xor:O:C:VT:HNb")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o, r, O, C, V, T, H, N, b
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -1350,6 +1406,9 @@ int main(int argc, char **argv)
 		}
 		case 'V': c.invert = 1; break;
 		case 'T': c.ext_dir = optarg; break;
+		case 'H': c.fmt_name = 1; break;
+		case 'N': c.fmt_num = 1; break;
+		case 'b': c.fmt_off = 1; break;
 		default: usage();
 		}
 	}
@@ -1465,6 +1524,11 @@ int main(int argc, char **argv)
 		printf("ERROR: -V needs -C and -T: it inverts the selection of the lines that are extracted\n");
 		err++;
 	}
+	c.fmt = c.fmt_name || c.fmt_num || c.fmt_off;
+	if (c.fmt && (!c.ctx || c.ext_dir.empty())) {
+		printf("ERROR: -H, -N and -b need -C and -T: they put a prefix in front of the lines that are extracted\n");
+		err++;
+	}
 	if (!c.ctx && !c.ext_dir.empty()) {
 		printf("ERROR: -T needs -C: the lines of context around a selected line (-C 0: none)\n");
 		err++;
@@ -1573,6 +1637,16 @@ int main(int argc, char **argv)
 	if (c.rewrite && acm_automaton_load_replacement_file(aut, c.repl_path.c_str()) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
+	}
+	if (c.fmt) {   // the longest prefix: a path (-H), a line number and an offset of a buffer (int32), a separator each
+		size_t longest = 0;
+		for (const std::string &f : sh.files)
+			longest = std::max(longest, f.size());
+		if (c.fmt_name && longest > ACM_FORMAT_MAX_NAME) {
+			fprintf(stderr, "ERROR: -H: an input path has %zu bytes, a name at most %d\n", longest, ACM_FORMAT_MAX_NAME);
+			return 1;
+		}
+		c.fmt_width = (c.fmt_name ? longest + 1 : 0) + (c.fmt_num ? 11 : 0) + (c.fmt_off ? 11 : 0);
 	}
 	if (c.rewrite || c.extract) {   // a file of a directory or a list goes to <-O>/<its name> (-C: <-T>/<its name>)
 		const char *opt_name = c.rewrite ? "-O" : "-T";

@@ -16,6 +16,7 @@
 // set), then the two-launch ordered write of record_pass.h over the bits.  Cost per record and per line,
 // never per text byte.  acm_line_context_async: the same bits, a prefix of their counts, and per line a
 // window clamped to its text; heads and tails of the runs of kept lines, written in order (see "context").
+// acm_line_context_lines_async: the same with the kept bits as a plane and one ordered write over them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -518,6 +519,132 @@ CtxLayout ctx_layout(size_t capacity)
 	return l;
 }
 
+// ---- the per-line form: one entry per KEPT line (acm_line_context_lines_async) ----
+// k_line_mark, k_ctx_count and k_ctx_rank as above, then
+//   k_ctx_keep_lines    k_ctx_keep's lane per line, leaving the KEPT bits and the head bits as planes; per block the
+//                       kept lines and the heads
+//   k_ctx_lines_write   the ordered write over the kept bits: rel, begin, next, and the kind from the SELECTED and the
+//                       head bit of the line
+struct CtxLinesArgs {
+	CtxArgs c;
+	uint32_t *kept;      // per flag word
+	int32_t *kind_out;
+};
+
+__global__ __launch_bounds__(kThreads) void k_ctx_keep_lines(CtxLinesArgs a)
+{
+	__shared__ uint32_t red[kWaves];
+	const CtxArgs &c = a.c;
+	uint32_t L, lead;
+	const uint32_t lines = lines_of(c.s, L, lead);
+	const uint32_t words = (lines + 31) / 32;
+	const Words sh = words_of(words);
+	const uint32_t lane = lane_id();
+	uint32_t kept = 0, heads = 0;   // (counted by lane 0 of every wave)
+	const uint64_t j_end = min((uint64_t)sh.w_end * 32, (uint64_t)lines);
+	for (uint64_t j0 = (uint64_t)sh.w_begin * 32; j0 < j_end; j0 += kThreads) {
+		const uint64_t jj = j0 + threadIdx.x;
+		const uint32_t j = (uint32_t)jj;
+		LineCtx x{ false, 0, 0 };
+		if (jj < j_end)
+			x = line_ctx(c, j, lines, L, lead);
+		bool prev = __shfl_up((int)x.kept, 1, 64) != 0;   // the lane in front, but for a wave's first
+		if (lane == 0 && x.kept && j > x.lo)
+			prev = line_ctx(c, j - 1, lines, L, lead).kept;
+		const bool head = x.kept && (j == x.lo || !prev);
+		const uint64_t kb = __ballot(x.kept), hb = __ballot(head);
+		const uint32_t w = (uint32_t)((j0 + (threadIdx.x & ~63u)) >> 5);   // the wave's first word
+		if (lane == 0) {
+			kept += (uint32_t)__popcll(kb);
+			heads += (uint32_t)__popcll(hb);
+			if (w < sh.w_end) {
+				a.kept[w] = (uint32_t)kb;
+				c.head[w] = (uint32_t)hb;
+			}
+			if (w + 1 < sh.w_end) {
+				a.kept[w + 1] = (uint32_t)(kb >> 32);
+				c.head[w + 1] = (uint32_t)(hb >> 32);
+			}
+		}
+	}
+	kept = block_sum(kept, red);
+	heads = block_sum(heads, red);
+	if (threadIdx.x == 0) {
+		c.blk_kept[blockIdx.x] = (int32_t)kept;
+		c.blk_head[blockIdx.x] = (int32_t)heads;
+	}
+}
+
+__global__ __launch_bounds__(kThreads) void k_ctx_lines_write(CtxLinesArgs a)
+{
+	__shared__ uint32_t red[2 * kWaves];
+	const CtxArgs &c = a.c;
+	const SelectArgs &g = c.s;
+	uint32_t L, lead;
+	const uint32_t lines = lines_of(g, L, lead);
+	const Words sh = words_of((lines + 31) / 32);
+	uint32_t total, groups;
+	blocks_before(c.blk_head, red, groups);
+	uint32_t base = blocks_before(c.blk_kept, red, total);
+	if (blockIdx.x == 0 && threadIdx.x == 0) {
+		write_ends(g.rel_out, g.cap, total, 0);
+		write_ends(g.begin_out, g.cap, total, 0);
+		write_ends(g.next_out, g.cap, total, 0);
+		write_ends(a.kind_out, g.cap, total, 0);
+		c.ctx_info[1] = (int32_t)total;
+		c.ctx_info[2] = (int32_t)groups;
+		c.ctx_info[3] = 0;
+	}
+	for (uint32_t w0 = sh.w_begin; w0 < sh.w_end; w0 += kTileWords) {
+		const uint32_t w = w0 + threadIdx.x;
+		uint32_t bits = 0, hbits = 0, sbits = 0;
+		if (w < sh.w_end) {
+			bits = a.kept[w];
+			hbits = c.head[w];
+			sbits = g.flags[w];
+		}
+		uint32_t tile_total;
+		uint32_t d = base + block_prefix((uint32_t)__popc(bits), red, tile_total);
+		while (bits) {
+			const uint32_t b = (uint32_t)__ffs((int)bits) - 1;
+			const uint32_t line = w * 32 + b;
+			bits &= bits - 1;
+			if (d + 2 < g.cap) {
+				const int64_t k = (int64_t)line - lead;
+				g.rel_out[1 + d] = (int32_t)line;
+				g.begin_out[1 + d] = k < 0 ? (int32_t)g.origin : g.line_start[k];
+				g.next_out[1 + d] = k + 1 < (int64_t)L ? g.line_start[k + 1] : (int32_t)g.end;
+				a.kind_out[1 + d] = (int32_t)(((sbits >> b) & 1) * ACM_LINE_SELECTED | ((hbits >> b) & 1) * ACM_LINE_GROUP_HEAD);
+			}
+			d++;
+		}
+		base += tile_total;
+	}
+}
+
+struct CtxLinesLayout {
+	size_t flags, rank, head, kept, blk_kept, blk_head, total;
+};
+
+CtxLinesLayout ctx_lines_layout(size_t capacity)
+{
+	CtxLinesLayout l;
+	size_t at = kCountBytes;   // the selected lines per block, as in the select pass
+	auto take = [&](size_t bytes) {
+		const size_t here = at;
+		at += round256(bytes);
+		return here;
+	};
+	l.flags = take(flag_bytes(capacity));
+	l.rank = take(flag_bytes(capacity));
+	l.head = take(flag_bytes(capacity));
+	l.kept = take(flag_bytes(capacity));
+	l.blk_kept = take(kCountBytes);
+	l.blk_head = take(kCountBytes);
+	l.total = at;
+	return l;
+}
+
 size_t mask_words(size_t n) { return ((n + 15) / 16 + 3) / 4; }
 
 // blocks of the fixed grid: four per CU of the current device, kMaxBlocks at most
@@ -708,6 +835,72 @@ extern "C" int acm_line_context_async(const int32_t *d_line_start, size_t capaci
 	hipLaunchKernelGGL(k_ctx_write<false>, dim3(blocks), dim3(kThreads), 0, s, c);
 	ACM_HIP_TRY(hipGetLastError());
 	hipLaunchKernelGGL(k_ctx_write<true>, dim3(blocks), dim3(kThreads), 0, s, c);
+	ACM_HIP_TRY(hipGetLastError());
+	return ACM_OK;
+}
+
+extern "C" size_t acm_line_context_lines_workspace_bytes(size_t capacity, size_t segments)
+{
+	(void)segments;   // (the starts are searched where they lie)
+	return ctx_lines_layout(capacity).total;
+}
+
+extern "C" int acm_line_context_lines_async(const int32_t *d_line_start, size_t capacity, const int32_t *d_info, long text_origin,
+    long text_end, const int32_t *d_off_plane, size_t max_records, int invert, int before, int after, const int32_t *d_seg_start,
+    size_t segments, int32_t *d_rel_out, int32_t *d_begin_out, int32_t *d_next_out, int32_t *d_kind_out, size_t out_capacity,
+    int32_t *d_ctx_info, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+	if (!d_line_start || !d_info || !d_off_plane || !d_rel_out || !d_begin_out || !d_next_out || !d_kind_out || !d_ctx_info ||
+	    capacity == 0 || capacity > 0xFFFFFFFEul || out_capacity < 2 || max_records > 0x7FFFFFFEul || text_end < text_origin ||
+	    before < 0 || after < 0 || segments > 0x7FFFFFFFul || (segments > 0) != (d_seg_start != nullptr))
+		return acm::fail(ACM_ERR_ARG, "acm_line_context_lines_async: bad arguments");
+	const CtxLinesLayout l = ctx_lines_layout(capacity);
+	if (!d_workspace || workspace_bytes < l.total)
+		return acm::fail(ACM_ERR_ARG, "acm_line_context_lines_async: workspace %zu B < required %zu B", workspace_bytes, l.total);
+	hipStream_t s = (hipStream_t)stream;
+	uint32_t blocks = 0;
+	if (int rc = fixed_grid(&blocks))
+		return rc;
+	char *ws = (char *)d_workspace;
+	CtxLinesArgs a{};
+	CtxArgs &c = a.c;
+	SelectArgs &g = c.s;
+	g.line_start = d_line_start;
+	g.capacity = (uint32_t)capacity;
+	g.info = d_info;
+	g.origin = (int64_t)text_origin;
+	g.end = (int64_t)text_end;
+	g.off_plane = d_off_plane;
+	g.max_records = (uint32_t)max_records;
+	g.invert = invert ? 1 : 0;
+	g.rel_out = d_rel_out;
+	g.begin_out = d_begin_out;
+	g.next_out = d_next_out;
+	g.cap = clamp_cap(out_capacity);
+	g.block_counts = (int32_t *)ws;
+	g.flags = (uint32_t *)(ws + l.flags);
+	c.before = before;
+	c.after = after;
+	c.seg_start = d_seg_start;
+	c.segments = (uint32_t)segments;
+	c.ctx_info = d_ctx_info;
+	c.rank = (uint32_t *)(ws + l.rank);
+	c.head = (uint32_t *)(ws + l.head);
+	c.blk_kept = (int32_t *)(ws + l.blk_kept);
+	c.blk_head = (int32_t *)(ws + l.blk_head);
+	a.kept = (uint32_t *)(ws + l.kept);
+	a.kind_out = d_kind_out;
+	ACM_HIP_TRY(hipMemsetAsync(g.flags, 0, (capacity / 32 + 1) * 4, s));
+	const uint32_t mark_blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>(blocks, (max_records + kThreads - 1) / kThreads));
+	hipLaunchKernelGGL(k_line_mark, dim3(mark_blocks), dim3(kThreads), 0, s, g);
+	ACM_HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_ctx_count, dim3(blocks), dim3(kThreads), 0, s, c);
+	ACM_HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_ctx_rank, dim3(blocks), dim3(kThreads), 0, s, c);
+	ACM_HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_ctx_keep_lines, dim3(blocks), dim3(kThreads), 0, s, a);
+	ACM_HIP_TRY(hipGetLastError());
+	hipLaunchKernelGGL(k_ctx_lines_write, dim3(blocks), dim3(kThreads), 0, s, a);
 	ACM_HIP_TRY(hipGetLastError());
 	return ACM_OK;
 }

@@ -1,4 +1,4 @@
-// 64-bit placement: what the passes that write a packed byte output (rewrite.hip, extract.hip) share on top of the
+// 64-bit placement: what the passes that write a packed byte output (rewrite.hip, extract.hip, format.hip) share on top of the
 // record-pass core.  Internal to the library, gfx950 only.  Two launches of 64-bit block sums over the input cells give
 // every used cell its end in the output; the copy kernels find the cells of a tile of OUTPUT by a search on those ends.
 #pragma once
@@ -109,6 +109,52 @@ __device__ __forceinline__ uint4 load_source(const uint8_t *text, int64_t sx)
 	default: return make_uint4(AB(hi.x, lo.w), AB(hi.y, hi.x), AB(hi.z, hi.y), AB(hi.w, hi.z));
 	}
 #undef AB
+}
+
+// exclusive prefix maximum of v (>= 0) over the block in thread order, and the block's maximum.  red: kWaves cells.
+__device__ __forceinline__ int64_t block_prefix_max64(int64_t v, int64_t *red, int64_t &total)
+{
+	const uint32_t lane = lane_id(), wave = threadIdx.x / 64;
+	int64_t inc = v;
+	for (int o = 1; o < 64; o <<= 1) {
+		const int64_t up = __shfl_up((long long)inc, o, 64);
+		inc = lane >= (uint32_t)o ? max(inc, up) : inc;
+	}
+	__syncthreads();
+	if (lane == 63)
+		red[wave] = inc;
+	__syncthreads();
+	int64_t before = 0;
+	total = 0;
+	for (uint32_t w = 0; w < (uint32_t)kWaves; w++) {
+		before = w < wave ? max(before, red[w]) : before;
+		total = max(total, red[w]);
+	}
+	const int64_t up = __shfl_up((long long)inc, 1, 64);
+	return lane > 0 ? max(before, up) : before;
+}
+
+// 16 source bytes v, of which [lo, hi) go to tile[base + lo, base + hi): dwords where a whole one is owed
+__device__ __forceinline__ void lds_put(uint8_t *tile, const uint4 &v, int lo, int hi, int base)
+{
+	const uint32_t w[6] = { 0, v.x, v.y, v.z, v.w, 0 };
+	const int sh = base & 3, base4 = base - sh;   // (two's complement: sh in 0..3 for a negative base too)
+#pragma unroll
+	for (int k = 0; k < 5; k++) {
+		// the destination dword at base4 + 4 * k holds source bytes i0 .. i0 + 3
+		const int i0 = 4 * k - sh;
+		if (i0 + 4 <= lo || i0 >= hi)
+			continue;
+		const uint32_t d = sh == 0 ? w[k + 1] : __builtin_amdgcn_alignbyte(w[k + 1], w[k], (uint32_t)(4 - sh));
+		if (i0 >= lo && i0 + 4 <= hi) {
+			*(uint32_t *)(tile + base4 + 4 * k) = d;
+		} else {
+#pragma unroll
+			for (int c = 0; c < 4; c++)
+				if (i0 + c >= lo && i0 + c < hi)
+					tile[base4 + 4 * k + c] = (uint8_t)(d >> (8 * c));
+		}
+	}
 }
 
 }  // namespace acm_rp

@@ -1030,13 +1030,75 @@ int acm_rewrite_async(const acm_dfa *, const void *d_text, size_t n, long text_o
  * segments and out_capacity only -- m lives on the device -- and tiles behind min(m, out_capacity) leave
  * at once.  The workspace query is monotone in both arguments and a multiple of 256.
  * Not provided: extraction continued across calls (a range is used whole or not at all: give whole texts);
- * lines cut at a text start that is not a line start; per-line prefixes (file:line:) in the output;
- * wildcard post contexts in the END_INCLUSIVE (-o) form: such a match ends post bytes behind the offset. */
+ * lines cut at a text start that is not a line start; per-line prefixes (file:line:) in the output: that is
+ * acm_format_async below; wildcard post contexts in the END_INCLUSIVE (-o) form: such a match ends post bytes behind the offset. */
 enum { ACM_EXTRACT_END_INCLUSIVE = 1 };
 #define ACM_EXTRACT_MAX_GLUE 16
 size_t acm_extract_workspace_bytes(size_t max_ranges, size_t segments);
 int acm_extract_async(const void *d_text, size_t n, long text_origin,
     const int32_t *d_begin_plane, const int32_t *d_end_plane, size_t max_ranges, unsigned flags,
+    const uint8_t *glue, int glue_len, int terminator,
+    void *d_out, size_t out_capacity, int32_t *d_at_out, size_t at_capacity,
+    const int32_t *d_seg_start, size_t segments, int32_t *d_seg_out,
+    int32_t *d_info, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Formatting extract: acm_extract_async with a generated prefix in front of every range's bytes -- grep's
+ * `name:12:345:` in front of a selected line and `name-11-330-` in front of a context line (-H -n -b), or in
+ * front of every match (-o).  The text, the ranges, USED and skipped, ACM_EXTRACT_END_INCLUSIVE, the
+ * terminator, d_out / out_capacity, d_at_out, d_seg_start / d_seg_out, d_info[8], the robustness and the
+ * argument errors are acm_extract_async's, word for word; d_at_out still holds where a range's BYTES begin,
+ * behind its glue and its prefix, and everything a range puts into the output counts in m and d_seg_out.
+ * The text id t of a range is the extract's: the cells of d_seg_start that are <= b, 0..segments.
+ * More inputs:
+ *   d_kind_plane  int32, the scan's cell layout (cell 1 + i belongs to range i); may be NULL.  Bit 0
+ *                 (ACM_LINE_SELECTED) chooses the separator, bit 1 (ACM_LINE_GROUP_HEAD) asks for the glue;
+ *                 bits above bit 1 are ignored.  NULL: every range is SELECTED and none is a head.
+ *                 acm_line_context_lines_async's d_kind_out is such a plane
+ *   d_num_plane   int32, cell layout; required iff ACM_FORMAT_NUMBER: the number of range i before the bases
+ *                 (acm_line_context_lines_async's d_rel_out, or acm_line_number_async's output one cell up)
+ *   d_seg_num     int32[segments], may be NULL: what is subtracted from the numbers of text t > 0, cell t - 1
+ *                 (acm_line_number_async over d_seg_start: the lines in front of each text)
+ *   number_base, offset_base   0..10^18 each, else ACM_ERR_ARG (1 and 0 for grep)
+ *   sel_sep, ctx_sep   0..255: the byte behind every part of the prefix of a SELECTED / of another range
+ *   d_names, d_name_off, names_bytes   the name of text id t is d_names[off[t], off[t + 1]), d_name_off being
+ *                 int32[segments + 2].  A name whose two cells descend, leave [0, names_bytes] or lie more
+ *                 than ACM_FORMAT_MAX_NAME bytes apart is empty: no read leaves the table, whatever it holds.
+ *                 names_bytes <= 2^31 - 1
+ *   flags         ACM_EXTRACT_END_INCLUSIVE | ACM_FORMAT_NAME | ACM_FORMAT_NUMBER | ACM_FORMAT_OFFSET; unknown
+ *                 bits, ACM_FORMAT_NAME without both name arrays, ACM_FORMAT_NUMBER without d_num_plane and a
+ *                 separator outside 0..255 return ACM_ERR_ARG before anything is enqueued
+ * Output, for every used range in input order:
+ *   glue         iff the range's HEAD bit is set and a used range of the same text id lies in front (the last
+ *                used range in front decides; skipped cells in between do not matter)
+ *   prefix       with sep = sel_sep if the range is SELECTED, else ctx_sep:
+ *                  ACM_FORMAT_NAME    the name of t, then sep
+ *                  ACM_FORMAT_NUMBER  number_base + num[i] - (t > 0 && d_seg_num ? d_seg_num[t - 1] : 0), then sep
+ *                  ACM_FORMAT_OFFSET  offset_base + b - (t > 0 ? d_seg_start[t - 1] : text_origin), then sep
+ *                both values in int64, a negative one prints as 0; decimal, no sign, no padding, at least one digit
+ *   the bytes, the terminator   as in the extract
+ * With flags == 0 and d_kind_plane == NULL this is acm_extract_async with glue_len == 0, whatever glue is
+ * given.  With flags == 0, the planes of acm_line_context_lines_async and a glue, the bytes are those of the
+ * extract over acm_line_context_async's groups but for terminators inside a group (none when every line
+ * keeps its delimiter).
+ * Two launches over max_ranges cells place the parts (64-bit sums; a part's size includes its prefix: the
+ * name's length and a digit count against the powers of ten), two more give the segment sums, and the copy
+ * kernel runs on a grid over out_capacity: a workgroup owns 16 KiB of OUTPUT, finds its ranges by a search on
+ * the output ends and stages the tile in LDS: a thread per range writes glue, prefix and terminator (a name
+ * over 32 bytes is copied by the thread's wave), the bytes go as aligned 16-byte source pieces, a piece a
+ * lane, and the tile leaves in aligned 16-byte stores (csrc/format.hip).  The launch count and the grids
+ * depend on max_ranges, segments and out_capacity only.  Every run gives the same bytes.  The workspace
+ * query is monotone in both arguments and a multiple of 256.
+ * Not provided: prefixes continued across calls (the caller carries the bases); "--" between two texts (glue
+ * never joins texts; grep prints one there); padded or aligned numbers (grep -T); lines cut at a text start
+ * that is not a line start; wildcard post contexts in the END_INCLUSIVE form. */
+enum { ACM_FORMAT_NAME = 2, ACM_FORMAT_NUMBER = 4, ACM_FORMAT_OFFSET = 8 };
+#define ACM_FORMAT_MAX_NAME 4096
+size_t acm_format_workspace_bytes(size_t max_ranges, size_t segments);
+int acm_format_async(const void *d_text, size_t n, long text_origin,
+    const int32_t *d_begin_plane, const int32_t *d_end_plane, size_t max_ranges, unsigned flags,
+    const int32_t *d_kind_plane, const int32_t *d_num_plane, const int32_t *d_seg_num,
+    long number_base, long offset_base, int sel_sep, int ctx_sep,
+    const uint8_t *d_names, const int32_t *d_name_off, size_t names_bytes,
     const uint8_t *glue, int glue_len, int terminator,
     void *d_out, size_t out_capacity, int32_t *d_at_out, size_t at_capacity,
     const int32_t *d_seg_start, size_t segments, int32_t *d_seg_out,
@@ -1174,6 +1236,31 @@ int acm_line_context_async(const int32_t *d_line_start, size_t capacity, const i
     long text_origin, long text_end, const int32_t *d_off_plane, size_t max_records, int invert,
     int before, int after, const int32_t *d_seg_start, size_t segments,
     int32_t *d_rel_out, int32_t *d_begin_out, int32_t *d_next_out, int32_t *d_lines_out,
+    size_t out_capacity, int32_t *d_ctx_info, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* The per-line form of acm_line_context_async: the same inputs, the same line, SELECTED, text id, KEPT and
+ * GROUP rules and the same argument errors (d_kind_out in the place of d_lines_out, and required), but one
+ * entry per KEPT line instead of one per group, so that every line can get a prefix of its own
+ * (acm_format_async).  Output, the scan's cell layout and overflow contract in every plane ([0] = full
+ * count of kept lines, entries ascending, trailer cell at min(count + 1, out_capacity - 1) = 0), per line:
+ *   d_rel_out     delimiters in front of the line: acm_line_select_async's value, relative to the piece
+ *   d_begin_out   the line's first byte;  d_next_out: the first byte behind it
+ *   d_kind_out    bit 0 (ACM_LINE_SELECTED) iff the line is selected, bit 1 (ACM_LINE_GROUP_HEAD) iff it is
+ *                 the first line of its group
+ *   d_ctx_info    int32[4], required, written whole, as in the group form: selected lines, kept lines,
+ *                 groups, 0
+ * The entries whose HEAD bit is set begin acm_line_context_async's groups over the same input, and a group
+ * ends where the next begins.  Five launches behind the zero-fill of the flags -- the group form's first
+ * three, one that leaves the kept and the head bits as planes and one ordered write over the kept bits --
+ * on grids that depend on capacity and max_records only, never on before, after or the data
+ * (csrc/lines.hip).  Stream-ordered, no host sync, no allocation; exact when info[0] <= capacity.  The
+ * workspace query is monotone in both arguments and a multiple of 256.  Not provided: as the group form. */
+enum { ACM_LINE_SELECTED = 1, ACM_LINE_GROUP_HEAD = 2 };
+size_t acm_line_context_lines_workspace_bytes(size_t capacity, size_t segments);
+int acm_line_context_lines_async(const int32_t *d_line_start, size_t capacity, const int32_t *d_info,
+    long text_origin, long text_end, const int32_t *d_off_plane, size_t max_records, int invert,
+    int before, int after, const int32_t *d_seg_start, size_t segments,
+    int32_t *d_rel_out, int32_t *d_begin_out, int32_t *d_next_out, int32_t *d_kind_out,
     size_t out_capacity, int32_t *d_ctx_info, void *d_workspace, size_t workspace_bytes, void *stream);
 
 int acm_scan_batch_async(const acm_dfa *, const acm_scan_batch *);
