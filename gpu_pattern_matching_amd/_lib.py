@@ -48,6 +48,8 @@ LINE_SELECTED, LINE_GROUP_HEAD = 1, 2
 SEQ_MAX_PARTS = 32
 GAP_UNBOUNDED = 0x7FFFFFFF
 WILDCARD_MAX_POSITIONS = 4096
+APPROX_MAX_K = 15
+APPROX_MAX_LEN = 4096
 SIG_EXTENDED = 1
 SIG_GROUPS = 2
 GROUP_MAX_WIDTH = 32
@@ -114,6 +116,11 @@ NATIVE_API = {
     "acm_automaton_pattern_group": (C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.POINTER(_vp)]),
     "acm_automaton_groups": (C.c_int, [_vp]),
     "acm_automaton_add_signature_ex": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_uint, C.c_uint]),
+    "acm_automaton_add_approx": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_uint]),
+    "acm_automaton_num_approx": (C.c_int, [_vp]),
+    "acm_automaton_approx": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_uint), C.POINTER(_vp)]),
+    "acm_automaton_pattern_approx": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p]),
+    "acm_automaton_approx_reach": (C.c_int, [_vp, _i32p, _i32p]),
     "acm_automaton_load_signature_file_ex": (C.c_int, [_vp, C.c_char_p, C.c_uint, C.c_uint]),
     "acm_automaton_add_rule": (C.c_int, [_vp, _i32p, C.c_int, C.c_char_p, C.c_int]),
     "acm_automaton_num_rules": (C.c_int, [_vp]),
@@ -171,6 +178,10 @@ NATIVE_API = {
     "acm_wildcard_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_long, C.c_long, _vp, C.c_size_t,
                                              _vp, C.c_size_t, C.c_long, C.c_long, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp,
                                              C.c_size_t, _vp]),
+    "acm_approx_workspace_bytes": (C.c_size_t, [C.c_size_t]),
+    "acm_approx_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_long, C.c_long, _vp, C.c_size_t,
+                                           _vp, C.c_size_t, C.c_long, C.c_long, _vp, _vp, _vp, C.c_size_t, _vp, _vp,
+                                           C.c_size_t, _vp]),
     "acm_sequence_workspace_bytes": (C.c_size_t, [_vp, C.c_size_t]),
     "acm_sequence_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_long, C.c_long, _vp, _vp,
                                              C.c_size_t, _vp, _vp, C.c_size_t, _vp]),

@@ -333,6 +333,44 @@ class Automaton:
         check(self.lib.acm_automaton_wildcard_reach(self.h, C.byref(b), C.byref(f)), "acm_automaton_wildcard_reach")
         return b.value, f.value
 
+    def add_approx(self, pattern: bytes, k: int, iid: int = 0, nocase: bool = False):
+        """An approximate pattern (acm_automaton_add_approx): matches where at most k bytes differ.  Its k + 1 pieces
+        enter the automaton as consecutive patterns; returns the index of piece 0 (k == 0: a plain add, the index of
+        the new pattern).  nocase: the whole comparison folds ASCII case.  Only before compile(); the mismatches
+        are counted by Matcher.scan_approx."""
+        r = self.lib.acm_automaton_add_approx(self.h, bytes(pattern), len(pattern), k, iid,
+                                              _lib.PATTERN_NOCASE if nocase else 0)
+        if r < 0:
+            check(r, "acm_automaton_add_approx")
+        return r
+
+    @property
+    def num_approx(self):
+        return self.lib.acm_automaton_num_approx(self.h)
+
+    def approx(self, x):
+        """(first_piece, bytes, k, iid, flags) of approximate pattern x (acm_automaton_approx)"""
+        f, n, k, iid, fl, b = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint(), C.c_void_p()
+        check(self.lib.acm_automaton_approx(self.h, x, C.byref(f), C.byref(n), C.byref(k), C.byref(iid), C.byref(fl),
+                                            C.byref(b)), "acm_automaton_approx")
+        return f.value, C.string_at(b.value, n.value), k.value, iid.value, fl.value
+
+    def pattern_approx(self, i):
+        """(x, piece, pre, post) where pattern i is a piece of approximate pattern x (acm_automaton_pattern_approx):
+        pre bytes of x lie in front of the piece and post behind it; None for a plain pattern"""
+        x, j, pre, post = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        r = self.lib.acm_automaton_pattern_approx(self.h, i, C.byref(x), C.byref(j), C.byref(pre), C.byref(post))
+        if r < 0:
+            check(r, "acm_automaton_pattern_approx")
+        return (x.value, j.value, pre.value, post.value) if r else None
+
+    @property
+    def approx_reach(self):
+        """(back, ahead) over the approximate patterns: the largest length, the largest post"""
+        b, f = C.c_int32(), C.c_int32()
+        check(self.lib.acm_automaton_approx_reach(self.h, C.byref(b), C.byref(f)), "acm_automaton_approx_reach")
+        return b.value, f.value
+
     def add_rule(self, sequences, expr, iid=0):
         """A condition over the sequences that hit one text (acm_automaton_add_rule): sequences are the operands,
         sequence indices, expr e.g. "(0&1)|2>3" over their positions in that list.  Before or after compile(),
@@ -596,6 +634,17 @@ class _Pipeline:
                               workspace=ws)
         self._advance(pat, off, cells, _lib.REPORT_HEAD)
 
+    def approx(self, cells, info, lead_begin, dist=True):
+        """the approx pass over the current planes; returns the distance plane (None without dist)"""
+        ws = self.workspace(self.m.lib.acm_approx_workspace_bytes, self.max_records)
+        pat, off = self.planes(cells)
+        d = self.alloc(cells * 4) if dist else None
+        self.m.approx_async(self.pat, self.off, self.max_records, self.d, 0, self.n, pat, off, cells, info, dist_out=d,
+                            report=self.report, before=self.d_bf, before_len=self.before_len, seg_start=self.d_st,
+                            segments=self.nseg, lead_begin=lead_begin, open_end=self.n, workspace=ws)
+        self._advance(pat, off, cells, _lib.REPORT_HEAD)
+        return d
+
     def position(self, cells, info, all_patterns, lead_begin, open_end, ws=None):
         ws = ws or self.workspace(self.m.lib.acm_position_workspace_bytes, self.max_records)
         pat, off = self.planes(cells)
@@ -720,6 +769,15 @@ class Matcher:
         # post context of every sequence's last part: a match ends that far behind the offset the sequence pass reports
         self.seq_post = np.array([automaton.wildcard_lengths(automaton.sequence(q)[0][-1])[1]
                                   for q in range(automaton.num_sequences)] if self.wild else [], dtype=np.int64)
+        # per pattern, for scan_approx: the first piece of the approximate pattern it is a piece of (else itself), and
+        # how far behind a piece's end the match ends
+        self.approx_first = np.arange(self.num_patterns, dtype=np.int32)
+        self.approx_post = np.zeros(self.num_patterns, dtype=np.int64)
+        for x in range(automaton.num_approx):
+            first, b, k = automaton.approx(x)[:3]
+            for j in range(k + 1):
+                self.approx_first[first + j] = first
+                self.approx_post[first + j] = automaton.pattern_approx(first + j)[3]
         self.max_text = 0
         self.ws = self.pat_plane = self.off_plane = None
         self.reserve(max_text, plane_capacity)
@@ -1102,6 +1160,41 @@ class Matcher:
                 p.position(m + 2, p.alloc(16), False, -p.before_len, p.n)
                 m = p.count()
             return p.download(m) + (und,)
+
+    def approx_async(self, pat_plane, off_plane, max_records, d_text, text_origin, text_end, pat_out, off_out,
+                     out_capacity, info, dist_out=None, report=0, before=None, before_len=0, seg_start=None, segments=0,
+                     lead_begin=0, open_end=-1, workspace=None, stream=None):
+        """Enqueue the approx pass (acm_approx_matches_async) over caller-owned device planes: states
+        (report=REPORT_STATE) or pattern indices (REPORT_HEAD).  An entry that is a piece of an approximate pattern
+        (Automaton.add_approx) is kept where the whole pattern lies within its budget and no piece in front of this
+        one is exact; every other entry is kept.  dist_out: None, or a third plane for the distances.  info: device
+        int32[4].  workspace: (ptr, nbytes), or None for a temporary one that lives until the stream has passed it
+        (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        with self._workspace(workspace, st, self.lib.acm_approx_workspace_bytes, max_records) as (ws, nb):
+            check(self.lib.acm_approx_matches_async(
+                self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, report, _ptr(d_text), text_origin, text_end,
+                _ptr(before), before_len, _ptr(seg_start), segments, lead_begin, open_end, _ptr(pat_out), _ptr(off_out),
+                _ptr(dist_out), out_capacity, _ptr(info), _ptr(ws), nb, st), "acm_approx_matches_async")
+
+    def scan_approx(self, text=None, texts=None, before=b"", init_state=0, out_capacity=None):
+        """Matches of an automaton with approximate patterns (Automaton.add_approx): a REPORT_STATE scan, the
+        segment pass when texts is given (each text matched alone), then the approx pass
+        (acm_approx_matches_async).  text: host bytes; or None with texts: a list of bytes-like objects or a
+        (uint8 array, int32 starts) pair.  before: the bytes in front of text, part of the same text.  The text
+        ends with the bytes given.  Returns (pattern, end, dist, undecided) in record order: pattern is the index
+        of an approximate pattern's FIRST piece, or a plain pattern's own; end the offset of the match's last
+        byte (int64); dist the mismatches; undecided the candidates whose span left the bytes given."""
+        with _Pipeline(self, "Matcher.scan_approx", text, texts, before=before) as p:
+            ocap = out_capacity if out_capacity is not None else 8 * p.cap
+            info = p.alloc(16)
+            p.scan(init_state)
+            if p.nseg:
+                p.segment()
+            d = p.approx(ocap, info, -p.before_len)
+            off, pat, _, dist = p.download(p.count(), d)
+            und = int(info.to_numpy(np.int32, 4, stream=self.stream)[0])
+            return self.approx_first[pat], off.astype(np.int64) + self.approx_post[pat], dist, und
 
     def sequence_async(self, pat_plane, off_plane, max_records, seq_out, off_out, out_capacity, info, seg_start=None,
                        segments=0, lead_begin=0, text_end=0, workspace=None, stream=None):

@@ -59,7 +59,7 @@ double now_us()
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
 	       "             [-w cpu_threads] [-R max] [-I file] [-P file] [-tvxFMAiSWcno]\n"
-	       "             [-r file -O dir] [-C N[,M] -T dir [-V]]\n"
+	       "             [-r file -O dir] [-C N[,M] -T dir [-V]] [-k N]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -183,6 +183,18 @@ double now_us()
 	       "                 group pass and the extract, all on the device; -H -N -b together print name:line:offset:.  The\n"
 	       "                 output buffer is sized for lines of four bytes or more on average; a buffer whose output does\n"
 	       "                 not fit is an error that says so (extensions; they work with -V; each needs -C and -T)\n"
+	       "  -k N           approximate matching, 1 <= N <= 15: every pattern of -p and -I that has at least 3 * (N + 1) bytes\n"
+	       "                 after -x and -m also matches where up to N of its bytes are other bytes (substitutions only: the\n"
+	       "                 match has the pattern's length).  Such a pattern is cut into N + 1 pieces of 3 bytes or more; the\n"
+	       "                 pieces are matched by the automaton and the mismatches counted on the device where a piece\n"
+	       "                 matched.  Shorter patterns stay exact; their number is a NOTE on stderr.  Every pattern that ends\n"
+	       "                 at an offset is reported, as with -A.  The -v line names the pattern as written and the offset its\n"
+	       "                 whole span ends at, the number a run without -k prints for an exact match, and ends in\n"
+	       "                 ' mismatches <d>'.  A line is printed where the piece that found the match ends: the lines of one\n"
+	       "                 buffer may come out of offset order by up to the length of the longest pattern.  The pass is\n"
+	       "                 given the tail of the buffer in front; a candidate whose span reaches behind the buffer's end is\n"
+	       "                 not decided: such candidates are counted and reported on stderr at exit.  Composes with -i, -I,\n"
+	       "                 -S and -t (extension; not with -W, -P, -Q, -K, -E, -o, -r, -c, -n, -C or -F)\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -239,6 +251,7 @@ struct Config {
 	int ext = 0;             // -E: the signatures of -Q and the bodies of -K are read in the extended syntax
 	int rules = 0;           // -K: the sequence pass's records go through the rule pass; its records are reported (seq is set too)
 	int wild = 0;            // -E and some part has a context: the parts' records go through the wildcard pass
+	int approx = 0;          // -k N: the budget; every pattern's records go through the approx pass (all_patterns is set too)
 	int only = 0;            // -o: every pattern of the records goes through the select pass (all_patterns is set too)
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
@@ -255,6 +268,8 @@ struct Shared {
 	std::vector<int> seq_iid;             // -Q: the id of every sequence, for the -v line
 	std::vector<int> seq_post;            // -E: the post context of every sequence's last part: a match ends that far behind its record
 	std::vector<int> rule_iid;            // -K: the id of every rule, for the -v line
+	std::vector<int> apx_post;            // -k: per pattern, how far behind a piece's end its whole pattern ends (a plain pattern: 0)
+	int apx_back = 0;                     // -k: the longest approximate pattern: the tail of its stream a worker keeps
 	std::vector<std::string> out_paths;   // -r: where every input file's rewrite goes
 	std::vector<char> out_begun;          // -r: the file has been created in this run (a file belongs to one worker)
 	int max_pattern_len = 0;
@@ -304,6 +319,11 @@ struct Buffer {   // one of the two staging buffers of a worker
 	void *d_wild_pat = nullptr, *d_wild_off = nullptr, *d_wild_ws = nullptr, *d_wild_info = nullptr;
 	int32_t *h_wild_info = nullptr;
 	size_t wild_ws_bytes = 0;
+	// -k only: the approx pass's planes (patterns, offsets, distances), workspace and info (pinned twin: [0] = undecided
+	// entries); the distances go through the buckets into d_results3 as the lines of -n do
+	void *d_apx_pat = nullptr, *d_apx_off = nullptr, *d_apx_dist = nullptr, *d_apx_ws = nullptr, *d_apx_info = nullptr;
+	int32_t *h_apx_info = nullptr;
+	size_t apx_ws_bytes = 0;
 	// -o only: the select pass's planes, workspace and info (pinned twin: [1] = entries that began in front of the buffer)
 	void *d_sel_pat = nullptr, *d_sel_off = nullptr, *d_sel_ws = nullptr, *d_sel_info = nullptr;
 	int32_t *h_sel_info = nullptr;
@@ -374,6 +394,10 @@ struct Worker {
 	bool file_closed = false; // -P: the file of the last chunk filled has been read to its end
 	uint64_t undecided = 0;   // -P: end-anchored entries dropped because their text went on in the next buffer
 	uint64_t wild_undecided = 0;   // -E: candidates whose positions reach over a buffer border
+	uint64_t apx_undecided = 0;    // -k: candidates whose span reaches behind a buffer's end
+	void *d_atail[2] = { nullptr, nullptr };   // -k: the last apx_back bytes of the stream so far, ping-pong
+	int atail_cur = 0;
+	size_t atail_len = 0;
 	uint64_t cut_texts = 0;   // -K: texts that go on in the next buffer: not evaluated
 	uint64_t sel_dropped = 0; // -o: entries that began in the buffer in front: no candidates
 	long file_pos = 0;        // -K: bytes of the file being read that the buffers filled so far hold
@@ -483,6 +507,19 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 		CK(acm_rt_malloc(&b.d_pat_all, b.all_cap * 4));
 		CK(acm_rt_malloc(&b.d_off_all, b.all_cap * 4));
 		CK(acm_rt_malloc(&b.d_expand_ws, b.expand_ws_bytes));
+	}
+	if (c.approx) {   // (no more kept entries than entries: the planes in front hold all_cap cells)
+		b.apx_ws_bytes = acm_approx_workspace_bytes(b.all_cap);
+		CK(acm_rt_malloc(&b.d_apx_pat, b.all_cap * 4));
+		CK(acm_rt_malloc(&b.d_apx_off, b.all_cap * 4));
+		CK(acm_rt_malloc(&b.d_apx_dist, b.all_cap * 4));
+		CK(acm_rt_malloc(&b.d_apx_ws, b.apx_ws_bytes));
+		CK(acm_rt_malloc(&b.d_apx_info, 16));
+		CK(acm_rt_host_alloc((void **)&b.h_apx_info, 64));
+		b.h_apx_info[0] = 0;
+		CK(acm_rt_malloc(&b.d_results3, plane));
+		CK(acm_rt_malloc(&b.d_results3_off, plane));
+		CK(acm_rt_host_alloc((void **)&b.h_results3, plane));
 	}
 	if (c.only) {   // (the planes in front hold all_cap cells, the position pass's as many)
 		b.sel_ws_bytes = acm_select_workspace_bytes(b.all_cap - 2);
@@ -719,7 +756,7 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 	sb.report = states ? ACM_REPORT_STATE : ACM_REPORT_HEAD;
 	if (c.segmented && !b.seg_starts.empty())
 		CK(acm_rt_memcpy_h2d(b.d_seg_start, b.seg_starts.data(), b.seg_starts.size() * 4, s));
-	if ((c.pos || c.wild) && c.segmented && b.end_known) {   // a start at the stream's end, for the position and wildcard passes alone: the last text is closed
+	if ((c.pos || c.wild || c.approx) && c.segmented && b.end_known) {   // a start at the stream's end, for the position, wildcard and approx passes alone: the last text is closed
 		b.end_start = (int32_t)b.stream_len;
 		CK(acm_rt_memcpy_h2d((int32_t *)b.d_seg_start + b.seg_starts.size(), &b.end_start, 4, s));
 	}
@@ -788,6 +825,31 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		off = (int32_t *)b.d_off_all;
 		cap = b.all_cap;
 		CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
+	}
+	if (c.approx) {
+		// the mismatches of every piece's whole pattern, each in its own text.  The planes hold every pattern (the
+		// expansion's, or the case pass's); the tail of the worker's stream so far is this buffer's before: a span
+		// that began in the buffer in front is compared whole, one that reaches behind this buffer's end is
+		// undecided and counted.
+		const size_t nseg = c.segmented ? b.seg_starts.size() + (b.end_known ? 1 : 0) : 0;
+		CK(acm_approx_matches_async(w.dfa, pat, off, cap - 2, ACM_REPORT_HEAD, b.text, 0, (long)b.stream_len,
+		    w.atail_len ? w.d_atail[w.atail_cur] : nullptr, w.atail_len, nseg ? (const int32_t *)b.d_seg_start : nullptr, nseg,
+		    c.segmented ? b.lead_begin : -(1L << 40), b.last_of_input ? (long)b.stream_len : -1L, (int32_t *)b.d_apx_pat,
+		    (int32_t *)b.d_apx_off, (int32_t *)b.d_apx_dist, b.all_cap, (int32_t *)b.d_apx_info, b.d_apx_ws, b.apx_ws_bytes, s));
+		// the next buffer's before: the last apx_back bytes of the old tail and this stream
+		const size_t keep = std::min((size_t)w.sh->apx_back, w.atail_len + b.stream_len);
+		const size_t from_text = std::min(keep, b.stream_len), from_old = keep - from_text;
+		char *next_tail = (char *)w.d_atail[w.atail_cur ^ 1];
+		if (from_old)
+			CK(acm_rt_memcpy_d2d(next_tail, (const char *)w.d_atail[w.atail_cur] + (w.atail_len - from_old), from_old, s));
+		if (from_text)
+			CK(acm_rt_memcpy_d2d(next_tail + from_old, (const char *)b.text + (b.stream_len - from_text), from_text, s));
+		w.atail_cur ^= 1;
+		w.atail_len = keep;
+		pat = (int32_t *)b.d_apx_pat;
+		off = (int32_t *)b.d_apx_off;
+		cap = b.all_cap;
+		CK(acm_rt_memcpy_d2h(b.h_apx_info, b.d_apx_info, 16, s));
 	}
 	bool wild_ran = false;
 	if (c.wild) {
@@ -972,6 +1034,11 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		    c.max_results, (int32_t *)b.d_results3, (int32_t *)b.d_results3_off, cap, s));
 		CK(acm_rt_memcpy_d2h(b.h_results3, b.d_results3, cells * 4, s));
 	}
+	if (c.approx) {   // the distance plane through the same buckets: cell for cell where the pattern plane's cells went
+		CK(acm_bucketize((const int32_t *)b.d_apx_dist, off, (const int32_t *)b.d_indices, (const int32_t *)b.d_sizes, chunks,
+		    c.max_results, (int32_t *)b.d_results3, (int32_t *)b.d_results3_off, cap, s));
+		CK(acm_rt_memcpy_d2h(b.h_results3, b.d_results3, cells * 4, s));
+	}
 	CK(acm_rt_memcpy_d2h(b.h_results, b.d_results, cells * 4, s));
 	CK(acm_rt_memcpy_d2h(b.h_results2, b.d_results2, cells * 4, s));
 	if (!b.done)
@@ -1105,6 +1172,8 @@ void collect(Worker &w, Buffer &b)
 		w.undecided += (uint64_t)b.h_pos_info[0];
 	if (c.wild)
 		w.wild_undecided += (uint64_t)b.h_wild_info[0];
+	if (c.approx)
+		w.apx_undecided += (uint64_t)b.h_apx_info[0];
 	if (c.only)
 		w.sel_dropped += (uint64_t)b.h_sel_info[1];
 	if (c.rewrite)
@@ -1145,6 +1214,8 @@ void collect(Worker &w, Buffer &b)
 			int off = b.h_results2[(size_t)(j + 1) * chunks + i] + 1;  // end + 1 (databuf.c:771)
 			if (c.wild)   // the record is the end of the last part's anchor: the match ends its post context behind
 				off += w.sh->seq_post[p_idx];
+			if (c.approx)   // the record is the end of the piece that found the match: the pattern ends its post behind
+				off += w.sh->apx_post[p_idx];
 			w.reported++;
 			if (!c.verbose)
 				continue;
@@ -1160,6 +1231,10 @@ void collect(Worker &w, Buffer &b)
 				printf("Pattern %d ('%s') found in file '%s' at line %lu offset %d [relative: %d]\n",
 				    w.sh->pat_iid[p_idx], w.sh->pat_bytes[p_idx].c_str(),
 				    w.sh->files[b.file_ids[i]].c_str(), (unsigned long)line, off, off - b.h_indices[i]);
+			} else if (c.approx) {
+				printf("Pattern %d ('%s') found in file '%s' at offset %d [relative: %d] mismatches %d\n",
+				    w.sh->pat_iid[p_idx], w.sh->pat_bytes[p_idx].c_str(),
+				    w.sh->files[b.file_ids[i]].c_str(), off, off - b.h_indices[i], b.h_results3[(size_t)(j + 1) * chunks + i]);
 			} else {
 				printf("Pattern %d ('%s') found in file '%s' at offset %d [relative: %d]\n",
 				    w.sh->pat_iid[p_idx], w.sh->pat_bytes[p_idx].c_str(),
@@ -1233,6 +1308,9 @@ void *worker_main(void *arg)
 	if (c.words || c.cased)
 		for (void *&t : w.d_tail)
 			CK(acm_rt_malloc(&t, (size_t)sh.max_pattern_len + 16));
+	if (c.approx)
+		for (void *&t : w.d_atail)
+			CK(acm_rt_malloc(&t, (size_t)sh.apx_back + 16));
 	const size_t npat = sh.pat_iid.size();
 	if (c.count) {
 		w.file_total.assign(sh.files.size(), 0);
@@ -1351,7 +1429,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xor:O:C:VT:HNb")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o, r, O, C, V, T, H, N, b
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xor:O:C:VT:HNbk:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o, r, O, C, V, T, H, N, b, k
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -1409,6 +1487,13 @@ int main(int argc, char **argv)
 		case 'H': c.fmt_name = 1; break;
 		case 'N': c.fmt_num = 1; break;
 		case 'b': c.fmt_off = 1; break;
+		case 'k': {   // decimal digits only; 0 and junk are refused below
+			const std::string v = optarg;
+			c.approx = !v.empty() && v.size() <= 2 && v.find_first_not_of("0123456789") == std::string::npos ? atoi(v.c_str()) : -1;
+			if (c.approx == 0)
+				c.approx = -1;
+			break;
+		}
 		default: usage();
 		}
 	}
@@ -1540,8 +1625,33 @@ int main(int argc, char **argv)
 		err++;
 	}
 	c.extract = c.ctx == 1 && !c.ext_dir.empty();
+	if (c.approx < 0 || c.approx > ACM_APPROX_MAX_K) {
+		printf("ERROR: -k takes 1 to %d: the bytes of a pattern that may be other bytes\n", ACM_APPROX_MAX_K);
+		err++;
+	} else if (c.approx) {
+		const struct { bool on; const char *opt, *why; } refused[] = {
+			{ c.words != 0, "-W", "the word pass looks at the bytes next to a piece, not next to the match" },
+			{ !c.pos_path.empty(), "-P", "a window would count from a piece's start, not from the match's" },
+			{ !c.seq_path.empty(), "-Q", "a part of a signature is matched exactly" },
+			{ c.rules != 0, "-K", "the bodies of a rule are matched exactly" },
+			{ c.ext != 0, "-E", "it is the syntax of the signature file" },
+			{ c.only != 0 && c.repl_path.empty() && c.out_dir.empty(), "-o", "the select pass would take a piece for the match" },
+			{ !c.repl_path.empty() || !c.out_dir.empty(), "-r", "the rewrite would replace a piece, not the match" },
+			{ c.count != 0, "-c", "the tallies would count pieces" },
+			{ c.lineno != 0, "-n", "the line would be that of the piece's end, not of the match's" },
+			{ c.ctx != 0 || c.invert || !c.ext_dir.empty(), "-C", "the lines would be those of the pieces' ends" },
+			{ c.follow != 0, "-F", "the bytes behind a paused input are not known" },
+		};
+		for (const auto &r : refused)
+			if (r.on) {
+				printf("ERROR: -k cannot be combined with %s: %s\n", r.opt, r.why);
+				err++;
+			}
+	}
 	if (err)
 		usage();
+	if (c.approx)   // the approx pass takes every pattern of every record: the planes -A would have printed
+		c.all_patterns = 1;
 	if (c.only)   // the select pass takes every pattern of every record: the planes -A would have printed
 		c.all_patterns = 1;
 	auto align16 = [](long &v, const char *what) {   // align_parameters, ocl_aho_grep.c:316-346
@@ -1597,14 +1707,34 @@ int main(int argc, char **argv)
 	// one automaton, one copy per device, shared by the workers of that device
 	acm_automaton *aut = acm_automaton_new();
 	CK(acm_automaton_set_nocase(aut, c.nocase));
-	if (!c.pat_path.empty() && acm_automaton_load_file(aut, c.pat_path.c_str(), c.hex, c.pat_limit) < 0) {
+	// -k: the files are read into an automaton of their own, and every pattern is added from there: with a budget
+	// where it is long enough for pieces of three bytes, as it is where not
+	acm_automaton *read_into = c.approx ? acm_automaton_new() : aut;
+	if (!c.pat_path.empty() && acm_automaton_load_file(read_into, c.pat_path.c_str(), c.hex, c.pat_limit) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
 	}
 	if (!c.loose_path.empty() &&
-	    acm_automaton_load_file_ex(aut, c.loose_path.c_str(), c.hex, c.pat_limit, ACM_PATTERN_NOCASE) < 0) {
+	    acm_automaton_load_file_ex(read_into, c.loose_path.c_str(), c.hex, c.pat_limit, ACM_PATTERN_NOCASE) < 0) {
 		fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 		return 1;
+	}
+	if (c.approx) {
+		int exact = 0;
+		for (int i = 0; i < acm_automaton_num_patterns(read_into); i++) {
+			int iid = 0, n = 0;
+			const unsigned char *bytes = nullptr;
+			acm_automaton_pattern(read_into, i, &iid, &n, &bytes, nullptr);
+			const bool tolerant = n >= 3 * (c.approx + 1);
+			exact += !tolerant;
+			if (acm_automaton_add_approx(aut, bytes, n, tolerant ? c.approx : 0, iid, (unsigned)acm_automaton_pattern_flags(read_into, i)) < 0) {
+				fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
+				return 1;
+			}
+		}
+		acm_automaton_free(read_into);
+		if (exact)
+			fprintf(stderr, "NOTE: %d patterns have fewer than %d bytes and stay exact under -k %d\n", exact, 3 * (c.approx + 1), c.approx);
 	}
 	const unsigned syntax = c.ext ? (c.grp ? ACM_SIG_EXTENDED | ACM_SIG_GROUPS : ACM_SIG_EXTENDED) : 0;
 	if (!c.seq_path.empty() && acm_automaton_load_signature_file_ex(aut, c.seq_path.c_str(), 0, syntax) < 0) {
@@ -1686,9 +1816,14 @@ int main(int argc, char **argv)
 		int iid = 0, n = 0;
 		const unsigned char *bytes = nullptr;
 		acm_automaton_pattern(aut, i, &iid, &n, &bytes, nullptr);
+		int x = -1, post = 0;
+		if (acm_automaton_pattern_approx(aut, i, &x, nullptr, nullptr, &post) == 1)   // a piece: the -v line names its whole pattern
+			acm_automaton_approx(aut, x, nullptr, &n, nullptr, nullptr, nullptr, &bytes);
 		sh.pat_iid.push_back(iid);
 		sh.pat_bytes.emplace_back((const char *)bytes, (size_t)n);
+		sh.apx_post.push_back(post);
 	}
+	acm_automaton_approx_reach(aut, &sh.apx_back, nullptr);
 	for (int dev : c.devs) {
 		acm_dfa *dfa = nullptr;
 		if (acm_dfa_upload(aut, dev, &dfa) != ACM_OK) {
@@ -1717,11 +1852,12 @@ int main(int argc, char **argv)
 	pthread_barrier_wait(&sh.ready);
 	const double t0 = now_us();
 	size_t matches = 0, reported = 0, bytes = 0, lines = 0, rounds = 0;
-	uint64_t undecided = 0, wild_undecided = 0, cut_texts = 0, sel_dropped = 0;
+	uint64_t undecided = 0, wild_undecided = 0, cut_texts = 0, sel_dropped = 0, apx_undecided = 0;
 	for (auto &w : workers) {
 		pthread_join(w.thread, nullptr);
 		undecided += w.undecided;
 		wild_undecided += w.wild_undecided;
+		apx_undecided += w.apx_undecided;
 		cut_texts += w.cut_texts;
 		sel_dropped += w.sel_dropped;
 		matches += w.matches;
@@ -1769,6 +1905,9 @@ int main(int argc, char **argv)
 	if (wild_undecided)   // no silent loss: a signature cut by a buffer border is not found, and here that is known
 		fprintf(stderr, "NOTE: %lu wildcard candidates reach over a buffer border and were not decided (raise -B/-G)\n",
 		    (unsigned long)wild_undecided);
+	if (apx_undecided)   // no silent loss: a match cut by a buffer's end is not found, and here that is known
+		fprintf(stderr, "NOTE: %lu approximate candidates reach behind a buffer's end and were not decided (raise -B/-G)\n",
+		    (unsigned long)apx_undecided);
 	if (cut_texts)   // no silent loss: the rules of these texts were not evaluated
 		fprintf(stderr, "NOTE: %lu texts are cut by a buffer border and their rules were not evaluated (use a larger -G/-B)\n",
 		    (unsigned long)cut_texts);

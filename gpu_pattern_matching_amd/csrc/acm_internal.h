@@ -97,7 +97,19 @@ struct acm_automaton {
 		// (rewrite.hip)
 		int repl_kind = acm::kReplNone;
 		std::vector<unsigned char> repl;       // kReplBytes: the bytes (none: delete); kReplFill: the one fill byte
+		// a piece of an approximate pattern (acm_automaton_add_approx): which one in acm_automaton::approx, and
+		// which of its k + 1 pieces; -1: a pattern of its own
+		int32_t approx = -1, approx_piece = 0;
 	};
+	// approximate patterns (acm_automaton_add_approx): the whole pattern as added; its pieces are the patterns
+	// [first_piece, first_piece + k].  compile never reads these: acm_dfa_upload copies them for the approx pass
+	// (approx.hip)
+	struct Approx {
+		int first_piece, n, k, iid;
+		unsigned flags;
+		std::vector<unsigned char> bytes;
+	};
+	std::vector<Approx> approx;
 	// the distinct context sets of two or more bytes, interned: at most 256
 	std::vector<std::array<uint8_t, 32>> wild_classes;
 	// ordered multi-part signatures (acm_automaton_add_sequence).  compile never reads these:

@@ -1504,6 +1504,101 @@ extern "C" int acm_automaton_wildcard_reach(const acm_automaton *a, int *back, i
 	return ACM_OK;
 }
 
+// ---- approximate patterns ------------------------------------------------------
+
+// where piece i of an approximate pattern of n bytes and budget k begins (i == k + 1: n)
+static int approx_piece_begin(int n, int k, int i)
+{
+	const int q = n / (k + 1), r = n % (k + 1);
+	return i * q + std::min(i, r);
+}
+
+extern "C" int acm_automaton_add_approx(acm_automaton *a, const unsigned char *bytes, int n, int k, int iid, unsigned flags)
+{
+	if (!a || n < 0 || (n > 0 && !bytes) || k < 0)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_approx: bad arguments");
+	if (flags & ~(unsigned)ACM_PATTERN_NOCASE)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_approx: unknown flag bits 0x%x", flags & ~(unsigned)ACM_PATTERN_NOCASE);
+	if (a->compiled)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_approx: automaton already compiled");
+	if (k > ACM_APPROX_MAX_K)
+		return acm::fail(ACM_ERR_LIMIT, "acm_automaton_add_approx: budget %d, at most %d", k, ACM_APPROX_MAX_K);
+	const int index = (int)a->patterns.size();
+	if (k == 0) {
+		const int rc = acm_automaton_add_ex(a, bytes, n, iid, flags);
+		return rc != ACM_OK ? rc : index;
+	}
+	if (n < k + 1)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_approx: %d bytes cannot be cut into %d pieces", n, k + 1);
+	if (n > ACM_APPROX_MAX_LEN)
+		return acm::fail(ACM_ERR_LIMIT, "acm_automaton_add_approx: %d bytes, at most %d", n, ACM_APPROX_MAX_LEN);
+	acm_automaton::Approx x;
+	x.first_piece = index;
+	x.n = n;
+	x.k = k;
+	x.iid = iid;
+	x.flags = flags;
+	x.bytes.assign(bytes, bytes + n);
+	a->patterns.reserve(a->patterns.size() + (size_t)k + 1);   // (nothing is applied when memory runs out half way)
+	a->approx.reserve(a->approx.size() + 1);
+	for (int i = 0; i <= k; i++) {
+		const int b = approx_piece_begin(n, k, i), e = approx_piece_begin(n, k, i + 1);
+		if (int rc = acm_automaton_add_ex(a, bytes + b, e - b, iid, flags)) {   // (every check it makes was made above)
+			a->patterns.resize((size_t)index);
+			return rc;
+		}
+		a->patterns.back().approx = (int32_t)a->approx.size();
+		a->patterns.back().approx_piece = i;
+	}
+	a->approx.push_back(std::move(x));
+	return index;
+}
+
+extern "C" int acm_automaton_num_approx(const acm_automaton *a) { return a ? (int)a->approx.size() : 0; }
+
+extern "C" int acm_automaton_approx(const acm_automaton *a, int x, int *first_piece, int *n, int *k, int *iid, unsigned *flags,
+    const unsigned char **bytes)
+{
+	if (!a || x < 0 || x >= (int)a->approx.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_approx: index out of range");
+	const acm_automaton::Approx &p = a->approx[x];
+	if (first_piece) *first_piece = p.first_piece;
+	if (n) *n = p.n;
+	if (k) *k = p.k;
+	if (iid) *iid = p.iid;
+	if (flags) *flags = p.flags;
+	if (bytes) *bytes = p.bytes.data();
+	return ACM_OK;
+}
+
+extern "C" int acm_automaton_pattern_approx(const acm_automaton *a, int index, int *x, int *piece, int *pre, int *post)
+{
+	if (!a || index < 0 || index >= (int)a->patterns.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_pattern_approx: index out of range");
+	const acm_automaton::Pattern &p = a->patterns[index];
+	const bool is = p.approx >= 0;
+	const acm_automaton::Approx *q = is ? &a->approx[p.approx] : nullptr;
+	if (x) *x = p.approx;
+	if (piece) *piece = is ? p.approx_piece : 0;
+	if (pre) *pre = is ? approx_piece_begin(q->n, q->k, p.approx_piece) : 0;
+	if (post) *post = is ? q->n - approx_piece_begin(q->n, q->k, p.approx_piece + 1) : 0;
+	return is ? 1 : 0;
+}
+
+extern "C" int acm_automaton_approx_reach(const acm_automaton *a, int *back, int *ahead)
+{
+	if (!a)
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_approx_reach: null automaton");
+	int b = 0, f = 0;
+	for (auto &p : a->approx) {
+		b = std::max(b, p.n);
+		f = std::max(f, p.n - approx_piece_begin(p.n, p.k, 1));   // (piece 0 has the most behind it)
+	}
+	if (back) *back = b;
+	if (ahead) *ahead = f;
+	return ACM_OK;
+}
+
 // ---- pattern file ------------------------------------------------------------
 
 // "[+-]?digits" followed by a blank => the file is "ID pattern" per line.

@@ -152,4 +152,11 @@ struct acm_dfa {
 	bool replacements = false;
 	int32_t *d_repl_ent = nullptr;       // [patterns][4] {acm::ReplKind, bytes of the replacement, where they begin in d_repl_blob, the fill byte}
 	uint8_t *d_repl_blob = nullptr;      // the replacements' bytes, back to back
+
+	// an automaton with approximate patterns only (acm_automaton_num_approx at upload), for the approx pass
+	// (approx.hip); null otherwise: every entry is then kept with distance 0
+	bool approx = false;
+	int32_t *d_approx_ent = nullptr;     // [patterns][4] {word index of the whole pattern in d_approx_pool, or -1: not a piece; n;
+	                                     // k | piece << 8 | folds << 16; 0}: one 16-byte load per entry
+	uint32_t *d_approx_pool = nullptr;   // the approximate patterns' bytes (folded for one that folds), each padded to whole words, one spare word behind
 };

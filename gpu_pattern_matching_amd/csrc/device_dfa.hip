@@ -410,6 +410,38 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 			rc = upload(&d->d_repl_ent, ent.data(), ent.size(), &d->device_bytes);
 			if (rc == ACM_OK) rc = upload(&d->d_repl_blob, blob.data(), blob.size(), &d->device_bytes);
 		}
+		// an automaton with approximate patterns (acm_automaton_add_approx): per pattern whether it is a piece,
+		// and then of what; the whole patterns' bytes, folded where the compare folds (approx.hip).  Where piece i
+		// begins follows from n and k.  Allocations of their own, as above.
+		d->approx = !a->approx.empty();
+		if (rc == ACM_OK && d->approx) {
+			std::vector<int32_t> ent(4 * a->patterns.size(), 0);
+			std::vector<uint32_t> pool, where(a->approx.size());
+			for (size_t x = 0; x < a->approx.size(); x++) {
+				const acm_automaton::Approx &q = a->approx[x];
+				std::vector<unsigned char> b = q.bytes;
+				if ((q.flags & ACM_PATTERN_NOCASE) || a->want_nocase)
+					for (unsigned char &c : b)
+						c = (unsigned char)acm::fold_byte(c);
+				where[x] = (uint32_t)pool.size();
+				pool.resize(pool.size() + (b.size() + 3) / 4, 0);
+				memcpy(&pool[where[x]], b.data(), b.size());
+			}
+			pool.push_back(0);   // the word behind the last pattern: the compare loads one word ahead
+			for (size_t i = 0; i < a->patterns.size(); i++) {
+				const acm_automaton::Pattern &p = a->patterns[i];
+				ent[4 * i] = -1;
+				if (p.approx >= 0) {
+					const acm_automaton::Approx &q = a->approx[p.approx];
+					const bool folds = (q.flags & ACM_PATTERN_NOCASE) || a->want_nocase;
+					ent[4 * i] = (int32_t)where[p.approx];
+					ent[4 * i + 1] = q.n;
+					ent[4 * i + 2] = q.k | p.approx_piece << 8 | (folds ? 1 << 16 : 0);
+				}
+			}
+			rc = upload(&d->d_approx_ent, ent.data(), ent.size(), &d->device_bytes);
+			if (rc == ACM_OK) rc = upload(&d->d_approx_pool, pool.data(), pool.size(), &d->device_bytes);
+		}
 	} catch (const std::bad_alloc &) {
 		rc = acm::fail(ACM_ERR_NOMEM, "acm_dfa_upload: out of host memory");
 	}
@@ -482,6 +514,8 @@ extern "C" void acm_dfa_release(acm_dfa *d)
 		hipFree(d->d_grp_pool);
 		hipFree(d->d_repl_ent);
 		hipFree(d->d_repl_blob);
+		hipFree(d->d_approx_ent);
+		hipFree(d->d_approx_pool);
 		free_small(d, d->d_depth);
 		free_small(d, d->d_class);
 		free_small(d, d->d_sv_bloom);

@@ -1,5 +1,5 @@
 // The entry-filter layer on the record-pass core: what the passes that keep or drop match-list entries
-// (word.hip, case.hip, position.hip, wildcard.hip) share.  Internal to the library, gfx950 only.  DESIGN.md 6f.
+// (word.hip, case.hip, position.hip, wildcard.hip, approx.hip) share.  Internal to the library, gfx950 only.  DESIGN.md 6f.
 //
 // Such a pass reads the planes of a scan (a cell and an offset per record), walks the match list of every
 // record's state, keeps the entries a predicate of its own accepts and writes them in position order: the

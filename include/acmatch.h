@@ -350,6 +350,43 @@ int acm_automaton_add_signature_ex(acm_automaton *, const char *body, int iid, u
 int acm_automaton_load_signature_file_ex(acm_automaton *, const char *path, unsigned flags,
     unsigned syntax);
 
+/* Approximate patterns: up to k substituted bytes (Hamming distance).  An APPROXIMATE PATTERN is n bytes and a
+ * budget k, 0 <= k <= ACM_APPROX_MAX_K and k + 1 <= n <= ACM_APPROX_MAX_LEN.  It matches a span of n text bytes
+ * that differs from it in at most k positions.  It is cut into k + 1 PIECES that tile it: with q = n / (k + 1)
+ * and r = n % (k + 1), piece i (0 <= i <= k) covers the pattern bytes [b_i, e_i), b_i = i * q + min(i, r) and
+ * e_i = b_{i + 1}: the first r pieces are one byte longer.  A span within the budget holds at least one piece
+ * exactly, so only the pieces enter the automaton, as k + 1 consecutive patterns added with
+ * acm_automaton_add_ex(..., iid, flags); acm_approx_matches_async counts the mismatches where a piece matched.
+ * ACM_PATTERN_NOCASE is the only flag and makes the whole comparison fold ASCII case (a..z only: '@' and '`',
+ * '[' and '{' stay different bytes), as does acm_automaton_set_nocase for every pattern.  Approximate
+ * patterns do not enter acm_automaton_compile; acm_dfa_upload takes a copy.  An automaton without any is bit
+ * for bit what it is without this interface: tables, digests, self-tests and acm_dfa_device_bytes.
+ *   acm_automaton_add_approx      the index of piece 0 (>= 0), or an error (< 0).  With k == 0 it is exactly
+ *                                 acm_automaton_add_ex (any n that call takes; no approximate pattern is
+ *                                 recorded) and returns the new pattern's index.  ACM_ERR_ARG: a null pointer,
+ *                                 k < 0, n < k + 1, unknown flags, a compiled automaton; ACM_ERR_LIMIT: k or n
+ *                                 above the maxima.  On an error nothing is applied.
+ *   acm_automaton_num_approx      the number of approximate patterns (k >= 1)
+ *   acm_automaton_approx          approximate pattern x: the index of its piece 0, n, k, iid, flags and a borrowed
+ *                                 pointer to its n bytes as added (any pointer may be NULL)
+ *   acm_automaton_pattern_approx  1 if pattern `index` is a piece, else 0 (negative: a bad index): x, its piece
+ *                                 number j, pre = b_j and post = n - e_j (x = -1 and zeros for a plain pattern)
+ *   acm_automaton_approx_reach    back = the largest n, ahead = the largest post: what a streaming caller keeps
+ *                                 of the text in front, and how far behind a record a match can end.  Both 0
+ *                                 without approximate patterns.
+ * NOT composed: position windows, sequences, replacements, select and the word pass see a piece as the plain
+ * pattern it is (its own bytes, its own span).  Insertions and deletions are not provided: they change the
+ * span's length, which every table of this library takes as fixed. */
+#define ACM_APPROX_MAX_K 15
+#define ACM_APPROX_MAX_LEN 4096
+int acm_automaton_add_approx(acm_automaton *, const unsigned char *bytes, int n, int k, int iid,
+    unsigned flags);
+int acm_automaton_num_approx(const acm_automaton *);
+int acm_automaton_approx(const acm_automaton *, int x, int *first_piece, int *n, int *k, int *iid,
+    unsigned *flags, const unsigned char **bytes);
+int acm_automaton_pattern_approx(const acm_automaton *, int index, int *x, int *piece, int *pre, int *post);
+int acm_automaton_approx_reach(const acm_automaton *, int *back, int *ahead);
+
 /* Rules: a boolean condition over the signatures that hit ONE text.  A RULE is nops operands, 1 <= nops <=
  * ACM_RULE_MAX_OPERANDS, an expression over them and a user id iid.  Operand j is a SEQUENCE index: the id
  * space in which plain patterns (1-part sequences), multi-part signatures and wildcard signatures meet.  A
@@ -827,6 +864,48 @@ int acm_wildcard_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
     long text_end, const void *d_before, size_t before_len, const int32_t *d_seg_start,
     size_t segments, long lead_begin, long open_end, int all_patterns, int32_t *d_pat_out,
     int32_t *d_off_out, size_t out_capacity, int32_t *d_info, void *d_workspace,
+    size_t workspace_bytes, void *stream);
+
+/* Approximate patterns (acm_automaton_add_approx) confirmed on the device: where a piece matched, the
+ * mismatches of the whole pattern are counted.  A pass over the records: cost per record and per compared
+ * byte, never per text byte; no scan kernel is involved.
+ * Input, text bytes and texts exactly as acm_wildcard_matches_async takes them (report: ACM_REPORT_STATE, or
+ * ACM_REPORT_HEAD for pattern cells: a HEAD scan or the all-patterns output of the expand, case or position
+ * pass).  The pass always writes one record per kept entry: there is no first-entry form.
+ * The rule for entry (p, o) with L >= 1, int64 arithmetic, in this order:
+ *   1. p is no piece: kept, distance 0
+ *   2. p is piece j of pattern A (n bytes, budget k): a = o - L + 1, s = a - b_j, span [s, s + n).  The span
+ *      leaves [T0, Tend): dropped
+ *   3. the span leaves the bytes given, [text_origin - before_len, text_end): UNDECIDED -- dropped and counted,
+ *      whatever the available bytes hold
+ *   4. m_i = the mismatches of piece i against the text under it (raw bytes, or both sides folded if A folds):
+ *      kept iff m_j == 0, m_i > 0 for every i < j and the sum of all m_i <= k
+ * Rule 4 reports an occurrence within the budget exactly once, by its first exact piece, without a sort.  It
+ * stands on the text alone: a mixed automaton needs no case pass in front, and a pattern cell that names a
+ * piece where none matched is dropped.
+ * Output, the scan's cell layout and overflow contract ([0] = full count, records, trailer -- the input trailer
+ * unchanged -- at min(count + 1, out_capacity - 1)), per kept entry in list order (STATE) or input order (HEAD):
+ *   d_pat_out    p, the piece (acm_automaton_pattern_approx names its pattern)
+ *   d_off_out    o, unchanged: the order is the input's, and the match ends post bytes behind o
+ *   d_dist_out   NULL, or a third plane of out_capacity cells: the sum of the m_i in the record's cell; cell 0
+ *                and the trailer as in the other planes
+ *   d_info       int32[4], required, written whole: [0] undecided entries, [1..3] 0
+ * For an uploaded set without approximate patterns the call is legal: STATE input gives
+ * acm_expand_matches_async's output and HEAD input the input, bit for bit (entries of length 0 aside), with
+ * distances 0.  A cell that is neither a state nor a pattern index writes nothing.  No read leaves the input
+ * planes, the starts, [0, text_end - text_origin) of d_text, [0, before_len) of d_before and the library's
+ * tables, and no write leaves the outputs and the workspace, whatever the planes hold.  The outputs must not
+ * overlap the inputs.  Stream-ordered, no host sync, no allocation, no host read of device data; argument
+ * errors (a NULL plane, output or d_info, out_capacity < 2, an unknown report, a bad text window, open_end
+ * outside {-1} and [text_end, inf), segments without starts, a short workspace) return ACM_ERR_ARG before
+ * anything is enqueued.  Two launches (csrc/approx.hip).  The workspace query is monotone and a multiple of
+ * 256. */
+size_t acm_approx_workspace_bytes(size_t max_records);
+int acm_approx_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
+    const int32_t *d_off_plane, size_t max_records, int report, const void *d_text, long text_origin,
+    long text_end, const void *d_before, size_t before_len, const int32_t *d_seg_start,
+    size_t segments, long lead_begin, long open_end, int32_t *d_pat_out, int32_t *d_off_out,
+    int32_t *d_dist_out, size_t out_capacity, int32_t *d_info, void *d_workspace,
     size_t workspace_bytes, void *stream);
 
 /* Sequences (acm_automaton_add_sequence) joined on the device: the records of the parts in, one record
