@@ -121,6 +121,8 @@ NATIVE_API = {
     "acm_automaton_approx": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_uint), C.POINTER(_vp)]),
     "acm_automaton_pattern_approx": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p]),
     "acm_automaton_approx_reach": (C.c_int, [_vp, _i32p, _i32p]),
+    "acm_automaton_add_edit": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_uint]),
+    "acm_automaton_approx_mode": (C.c_int, [_vp, C.c_int]),
     "acm_automaton_load_signature_file_ex": (C.c_int, [_vp, C.c_char_p, C.c_uint, C.c_uint]),
     "acm_automaton_add_rule": (C.c_int, [_vp, _i32p, C.c_int, C.c_char_p, C.c_int]),
     "acm_automaton_num_rules": (C.c_int, [_vp]),
@@ -182,6 +184,10 @@ NATIVE_API = {
     "acm_approx_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_long, C.c_long, _vp, C.c_size_t,
                                            _vp, C.c_size_t, C.c_long, C.c_long, _vp, _vp, _vp, C.c_size_t, _vp, _vp,
                                            C.c_size_t, _vp]),
+    "acm_edit_workspace_bytes": (C.c_size_t, [_vp, C.c_size_t]),
+    "acm_edit_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, _vp, C.c_long, C.c_long, _vp, C.c_size_t,
+                                         _vp, C.c_size_t, C.c_long, C.c_long, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp,
+                                         C.c_size_t, _vp]),
     "acm_sequence_workspace_bytes": (C.c_size_t, [_vp, C.c_size_t]),
     "acm_sequence_matches_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_long, C.c_long, _vp, _vp,
                                              C.c_size_t, _vp, _vp, C.c_size_t, _vp]),

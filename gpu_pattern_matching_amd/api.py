@@ -371,6 +371,23 @@ class Automaton:
         check(self.lib.acm_automaton_approx_reach(self.h, C.byref(b), C.byref(f)), "acm_automaton_approx_reach")
         return b.value, f.value
 
+    def add_edit(self, pattern: bytes, k: int, iid: int = 0, nocase: bool = False):
+        """An edit pattern (acm_automaton_add_edit): matches where at most k bytes are substituted, inserted or
+        deleted, k <= 4.  Pieces, return value and errors as add_approx; k == 0 is a plain add.  The matches are
+        verified by Matcher.scan_edit."""
+        r = self.lib.acm_automaton_add_edit(self.h, bytes(pattern), len(pattern), k, iid,
+                                            _lib.PATTERN_NOCASE if nocase else 0)
+        if r < 0:
+            check(r, "acm_automaton_add_edit")
+        return r
+
+    def approx_mode(self, x):
+        """0 where approximate pattern x counts substitutions (add_approx), 1 where it is an edit pattern (add_edit)"""
+        r = self.lib.acm_automaton_approx_mode(self.h, x)
+        if r < 0:
+            check(r, "acm_automaton_approx_mode")
+        return r
+
     def add_rule(self, sequences, expr, iid=0):
         """A condition over the sequences that hit one text (acm_automaton_add_rule): sequences are the operands,
         sequence indices, expr e.g. "(0&1)|2>3" over their positions in that list.  Before or after compile(),
@@ -644,6 +661,16 @@ class _Pipeline:
                             segments=self.nseg, lead_begin=lead_begin, open_end=self.n, workspace=ws)
         self._advance(pat, off, cells, _lib.REPORT_HEAD)
         return d
+
+    def edit(self, cells, info, lead_begin):
+        """the edit pass over the current planes; returns the distance and the length plane"""
+        ws = self.workspace(self.m.lib.acm_edit_workspace_bytes, self.m.dfa, self.max_records)
+        pat, off, d, ln = self.planes(cells, 4)
+        self.m.edit_async(self.pat, self.off, self.max_records, self.d, 0, self.n, pat, off, cells, info, dist_out=d,
+                          len_out=ln, report=self.report, before=self.d_bf, before_len=self.before_len,
+                          seg_start=self.d_st, segments=self.nseg, lead_begin=lead_begin, open_end=self.n, workspace=ws)
+        self._advance(pat, off, cells, _lib.REPORT_HEAD)
+        return d, ln
 
     def position(self, cells, info, all_patterns, lead_begin, open_end, ws=None):
         ws = ws or self.workspace(self.m.lib.acm_position_workspace_bytes, self.max_records)
@@ -1195,6 +1222,44 @@ class Matcher:
             off, pat, _, dist = p.download(p.count(), d)
             und = int(info.to_numpy(np.int32, 4, stream=self.stream)[0])
             return self.approx_first[pat], off.astype(np.int64) + self.approx_post[pat], dist, und
+
+    def edit_async(self, pat_plane, off_plane, max_records, d_text, text_origin, text_end, pat_out, off_out,
+                   out_capacity, info, dist_out=None, len_out=None, report=0, before=None, before_len=0, seg_start=None,
+                   segments=0, lead_begin=0, open_end=-1, workspace=None, stream=None):
+        """Enqueue the edit pass (acm_edit_matches_async) over caller-owned device planes: states
+        (report=REPORT_STATE) or pattern indices (REPORT_HEAD).  A piece of an edit pattern (Automaton.add_edit)
+        becomes the nearest end within edit distance k and the shortest span that has it; plain and Hamming
+        entries become their normalised record.  The records are unique and ordered by (offset, pattern).
+        dist_out, len_out: None, or planes for the distances and the span lengths.  info: device int32[4].  The
+        pass orders max_records cells (times the longest match list for states): size it to the planes.
+        workspace: (ptr, nbytes), or None for a temporary one that lives until the stream has passed it (the call
+        then synchronises)."""
+        st = stream if stream is not None else self.stream
+        with self._workspace(workspace, st, self.lib.acm_edit_workspace_bytes, self.dfa, max_records) as (ws, nb):
+            check(self.lib.acm_edit_matches_async(
+                self.dfa, _ptr(pat_plane), _ptr(off_plane), max_records, report, _ptr(d_text), text_origin, text_end,
+                _ptr(before), before_len, _ptr(seg_start), segments, lead_begin, open_end, _ptr(pat_out), _ptr(off_out),
+                _ptr(dist_out), _ptr(len_out), out_capacity, _ptr(info), _ptr(ws), nb, st), "acm_edit_matches_async")
+
+    def scan_edit(self, text=None, texts=None, before=b"", init_state=0, out_capacity=None):
+        """Matches of an automaton with edit patterns (Automaton.add_edit): a REPORT_STATE scan, the segment pass
+        when texts is given (each text matched alone), then the edit pass (acm_edit_matches_async) over the records
+        the scan left.  Arguments as scan_approx.  Returns (pattern, end, dist, length, undecided), unique and
+        ordered by (end, pattern): pattern is the index of an approximate pattern's FIRST piece, or a plain
+        pattern's own; end the offset of the match's last byte (int64); dist the errors; length the bytes of the
+        shortest span with that distance that ends there; undecided the candidates whose window left the bytes
+        given."""
+        with _Pipeline(self, "Matcher.scan_edit", text, texts, before=before) as p:
+            info = p.alloc(16)
+            p.scan(init_state)
+            if p.nseg:
+                p.segment()
+            p.max_records = p.count()                  # the pass orders max_records cells: no more than there are
+            ocap = out_capacity if out_capacity is not None else 8 * p.max_records + 2
+            d, ln = p.edit(ocap, info, -p.before_len)
+            off, pat, _, dist, length = p.download(p.count(), d, ln)
+            und = int(info.to_numpy(np.int32, 4, stream=self.stream)[0])
+            return pat, off.astype(np.int64), dist, length, und
 
     def sequence_async(self, pat_plane, off_plane, max_records, seq_out, off_out, out_capacity, info, seg_start=None,
                        segments=0, lead_begin=0, text_end=0, workspace=None, stream=None):

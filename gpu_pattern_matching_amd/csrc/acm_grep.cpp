@@ -195,6 +195,14 @@ double now_us()
 	       "                 given the tail of the buffer in front; a candidate whose span reaches behind the buffer's end is\n"
 	       "                 not decided: such candidates are counted and reported on stderr at exit.  Composes with -i, -I,\n"
 	       "                 -S and -t (extension; not with -W, -P, -Q, -K, -E, -o, -r, -c, -n, -C or -F)\n"
+	       "  -e             with -k N, N <= 4: edit distance, agrep's -k.  The N errors may be inserted and deleted bytes as well\n"
+	       "                 as substituted ones, so a match may be up to N bytes shorter or longer than its pattern.  The same\n"
+	       "                 patterns are cut into the same pieces; where a piece matched, a banded dynamic program on the\n"
+	       "                 device finds the nearest end within N errors and the shortest span that has that distance.  A\n"
+	       "                 match is reported once per (pattern, end), in offset order, and its neighbouring ends within\n"
+	       "                 the budget are reported only where another piece chose them.  The -v line ends in\n"
+	       "                 ' edits <d> length <l>'.  Composes with and refuses what -k does, and with -c, which counts the\n"
+	       "                 unique records (extension)\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -251,6 +259,7 @@ struct Config {
 	int ext = 0;             // -E: the signatures of -Q and the bodies of -K are read in the extended syntax
 	int rules = 0;           // -K: the sequence pass's records go through the rule pass; its records are reported (seq is set too)
 	int wild = 0;            // -E and some part has a context: the parts' records go through the wildcard pass
+	int edit = 0;            // -e: the patterns of -k are edit patterns, verified by the edit pass in the approx pass's place
 	int approx = 0;          // -k N: the budget; every pattern's records go through the approx pass (all_patterns is set too)
 	int only = 0;            // -o: every pattern of the records goes through the select pass (all_patterns is set too)
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
@@ -321,7 +330,10 @@ struct Buffer {   // one of the two staging buffers of a worker
 	size_t wild_ws_bytes = 0;
 	// -k only: the approx pass's planes (patterns, offsets, distances), workspace and info (pinned twin: [0] = undecided
 	// entries); the distances go through the buckets into d_results3 as the lines of -n do
+	// -e: the edit pass in its place, with a length plane that goes through the buckets into d_results4
 	void *d_apx_pat = nullptr, *d_apx_off = nullptr, *d_apx_dist = nullptr, *d_apx_ws = nullptr, *d_apx_info = nullptr;
+	void *d_apx_len = nullptr, *d_results4 = nullptr;
+	int32_t *h_results4 = nullptr;
 	int32_t *h_apx_info = nullptr;
 	size_t apx_ws_bytes = 0;
 	// -o only: the select pass's planes, workspace and info (pinned twin: [1] = entries that began in front of the buffer)
@@ -509,11 +521,17 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 		CK(acm_rt_malloc(&b.d_expand_ws, b.expand_ws_bytes));
 	}
 	if (c.approx) {   // (no more kept entries than entries: the planes in front hold all_cap cells)
-		b.apx_ws_bytes = acm_approx_workspace_bytes(b.all_cap);
 		CK(acm_rt_malloc(&b.d_apx_pat, b.all_cap * 4));
 		CK(acm_rt_malloc(&b.d_apx_off, b.all_cap * 4));
 		CK(acm_rt_malloc(&b.d_apx_dist, b.all_cap * 4));
-		CK(acm_rt_malloc(&b.d_apx_ws, b.apx_ws_bytes));
+		if (c.edit) {   // (the workspace depends on the uploaded set: worker_main)
+			CK(acm_rt_malloc(&b.d_apx_len, b.all_cap * 4));
+			CK(acm_rt_malloc(&b.d_results4, plane));
+			CK(acm_rt_host_alloc((void **)&b.h_results4, plane));
+		} else {
+			b.apx_ws_bytes = acm_approx_workspace_bytes(b.all_cap);
+			CK(acm_rt_malloc(&b.d_apx_ws, b.apx_ws_bytes));
+		}
 		CK(acm_rt_malloc(&b.d_apx_info, 16));
 		CK(acm_rt_host_alloc((void **)&b.h_apx_info, 64));
 		b.h_apx_info[0] = 0;
@@ -832,10 +850,18 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		// that began in the buffer in front is compared whole, one that reaches behind this buffer's end is
 		// undecided and counted.
 		const size_t nseg = c.segmented ? b.seg_starts.size() + (b.end_known ? 1 : 0) : 0;
-		CK(acm_approx_matches_async(w.dfa, pat, off, cap - 2, ACM_REPORT_HEAD, b.text, 0, (long)b.stream_len,
-		    w.atail_len ? w.d_atail[w.atail_cur] : nullptr, w.atail_len, nseg ? (const int32_t *)b.d_seg_start : nullptr, nseg,
-		    c.segmented ? b.lead_begin : -(1L << 40), b.last_of_input ? (long)b.stream_len : -1L, (int32_t *)b.d_apx_pat,
-		    (int32_t *)b.d_apx_off, (int32_t *)b.d_apx_dist, b.all_cap, (int32_t *)b.d_apx_info, b.d_apx_ws, b.apx_ws_bytes, s));
+		// -e: the edit pass takes the same planes, bytes and texts, and leaves whole matches: unique, in offset order
+		if (c.edit)
+			CK(acm_edit_matches_async(w.dfa, pat, off, cap - 2, ACM_REPORT_HEAD, b.text, 0, (long)b.stream_len,
+			    w.atail_len ? w.d_atail[w.atail_cur] : nullptr, w.atail_len, nseg ? (const int32_t *)b.d_seg_start : nullptr, nseg,
+			    c.segmented ? b.lead_begin : -(1L << 40), b.last_of_input ? (long)b.stream_len : -1L, (int32_t *)b.d_apx_pat,
+			    (int32_t *)b.d_apx_off, (int32_t *)b.d_apx_dist, (int32_t *)b.d_apx_len, b.all_cap, (int32_t *)b.d_apx_info,
+			    b.d_apx_ws, b.apx_ws_bytes, s));
+		else
+			CK(acm_approx_matches_async(w.dfa, pat, off, cap - 2, ACM_REPORT_HEAD, b.text, 0, (long)b.stream_len,
+			    w.atail_len ? w.d_atail[w.atail_cur] : nullptr, w.atail_len, nseg ? (const int32_t *)b.d_seg_start : nullptr, nseg,
+			    c.segmented ? b.lead_begin : -(1L << 40), b.last_of_input ? (long)b.stream_len : -1L, (int32_t *)b.d_apx_pat,
+			    (int32_t *)b.d_apx_off, (int32_t *)b.d_apx_dist, b.all_cap, (int32_t *)b.d_apx_info, b.d_apx_ws, b.apx_ws_bytes, s));
 		// the next buffer's before: the last apx_back bytes of the old tail and this stream
 		const size_t keep = std::min((size_t)w.sh->apx_back, w.atail_len + b.stream_len);
 		const size_t from_text = std::min(keep, b.stream_len), from_old = keep - from_text;
@@ -1038,6 +1064,11 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		CK(acm_bucketize((const int32_t *)b.d_apx_dist, off, (const int32_t *)b.d_indices, (const int32_t *)b.d_sizes, chunks,
 		    c.max_results, (int32_t *)b.d_results3, (int32_t *)b.d_results3_off, cap, s));
 		CK(acm_rt_memcpy_d2h(b.h_results3, b.d_results3, cells * 4, s));
+		if (c.edit) {   // and the length plane
+			CK(acm_bucketize((const int32_t *)b.d_apx_len, off, (const int32_t *)b.d_indices, (const int32_t *)b.d_sizes, chunks,
+			    c.max_results, (int32_t *)b.d_results4, (int32_t *)b.d_results3_off, cap, s));
+			CK(acm_rt_memcpy_d2h(b.h_results4, b.d_results4, cells * 4, s));
+		}
 	}
 	CK(acm_rt_memcpy_d2h(b.h_results, b.d_results, cells * 4, s));
 	CK(acm_rt_memcpy_d2h(b.h_results2, b.d_results2, cells * 4, s));
@@ -1214,7 +1245,7 @@ void collect(Worker &w, Buffer &b)
 			int off = b.h_results2[(size_t)(j + 1) * chunks + i] + 1;  // end + 1 (databuf.c:771)
 			if (c.wild)   // the record is the end of the last part's anchor: the match ends its post context behind
 				off += w.sh->seq_post[p_idx];
-			if (c.approx)   // the record is the end of the piece that found the match: the pattern ends its post behind
+			if (c.approx && !c.edit)   // the record is the end of the piece that found the match: the pattern ends its post behind (-e: the record is the match's)
 				off += w.sh->apx_post[p_idx];
 			w.reported++;
 			if (!c.verbose)
@@ -1231,6 +1262,11 @@ void collect(Worker &w, Buffer &b)
 				printf("Pattern %d ('%s') found in file '%s' at line %lu offset %d [relative: %d]\n",
 				    w.sh->pat_iid[p_idx], w.sh->pat_bytes[p_idx].c_str(),
 				    w.sh->files[b.file_ids[i]].c_str(), (unsigned long)line, off, off - b.h_indices[i]);
+			} else if (c.edit) {
+				printf("Pattern %d ('%s') found in file '%s' at offset %d [relative: %d] edits %d length %d\n",
+				    w.sh->pat_iid[p_idx], w.sh->pat_bytes[p_idx].c_str(),
+				    w.sh->files[b.file_ids[i]].c_str(), off, off - b.h_indices[i], b.h_results3[(size_t)(j + 1) * chunks + i],
+				    b.h_results4[(size_t)(j + 1) * chunks + i]);
 			} else if (c.approx) {
 				printf("Pattern %d ('%s') found in file '%s' at offset %d [relative: %d] mismatches %d\n",
 				    w.sh->pat_iid[p_idx], w.sh->pat_bytes[p_idx].c_str(),
@@ -1304,6 +1340,11 @@ void *worker_main(void *arg)
 				CK(acm_rt_host_alloc((void **)&b.h_wild_info, 64));
 				b.h_wild_info[0] = 0;
 			}
+		}
+	if (c.edit)
+		for (Buffer &b : w.buf) {
+			b.apx_ws_bytes = acm_edit_workspace_bytes(w.dfa, b.all_cap - 2);
+			CK(acm_rt_malloc(&b.d_apx_ws, b.apx_ws_bytes));
 		}
 	if (c.words || c.cased)
 		for (void *&t : w.d_tail)
@@ -1429,7 +1470,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xor:O:C:VT:HNbk:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o, r, O, C, V, T, H, N, b, k
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xor:O:C:VT:HNbk:e")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o, r, O, C, V, T, H, N, b, k, e
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -1494,6 +1535,7 @@ int main(int argc, char **argv)
 				c.approx = -1;
 			break;
 		}
+		case 'e': c.edit = 1; break;
 		default: usage();
 		}
 	}
@@ -1628,6 +1670,9 @@ int main(int argc, char **argv)
 	if (c.approx < 0 || c.approx > ACM_APPROX_MAX_K) {
 		printf("ERROR: -k takes 1 to %d: the bytes of a pattern that may be other bytes\n", ACM_APPROX_MAX_K);
 		err++;
+	} else if (c.edit && (c.approx == 0 || c.approx > ACM_EDIT_MAX_K)) {
+		printf("ERROR: -e needs -k N with N from 1 to %d: the bytes that may be substituted, inserted or deleted\n", ACM_EDIT_MAX_K);
+		err++;
 	} else if (c.approx) {
 		const struct { bool on; const char *opt, *why; } refused[] = {
 			{ c.words != 0, "-W", "the word pass looks at the bytes next to a piece, not next to the match" },
@@ -1637,7 +1682,7 @@ int main(int argc, char **argv)
 			{ c.ext != 0, "-E", "it is the syntax of the signature file" },
 			{ c.only != 0 && c.repl_path.empty() && c.out_dir.empty(), "-o", "the select pass would take a piece for the match" },
 			{ !c.repl_path.empty() || !c.out_dir.empty(), "-r", "the rewrite would replace a piece, not the match" },
-			{ c.count != 0, "-c", "the tallies would count pieces" },
+			{ c.count != 0 && !c.edit, "-c", "the tallies would count pieces" },   // (-e: the records are whole matches, each once)
 			{ c.lineno != 0, "-n", "the line would be that of the piece's end, not of the match's" },
 			{ c.ctx != 0 || c.invert || !c.ext_dir.empty(), "-C", "the lines would be those of the pieces' ends" },
 			{ c.follow != 0, "-F", "the bytes behind a paused input are not known" },
@@ -1727,7 +1772,9 @@ int main(int argc, char **argv)
 			acm_automaton_pattern(read_into, i, &iid, &n, &bytes, nullptr);
 			const bool tolerant = n >= 3 * (c.approx + 1);
 			exact += !tolerant;
-			if (acm_automaton_add_approx(aut, bytes, n, tolerant ? c.approx : 0, iid, (unsigned)acm_automaton_pattern_flags(read_into, i)) < 0) {
+			const unsigned flags = (unsigned)acm_automaton_pattern_flags(read_into, i);
+			if ((c.edit ? acm_automaton_add_edit(aut, bytes, n, tolerant ? c.approx : 0, iid, flags)
+			            : acm_automaton_add_approx(aut, bytes, n, tolerant ? c.approx : 0, iid, flags)) < 0) {
 				fprintf(stderr, "ERROR: init_ocl_worker_ctx\n%s\n", acm_last_error());
 				return 1;
 			}

@@ -108,6 +108,7 @@ struct acm_automaton {
 		int first_piece, n, k, iid;
 		unsigned flags;
 		std::vector<unsigned char> bytes;
+		int mode = 0;   // 0: Hamming distance (add_approx), 1: edit distance (add_edit, edit.hip)
 	};
 	std::vector<Approx> approx;
 	// the distinct context sets of two or more bytes, interned: at most 256

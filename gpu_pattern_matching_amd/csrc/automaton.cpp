@@ -1513,31 +1513,35 @@ static int approx_piece_begin(int n, int k, int i)
 	return i * q + std::min(i, r);
 }
 
-extern "C" int acm_automaton_add_approx(acm_automaton *a, const unsigned char *bytes, int n, int k, int iid, unsigned flags)
+// acm_automaton_add_approx and acm_automaton_add_edit: the same pieces, checks and errors; fn names the caller,
+// max_k is its largest budget and mode what the pattern's distance is (acm_automaton_approx_mode)
+static int add_pieces(acm_automaton *a, const char *fn, const unsigned char *bytes, int n, int k, int iid, unsigned flags, int max_k,
+    int mode)
 {
 	if (!a || n < 0 || (n > 0 && !bytes) || k < 0)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_approx: bad arguments");
+		return acm::fail(ACM_ERR_ARG, "%s: bad arguments", fn);
 	if (flags & ~(unsigned)ACM_PATTERN_NOCASE)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_approx: unknown flag bits 0x%x", flags & ~(unsigned)ACM_PATTERN_NOCASE);
+		return acm::fail(ACM_ERR_ARG, "%s: unknown flag bits 0x%x", fn, flags & ~(unsigned)ACM_PATTERN_NOCASE);
 	if (a->compiled)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_approx: automaton already compiled");
-	if (k > ACM_APPROX_MAX_K)
-		return acm::fail(ACM_ERR_LIMIT, "acm_automaton_add_approx: budget %d, at most %d", k, ACM_APPROX_MAX_K);
+		return acm::fail(ACM_ERR_ARG, "%s: automaton already compiled", fn);
+	if (k > max_k)
+		return acm::fail(ACM_ERR_LIMIT, "%s: budget %d, at most %d", fn, k, max_k);
 	const int index = (int)a->patterns.size();
 	if (k == 0) {
 		const int rc = acm_automaton_add_ex(a, bytes, n, iid, flags);
 		return rc != ACM_OK ? rc : index;
 	}
 	if (n < k + 1)
-		return acm::fail(ACM_ERR_ARG, "acm_automaton_add_approx: %d bytes cannot be cut into %d pieces", n, k + 1);
+		return acm::fail(ACM_ERR_ARG, "%s: %d bytes cannot be cut into %d pieces", fn, n, k + 1);
 	if (n > ACM_APPROX_MAX_LEN)
-		return acm::fail(ACM_ERR_LIMIT, "acm_automaton_add_approx: %d bytes, at most %d", n, ACM_APPROX_MAX_LEN);
+		return acm::fail(ACM_ERR_LIMIT, "%s: %d bytes, at most %d", fn, n, ACM_APPROX_MAX_LEN);
 	acm_automaton::Approx x;
 	x.first_piece = index;
 	x.n = n;
 	x.k = k;
 	x.iid = iid;
 	x.flags = flags;
+	x.mode = mode;
 	x.bytes.assign(bytes, bytes + n);
 	a->patterns.reserve(a->patterns.size() + (size_t)k + 1);   // (nothing is applied when memory runs out half way)
 	a->approx.reserve(a->approx.size() + 1);
@@ -1552,6 +1556,23 @@ extern "C" int acm_automaton_add_approx(acm_automaton *a, const unsigned char *b
 	}
 	a->approx.push_back(std::move(x));
 	return index;
+}
+
+extern "C" int acm_automaton_add_approx(acm_automaton *a, const unsigned char *bytes, int n, int k, int iid, unsigned flags)
+{
+	return add_pieces(a, "acm_automaton_add_approx", bytes, n, k, iid, flags, ACM_APPROX_MAX_K, 0);
+}
+
+extern "C" int acm_automaton_add_edit(acm_automaton *a, const unsigned char *bytes, int n, int k, int iid, unsigned flags)
+{
+	return add_pieces(a, "acm_automaton_add_edit", bytes, n, k, iid, flags, ACM_EDIT_MAX_K, 1);
+}
+
+extern "C" int acm_automaton_approx_mode(const acm_automaton *a, int x)
+{
+	if (!a || x < 0 || x >= (int)a->approx.size())
+		return acm::fail(ACM_ERR_ARG, "acm_automaton_approx_mode: index out of range");
+	return a->approx[x].mode;
 }
 
 extern "C" int acm_automaton_num_approx(const acm_automaton *a) { return a ? (int)a->approx.size() : 0; }
@@ -1591,8 +1612,9 @@ extern "C" int acm_automaton_approx_reach(const acm_automaton *a, int *back, int
 		return acm::fail(ACM_ERR_ARG, "acm_automaton_approx_reach: null automaton");
 	int b = 0, f = 0;
 	for (auto &p : a->approx) {
-		b = std::max(b, p.n);
-		f = std::max(f, p.n - approx_piece_begin(p.n, p.k, 1));   // (piece 0 has the most behind it)
+		const int slack = p.mode ? p.k : 0;   // an edit pattern's span begins up to 2k in front and ends up to k behind
+		b = std::max(b, p.n + 2 * slack);
+		f = std::max(f, p.n - approx_piece_begin(p.n, p.k, 1) + slack);   // (piece 0 has the most behind it)
 	}
 	if (back) *back = b;
 	if (ahead) *ahead = f;

@@ -157,6 +157,8 @@ struct acm_dfa {
 	// (approx.hip); null otherwise: every entry is then kept with distance 0
 	bool approx = false;
 	int32_t *d_approx_ent = nullptr;     // [patterns][4] {word index of the whole pattern in d_approx_pool, or -1: not a piece; n;
-	                                     // k | piece << 8 | folds << 16; 0}: one 16-byte load per entry
+	                                     // k | piece << 8 | folds << 16; the mode, 0 Hamming or 1 edit}: one 16-byte load per entry
 	uint32_t *d_approx_pool = nullptr;   // the approximate patterns' bytes (folded for one that folds), each padded to whole words, one spare word behind
+	bool edit = false;                   // some approximate pattern is an edit pattern (acm_automaton_add_edit): the edit pass (edit.hip) is the one to call
+	uint32_t max_list_len = 0;           // the longest match list: the candidates a record can give (edit.hip sizes its workspace by it)
 };

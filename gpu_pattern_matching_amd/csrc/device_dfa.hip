@@ -219,6 +219,7 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 			if (a->is_final_ref(r)) {
 				lbegin[r] = (uint32_t)a->list_begin[r];
 				llen[r] = (uint32_t)a->list_len[r];
+				d->max_list_len = std::max(d->max_list_len, llen[r]);
 			}
 		if (rc == ACM_OK) rc = upload(&d->d_list_begin, lbegin.data(), lbegin.size(), &d->device_bytes);
 		if (rc == ACM_OK) rc = upload(&d->d_list_len, llen.data(), llen.size(), &d->device_bytes);
@@ -437,6 +438,8 @@ extern "C" int acm_dfa_upload(const acm_automaton *a, int device, acm_dfa **out)
 					ent[4 * i] = (int32_t)where[p.approx];
 					ent[4 * i + 1] = q.n;
 					ent[4 * i + 2] = q.k | p.approx_piece << 8 | (folds ? 1 << 16 : 0);
+					ent[4 * i + 3] = q.mode;
+					d->edit = d->edit || q.mode != 0;
 				}
 			}
 			rc = upload(&d->d_approx_ent, ent.data(), ent.size(), &d->device_bytes);

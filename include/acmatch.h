@@ -375,10 +375,26 @@ int acm_automaton_load_signature_file_ex(acm_automaton *, const char *path, unsi
  *                                 of the text in front, and how far behind a record a match can end.  Both 0
  *                                 without approximate patterns.
  * NOT composed: position windows, sequences, replacements, select and the word pass see a piece as the plain
- * pattern it is (its own bytes, its own span).  Insertions and deletions are not provided: they change the
- * span's length, which every table of this library takes as fixed. */
+ * pattern it is (its own bytes, its own span).  Insertions and deletions: see EDIT PATTERNS below
+ * (acm_automaton_add_edit, acm_edit_matches_async), where the span's length is an output.
+ *
+ * EDIT PATTERNS: up to k substituted, inserted or deleted bytes.  An edit pattern is n bytes and a budget k,
+ * 1 <= k <= ACM_EDIT_MAX_K and k + 1 <= n <= ACM_APPROX_MAX_LEN.  It is an approximate pattern in every host-side
+ * respect: the same pieces [b_i, e_i) as k + 1 consecutive patterns, the same acm_automaton_approx* queries, the
+ * same folding.  One thing differs: its distance is the unit-cost edit distance ed (substitution, insertion and
+ * deletion cost 1 each), which only acm_edit_matches_async verifies.  The pigeonhole argument holds as it stands:
+ * a span within edit distance k holds at least one piece exactly.
+ *   acm_automaton_add_edit        as acm_automaton_add_approx: the same return value, the same errors, nothing
+ *                                 applied on an error; k above ACM_EDIT_MAX_K is ACM_ERR_LIMIT; with k == 0 it is
+ *                                 exactly acm_automaton_add_ex
+ *   acm_automaton_approx_mode     0 where approximate pattern x counts substitutions only (add_approx), 1 where
+ *                                 it is an edit pattern (negative: a bad index)
+ * For an edit pattern acm_automaton_approx_reach takes back = n + 2k and ahead = post + k: its span may begin up
+ * to 2k bytes further in front and end up to k bytes further behind than the nominal one.  A set without edit
+ * patterns is bit for bit what it is without them: tables, digests, acm_dfa_device_bytes and the reach. */
 #define ACM_APPROX_MAX_K 15
 #define ACM_APPROX_MAX_LEN 4096
+#define ACM_EDIT_MAX_K 4
 int acm_automaton_add_approx(acm_automaton *, const unsigned char *bytes, int n, int k, int iid,
     unsigned flags);
 int acm_automaton_num_approx(const acm_automaton *);
@@ -386,6 +402,9 @@ int acm_automaton_approx(const acm_automaton *, int x, int *first_piece, int *n,
     unsigned *flags, const unsigned char **bytes);
 int acm_automaton_pattern_approx(const acm_automaton *, int index, int *x, int *piece, int *pre, int *post);
 int acm_automaton_approx_reach(const acm_automaton *, int *back, int *ahead);
+int acm_automaton_add_edit(acm_automaton *, const unsigned char *bytes, int n, int k, int iid,
+    unsigned flags);
+int acm_automaton_approx_mode(const acm_automaton *, int x);
 
 /* Rules: a boolean condition over the signatures that hit ONE text.  A RULE is nops operands, 1 <= nops <=
  * ACM_RULE_MAX_OPERANDS, an expression over them and a user id iid.  Operand j is a SEQUENCE index: the id
@@ -906,6 +925,55 @@ int acm_approx_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
     long text_end, const void *d_before, size_t before_len, const int32_t *d_seg_start,
     size_t segments, long lead_begin, long open_end, int32_t *d_pat_out, int32_t *d_off_out,
     int32_t *d_dist_out, size_t out_capacity, int32_t *d_info, void *d_workspace,
+    size_t workspace_bytes, void *stream);
+
+/* Edit patterns (acm_automaton_add_edit) verified on the device: where a piece matched, a banded dynamic
+ * program finds the nearest end within edit distance k and the shortest span that has it.  A pass over the
+ * records, as acm_approx_matches_async, and the one to call for a set that holds an edit pattern
+ * (acm_approx_matches_async refuses such a set with ACM_ERR_ARG).
+ * Input, text bytes, texts, cell layout, overflow contract and argument errors: acm_approx_matches_async's.
+ * For a text [T0, Tend) and an end e, T0 < e <= Tend, D(e) is the minimum of ed(A, T[s:e]) over T0 <= s <= e
+ * (Sellers).  A piece (p, o), p piece j of edit pattern A, lies at [o - L + 1, o + 1); its nominal span begins at
+ * s0 = o - L + 1 - b_j and ends at e0 = s0 + n.  If D(e) <= k some piece lies exactly inside an optimal span ending
+ * at e, and that piece's e0 is within k of e.
+ * The rule for entry (p, o) with L >= 1, int64 arithmetic, in this order:
+ *   1. p is no piece: the candidate (p, o, 0, L)
+ *   2. p is a piece of a Hamming pattern: rules 2 - 4 of acm_approx_matches_async unchanged; a kept entry gives
+ *      (first piece of its pattern, o + post, sum of the m_i, n)
+ *   3. p is piece j of edit pattern A with window of ends W = { e : |e - e0| <= k, T0 < e <= Tend }:
+ *      - the piece itself leaves [T0, Tend): dropped
+ *      - Tend is unknown (open_end == -1) and e0 + k > text_end: UNDECIDED
+ *      - the bytes [max(T0, s0 - 2k), min(Tend, e0 + k)) leave the bytes given, [text_origin - before_len,
+ *        text_end): UNDECIDED -- dropped and counted, whatever the available bytes hold
+ *      otherwise e* is the end in W that minimises (min(D(e), k + 1), |e - e0|, e); W empty or D(e*) > k: dropped;
+ *      len* is the smallest l with e* - l >= T0 and ed(A, T[e* - l : e*]) == D(e*); the candidate is
+ *      (first piece of A, e* - 1, D(e*), len*)
+ *   4. the output is the SET of candidates -- equal candidates collapse; two pieces that choose the same (A, e*)
+ *      compute the same distance and length -- ordered by (offset, pattern)
+ * A candidate whose offset lies outside the bytes given, [text_origin - before_len, text_end), is no record of this
+ * text (a cell may hold anything) and is dropped: the order is keyed inside that range.
+ * So every record (x, e - 1, d, l) has d == D(e) <= k and ed(A, T[e - l : e]) == d with no shorter l; no (pattern,
+ * offset) appears twice; every e with D(e) == 0 is reported with length n, and for every e with D(e) <= k there is
+ * a record of the same pattern at e' with |e' - e| <= 2k and distance <= D(e).  Like Hamming rule 4 this stands
+ * on the text alone; with HEAD input completeness holds as far as the cells name the pieces.
+ *   d_pat_out    the first piece of the pattern, or the plain pattern
+ *   d_off_out    the offset of the match's last byte
+ *   d_dist_out   NULL, or the distances      d_len_out   NULL, or the lengths of the spans; cell 0 and the trailer
+ *                as in the other planes
+ *   d_info       int32[4], required, written whole: [0] undecided entries, [1] candidates before equal ones
+ *                collapse, [2..3] 0
+ * For a set without edit patterns the call is legal and gives the normalised records of rules 1 - 2.  No read
+ * leaves the input planes, the starts, the bytes given and the library's tables, and no write the outputs and the
+ * workspace, whatever the planes hold.  Stream-ordered, no host sync, no allocation, no host read of device data.
+ * The order is a stable radix sort over max_records * (the longest match list of the set) cells for STATE input and
+ * max_records cells for HEAD input: size max_records to the planes.  7 + 3 * (digits of the pattern count + digits
+ * of the bytes given) launches (csrc/edit.hip).  The workspace query is monotone and a multiple of 256. */
+size_t acm_edit_workspace_bytes(const acm_dfa *, size_t max_records);
+int acm_edit_matches_async(const acm_dfa *, const int32_t *d_pat_plane,
+    const int32_t *d_off_plane, size_t max_records, int report, const void *d_text, long text_origin,
+    long text_end, const void *d_before, size_t before_len, const int32_t *d_seg_start,
+    size_t segments, long lead_begin, long open_end, int32_t *d_pat_out, int32_t *d_off_out,
+    int32_t *d_dist_out, int32_t *d_len_out, size_t out_capacity, int32_t *d_info, void *d_workspace,
     size_t workspace_bytes, void *stream);
 
 /* Sequences (acm_automaton_add_sequence) joined on the device: the records of the parts in, one record
