@@ -52,7 +52,7 @@
 //                  at a time (stage 2), shadow inside the wave, hits appended to the
 //                  wave's row in position order, a 32-byte row summary.  Latency-bound,
 //                  five hundred waves of dependent loads; it runs beside the next batch's
-//                  bulk pass.  Its last workgroup walks the carried state instead.
+//                  bulk pass.  Its first workgroups walk the carried states instead.
 //   k_sieve_emit   exclusive prefix max / prefix sum over the row summaries, drops the
 //                  shadowed head of each row, copies the records to the planes.
 // Nothing is capped and nothing falls back: a tile's sample list has room for every
@@ -88,6 +88,7 @@ constexpr int kWaves = kBlock / 64;
 constexpr uint32_t kTilesPerChecker = 8;    // tiles whose flagged samples one wave of k_sieve_check takes when a batch is launched alone ...
 constexpr uint32_t kTilesPerCheckerWide = 16;   // ... and in a launch group (see k_sieve_check)
 constexpr int kCheckBlock = 64;            // threads of a k_sieve_check workgroup
+constexpr uint32_t kMaxTailWalk = 12;      // the most bytes side_walks() walks at the end of a text (tail_walk): registers for them
 constexpr uint32_t kQ2Cap = 64 + 64 * 8;   // followers a checker queues: what a round leaves + 64 samples x 8 offsets
 constexpr uint32_t kMinTile = 1024;        // bytes; one 16-byte group per lane
 constexpr uint32_t kMaxTiles = 4096;       // the tile size doubles until the text has at most this many
@@ -99,13 +100,15 @@ constexpr uint32_t kHeavyDivisor = 512;    // more than a flagged sample per thi
 constexpr uint32_t kBusyDivisor = 48;      // ... or a flagged sample per this many: the check kernel's time, not the bulk kernel's, is the batch's
                                            // (with helper waves the sparse pipeline keeps up with the chain pipeline's 70..95 us to about 700 k samples
                                            // per 32 MiB: 62 us at 447 k, 91 at 650 k, 106 at 983 k -- tools/real_data_probe.py)
-constexpr int kEmitBlock = 1024;
+constexpr int kEmitBlock = 256;             // threads of a k_sieve_emit workgroup: a wave per SIMD
 #ifdef ACM_SIEVE_CHECK_STAMPS   // debugging aid (with ACM_SIEVE_STAMPS=1 at run time): clock stamps and level counts of the check
 constexpr bool kCheckStamps = true;    // kernel's waves -- compiled in on request only, they cost the kernel registers
 #else
 constexpr bool kCheckStamps = false;
 #endif
 constexpr uint32_t kMaxRows = kMaxTiles / kTilesPerChecker + 1;   // static rows: the carried-state walker + a block of eight tiles each
+constexpr uint32_t kEmitLogBytes = 22;      // a k_sieve_emit workgroup per 2^this bytes of a batch's text, as a power of two (sparse_group_enqueue)
+constexpr uint32_t kEmitRounds = (kMaxRows - 1 + kEmitBlock - 1) / kEmitBlock;   // rounds of kEmitBlock rows the static rows behind the walker's take
 // A block whose tiles hold more flagged samples than this (real binaries: the 3-grams of code and tables
 // cluster) is cut into SUB-ROWS of at most this many samples, in position order; the block's own wave
 // takes the first, the others are numbered through the whole batch in block order and dealt to the
@@ -696,9 +699,28 @@ __device__ void side_walks(const SieveArgs &a)
 		// has a follower -- if its sample could be looked at: with 6-byte filter keys the sample of a path
 		// that starts less than W + 5 bytes before the end has its key cut off by the end of the text and
 		// is never flagged, so the walk covers W + 4 bytes then (tail_walk), not just D - 1
+		// The bytes and their classes do not depend on the state: all of them are loaded before the walk, two
+		// load levels, and the walk itself is one dependent load per byte.
+		const uint32_t x0 = a.n > a.tail_walk ? a.n - a.tail_walk : 0u, left = a.n - x0;
 		uint32_t st = 0;
-		for (uint32_t x = a.n > a.tail_walk ? a.n - a.tail_walk : 0u; x < a.n; x++)
-			st = a.cold[((size_t)st << a.ls) | a.cls[a.text[x]]];
+		if (left == 0) {
+			// (an empty text: nothing to read)
+		} else if (left <= kMaxTailWalk) {
+			uint32_t c[kMaxTailWalk];
+#pragma unroll
+			for (uint32_t i = 0; i < kMaxTailWalk; i++)
+				c[i] = a.text[x0 + (i < left ? i : 0u)];   // (no branch around a load: byte x0 again behind the last)
+#pragma unroll
+			for (uint32_t i = 0; i < kMaxTailWalk; i++)
+				c[i] = a.cls[c[i]];
+#pragma unroll
+			for (uint32_t i = 0; i < kMaxTailWalk; i++)
+				if (i < left)
+					st = a.cold[((size_t)st << a.ls) | c[i]];
+		} else {   // (cannot happen: tail_walk is D - 1 <= 9 or W + 4 <= 12)
+			for (uint32_t x = x0; x < a.n; x++)
+				st = a.cold[((size_t)st << a.ls) | a.cls[a.text[x]]];
+		}
 		a.misc[0] = st;
 	}
 	Row t;
@@ -1212,19 +1234,21 @@ __global__ __launch_bounds__(kCheckBlock) void k_sieve_check(SieveGroup g, uint3
 	const uint32_t lane = threadIdx.x;
 	// The workgroups of a launch are dealt over the group's batches, a multiple of 8 each: workgroup ids
 	// go round the 8 XCDs, and block r of EVERY batch should land on the XCD whose bulk-kernel workgroup
-	// r read the block's tiles a moment ago -- its L2 still has them.  Per batch: the blocks, the
-	// workgroup of the serial walks, the helpers.
+	// r read the block's tiles a moment ago -- its L2 still has them.  Per batch: the blocks, the helpers.
+	// The workgroups of the serial walks, one per batch, lead the grid (padded to a multiple of 8): theirs are
+	// the longest chains of dependent loads in the kernel, so they are placed first, not behind every block wave.
 	const uint32_t nblocks = g.common.nrows - 1;
 	const uint32_t nhelp = HELPED ? helpers : 0u;
-	const uint32_t per = (nblocks + 1 + nhelp + 7u) & ~7u, bi = blockIdx.x / per, blk = blockIdx.x - bi * per;
-	if (blk > nblocks + nhelp)
-		return;
-	const SieveArgs a = batch_view(g, bi);
-	if (blk == nblocks) {
-		if (threadIdx.x == 0)
-			side_walks<NOCASE>(a);
+	const uint32_t lead = (g.count + 7u) & ~7u;
+	if (blockIdx.x < lead) {
+		if (blockIdx.x < g.count && threadIdx.x == 0)
+			side_walks<NOCASE>(batch_view(g, blockIdx.x));
 		return;
 	}
+	const uint32_t per = (nblocks + nhelp + 7u) & ~7u, bi = (blockIdx.x - lead) / per, blk = blockIdx.x - lead - bi * per;
+	if (blk >= nblocks + nhelp)
+		return;
+	const SieveArgs a = batch_view(g, bi);
 	unsigned long long *stamp = kCheckStamps && a.stamps && blk < nblocks ? a.stamps + (size_t)(blk + 8192) * 8 : nullptr;
 	if (stamp && lane == 0)
 		stamp[0] = __builtin_amdgcn_s_memrealtime();
@@ -1263,7 +1287,7 @@ __global__ __launch_bounds__(kCheckBlock) void k_sieve_check(SieveGroup g, uint3
 			base = wave_excl_sum(mine, lane, all);
 		}
 		// one loop for everything a wave does, so that the two stages are in the kernel once
-		for (uint32_t s0 = blk - nblocks - 1;; s0 += nhelp) {
+		for (uint32_t s0 = blk - nblocks;; s0 += nhelp) {
 			uint32_t tb = blk, tj = 0, tslot = blk + 1;
 			if (!own) {
 				if (s0 >= all)
@@ -1331,18 +1355,85 @@ __device__ __forceinline__ uint32_t block_exclusive(uint32_t x, uint32_t *lds, u
 // share of the records: a thread per output cell finds the cell's row by binary search in LDS and
 // moves one record, so that the stores of a wave lie side by side.  (The owner of a row copying the
 // row's records itself, one predicated store per possible record, took three times as long: it is
-// the instruction count of 1024 threads that matters here.)
+// the instruction count of the threads that matters here.)
+// A workgroup is four waves, one per SIMD, at no more than 128 registers and 4 KiB of LDS (PLAIN):
+// that fits on a CU beside two bulk workgroups (384 of a SIMD's 512 registers, 128 of 160 KiB) and
+// the check waves of the other streams, so the kernel starts when it is launched and not when a
+// bulk workgroup retires.
 // Rows in position order: the walker's, then block by block the block's own row and its sub-rows
-// (k_sieve_check), kEmitBlock rows a round -- one round unless the text is sample-heavy.
-// PLAIN: the check kernel ran without helper waves, i.e. no block has sub-rows: rows = static rows = threads.
-// (Known at compile time, the kernel needs 40 registers instead of 75.)
+// (k_sieve_check).  The walker's row is first and nothing shadows it: every thread reads its summary
+// and the workgroup copies its records on their own; the rows behind it go kEmitBlock a round.
+// PLAIN: the check kernel ran without helper waves, i.e. no block has sub-rows: rows = static rows, at most
+// kEmitRounds rounds, whose summaries are all loaded up front (no round adds a load level).
+struct EmitCarry {
+	uint32_t carry_in, cell_in;   // largest extent + 1 and output cells of the rows in front of the round
+	unsigned long long alive;     // smallest {alive key, node} this thread has seen
+	bool gave_any;
+};
+
+// One round: the rows o0 + tid (summary su, sa; hits at rr), `have`: the thread has a row.
+template <bool PLAIN>
+__device__ __forceinline__ void emit_round(const SieveArgs &a, EmitCarry &st, uint4 su, uint4 sa, RowRef rr, bool have, uint32_t o0,
+    uint32_t rows_here, uint32_t blk, uint32_t per, uint32_t *lds, uint32_t *s_base, uint32_t *s_drop, uint32_t *s_slot,
+    uint32_t *s_lbase)
+{
+	const uint32_t tid = threadIdx.x;
+	const uint32_t E = su.x, cnt = su.y == kGaveUp ? 0u : su.y, first = su.z, last = su.w;
+	st.gave_any |= su.y == kGaveUp;
+	if (have && sa.x)
+		st.alive = min(st.alive, ((unsigned long long)sa.x << 32) | sa.y);
+	uint32_t all_max, all_cells;
+	const uint32_t carry = max(st.carry_in, block_exclusive<true>(have ? E : 0u, lds, &all_max));
+	uint32_t d = 0;
+	if (have && cnt && first < carry) {
+		if (last < carry) {
+			d = cnt;
+		} else {
+			while (d < cnt && hit_slot(a, rr, d)->x < carry)
+				d++;
+		}
+	}
+	const uint32_t kept = have ? cnt - d : 0u;
+	const uint32_t cell = st.cell_in + block_exclusive<false>(kept, lds, &all_cells);
+	s_base[tid] = cell;
+	s_drop[tid] = d;
+	if constexpr (!PLAIN) {
+		s_slot[tid] = rr.slot;
+		s_lbase[tid] = rr.lbase;
+	}
+	__syncthreads();
+	// one thread per output cell of the round: find the row it belongs to, copy the record
+	const uint32_t cell_end = st.cell_in + all_cells;
+	for (uint32_t c = st.cell_in + blk * kEmitBlock + tid; c < cell_end; c += per * kEmitBlock) {
+		uint32_t lo = 0, hi = rows_here;   // the row r with s_base[r] <= c < s_base[r + 1]
+		while (hi - lo > 1) {
+			const uint32_t mid = (lo + hi) >> 1;
+			if (s_base[mid] <= c)
+				lo = mid;
+			else
+				hi = mid;
+		}
+		RowRef from;
+		from.slot = PLAIN ? o0 + lo : s_slot[lo];
+		from.lbase = PLAIN ? (o0 + lo) * a.cap : s_lbase[lo];
+		const uint2 rec = *hit_slot(a, from, s_drop[lo] + (c - s_base[lo]));
+		if (c + 2 < a.plane_capacity) {
+			a.pat_plane[1 + c] = (int32_t)rec.y;
+			a.off_plane[1 + c] = (int32_t)rec.x + a.off_shift;
+		}
+	}
+	st.carry_in = max(st.carry_in, all_max);
+	st.cell_in = cell_end;
+	__syncthreads();
+}
+
 template <bool PLAIN>
 __global__ __launch_bounds__(kEmitBlock) void k_sieve_emit(SieveGroup g)
 {
 	const uint32_t per = gridDim.x / g.count, bi = blockIdx.x / per, blk = blockIdx.x - bi * per;
 	const SieveArgs a = batch_view(g, bi);
 	__shared__ uint32_t lds[kEmitBlock / 64];
-	__shared__ uint32_t s_base[kEmitBlock + 1];   // first output cell of each row of the round
+	__shared__ uint32_t s_base[kEmitBlock];       // first output cell of each row of the round
 	__shared__ uint32_t s_drop[kEmitBlock];       // shadowed head of each row's list
 	__shared__ uint32_t s_slot[kEmitBlock], s_lbase[kEmitBlock];   // where each row keeps its hits (RowRef)
 	__shared__ uint32_t s_ord[kMaxRows + 1];      // static row -> its place in the order of all rows
@@ -1361,32 +1452,48 @@ __global__ __launch_bounds__(kEmitBlock) void k_sieve_emit(SieveGroup g)
 		s_alive = ~0ull;
 		s_samples = 0;
 	}
-	static_assert(kMaxRows <= kEmitBlock, "a thread per static row");
-	// the static rows' summaries, a thread each (loads without a branch around them: in flight together)
-	uint4 s0, al0;
-	{
-		const uint32_t rc = min(tid, statics - 1);
-		s0 = *(const uint4 *)(a.summary + (size_t)rc * kSummaryWords);
-		al0 = *(const uint4 *)(a.summary + (size_t)rc * kSummaryWords + 4);   // alive key, node, samples, sub-rows
-		if (tid >= statics) {
-			s0 = make_uint4(0, 0, 0, 0);
-			al0 = make_uint4(0, 0, 0, 0);
+	static_assert(kMaxRows - 1 <= kEmitRounds * kEmitBlock, "the static rows behind the walker's: a thread each in kEmitRounds rounds");
+	// the static rows' summaries: the walker's for every thread, then a thread per row and round (loads
+	// without a branch around them: all in flight together)
+	const uint4 w0 = *(const uint4 *)a.summary, wa0 = *(const uint4 *)(a.summary + 4);
+	uint4 s0[kEmitRounds], al0[kEmitRounds];
+#pragma unroll
+	for (uint32_t j = 0; j < kEmitRounds; j++) {
+		const uint32_t r = 1 + j * kEmitBlock + tid, rc = min(r, statics - 1);
+		if constexpr (PLAIN)
+			s0[j] = *(const uint4 *)(a.summary + (size_t)rc * kSummaryWords);
+		al0[j] = *(const uint4 *)(a.summary + (size_t)rc * kSummaryWords + 4);   // alive key, node, samples, sub-rows
+		if (r >= statics) {
+			s0[j] = make_uint4(0, 0, 0, 0);
+			al0[j] = make_uint4(0, 0, 0, 0);
 		}
 	}
-	uint32_t my_samples = al0.z, rows_all;
-	const uint32_t extra = PLAIN || tid == 0 ? 0u : al0.w & 0xFFFFu;   // (row 0 is the walker's: its word says nothing)
+	uint32_t my_samples = tid == 0 ? wa0.z : 0u, rows_all;
+#pragma unroll
+	for (uint32_t j = 0; j < kEmitRounds; j++)
+		my_samples += al0[j].z;
 	if constexpr (PLAIN) {
-		rows_all = statics;   // (row = thread: no order to work out)
+		rows_all = statics;   // (a row per static row: no order to work out)
 	} else {
-		const uint32_t ord = block_exclusive<false>(tid < statics ? 1u + extra : 0u, lds, &rows_all);
-		if (tid < statics) {
-			s_ord[tid] = ord;
-			s_first[tid] = ord - tid;   // sub-rows of the blocks in front: the number of this block's first (k_sieve_check)
+		// the order of all rows: a static row, then its block's sub-rows (row 0 is the walker's: it has none)
+		rows_all = 1;
+		if (tid == 0)
+			s_ord[0] = s_first[0] = 0;
+#pragma unroll
+		for (uint32_t j = 0; j < kEmitRounds; j++) {
+			const uint32_t r = 1 + j * kEmitBlock + tid;
+			uint32_t total;
+			const uint32_t ord = rows_all + block_exclusive<false>(r < statics ? 1u + (al0[j].w & 0xFFFFu) : 0u, lds, &total);
+			if (r < statics) {
+				s_ord[r] = ord;
+				s_first[r] = ord - r;   // sub-rows of the blocks in front: the number of this block's first (k_sieve_check)
+			}
+			rows_all += total;
 		}
 		if (tid == 0)
 			s_ord[statics] = rows_all;
 	}
-	if (blk == 0) {   // (a wave at a time: five hundred atomics on one LDS word would take longer than the copy below)
+	if (blk == 0) {   // (a wave at a time: hundreds of atomics on one LDS word would take longer than the copy below)
 #pragma unroll
 		for (int o = 32; o > 0; o >>= 1)
 			my_samples += __shfl_xor(my_samples, o, 64);
@@ -1396,18 +1503,33 @@ __global__ __launch_bounds__(kEmitBlock) void k_sieve_emit(SieveGroup g)
 	__syncthreads();
 	if (stamp)
 		stamp[1] = __builtin_amdgcn_s_memrealtime();
-	const bool plain = PLAIN || rows_all == statics;   // no sub-rows: row = thread, everything is loaded already
-	uint32_t carry_in = 0, cell_in = 0;
-	unsigned long long alive = ~0ull;
-	bool gave_any = false;
-	for (uint32_t o0 = 0; o0 < rows_all; o0 += kEmitBlock) {
-		const uint32_t o = o0 + tid;
-		const bool have = o < rows_all;
-		uint4 su = s0, sa = al0;
-		RowRef rr;
-		rr.slot = tid;
-		rr.lbase = tid * a.cap;
-		if (!PLAIN && !plain) {
+	// the walker's row
+	EmitCarry st;
+	st.carry_in = w0.x;
+	st.cell_in = w0.y == kGaveUp ? 0u : w0.y;
+	st.alive = tid == 0 && wa0.x ? ((unsigned long long)wa0.x << 32) | wa0.y : ~0ull;
+	st.gave_any = w0.y == kGaveUp;
+	for (uint32_t c = blk * kEmitBlock + tid; c < st.cell_in; c += per * kEmitBlock) {
+		const uint2 rec = *hit_slot(a, RowRef{ 0, 0 }, c);
+		if (c + 2 < a.plane_capacity) {
+			a.pat_plane[1 + c] = (int32_t)rec.y;
+			a.off_plane[1 + c] = (int32_t)rec.x + a.off_shift;
+		}
+	}
+	if constexpr (PLAIN) {
+#pragma unroll
+		for (uint32_t j = 0; j < kEmitRounds; j++) {
+			const uint32_t o0 = 1 + j * kEmitBlock;
+			if (o0 < rows_all) {
+				const uint32_t o = o0 + tid;
+				emit_round<true>(a, st, s0[j], al0[j], RowRef{ o, o * a.cap }, o < rows_all, o0, min(rows_all - o0, (uint32_t)kEmitBlock),
+				    blk, per, lds, s_base, s_drop, nullptr, nullptr);
+			}
+		}
+	} else {
+		for (uint32_t o0 = 1; o0 < rows_all; o0 += kEmitBlock) {
+			const uint32_t o = o0 + tid;
+			const bool have = o < rows_all;
 			// the static row this row belongs to: the last one whose place is not behind o
 			uint32_t lo = 0, hi = statics;
 			while (hi - lo > 1) {
@@ -1418,81 +1540,34 @@ __global__ __launch_bounds__(kEmitBlock) void k_sieve_emit(SieveGroup g)
 					hi = mid;
 			}
 			const uint32_t k = o - s_ord[lo];
+			RowRef rr;
 			rr.slot = k == 0 ? lo : statics + s_first[lo] + k - 1;
 			rr.lbase = lo * a.cap;
-			su = make_uint4(0, 0, 0, 0);
-			sa = make_uint4(0, 0, 0, 0);
+			uint4 su = make_uint4(0, 0, 0, 0), sa = make_uint4(0, 0, 0, 0);
 			if (have) {
 				su = *(const uint4 *)(a.summary + (size_t)rr.slot * kSummaryWords);
 				sa = *(const uint4 *)(a.summary + (size_t)rr.slot * kSummaryWords + 4);
 				if (k)
 					rr.lbase = sa.w;
 			}
+			emit_round<false>(a, st, su, sa, rr, have, o0, min(rows_all - o0, (uint32_t)kEmitBlock), blk, per, lds, s_base, s_drop,
+			    s_slot, s_lbase);
 		}
-		const uint32_t E = su.x, cnt = su.y == kGaveUp ? 0u : su.y, first = su.z, last = su.w;
-		gave_any |= su.y == kGaveUp;
-		if (have && sa.x)
-			alive = min(alive, ((unsigned long long)sa.x << 32) | sa.y);
-		uint32_t all_max, all_cells;
-		const uint32_t carry = max(carry_in, block_exclusive<true>(have ? E : 0u, lds, &all_max));
-		uint32_t d = 0;
-		if (have && cnt && first < carry) {
-			if (last < carry) {
-				d = cnt;
-			} else {
-				while (d < cnt && hit_slot(a, rr, d)->x < carry)
-					d++;
-			}
-		}
-		const uint32_t kept = have ? cnt - d : 0u;
-		const uint32_t cell = cell_in + block_exclusive<false>(kept, lds, &all_cells);
-		s_base[tid] = cell;
-		s_drop[tid] = d;
-		if constexpr (!PLAIN) {
-			s_slot[tid] = rr.slot;
-			s_lbase[tid] = rr.lbase;
-		}
-		if (tid == 0)
-			s_base[kEmitBlock] = cell_in + all_cells;
-		__syncthreads();
-		// one thread per output cell of the round: find the row it belongs to, copy the record
-		const uint32_t rows_here = min(rows_all - o0, (uint32_t)kEmitBlock), cell_end = cell_in + all_cells;
-		for (uint32_t c = cell_in + blk * kEmitBlock + tid; c < cell_end; c += per * kEmitBlock) {
-			uint32_t lo = 0, hi = rows_here;   // the row r with s_base[r] <= c < s_base[r + 1]
-			while (hi - lo > 1) {
-				const uint32_t mid = (lo + hi) >> 1;
-				if (s_base[mid] <= c)
-					lo = mid;
-				else
-					hi = mid;
-			}
-			RowRef from;
-			from.slot = PLAIN ? lo : s_slot[lo];
-			from.lbase = PLAIN ? lo * a.cap : s_lbase[lo];
-			const uint2 rec = *hit_slot(a, from, s_drop[lo] + (c - s_base[lo]));
-			if (c + 2 < a.plane_capacity) {
-				a.pat_plane[1 + c] = (int32_t)rec.y;
-				a.off_plane[1 + c] = (int32_t)rec.x + a.off_shift;
-			}
-		}
-		carry_in = max(carry_in, all_max);
-		cell_in = cell_end;
-		__syncthreads();
 	}
-	if (__syncthreads_or(gave_any ? 1 : 0)) {   // cannot happen (geometry_for): say so instead of leaving planes that look complete
+	if (__syncthreads_or(st.gave_any ? 1 : 0)) {   // cannot happen (geometry_for): say so instead of leaving planes that look complete
 		if (blk == 0 && tid == 0) {
 			*a.path_marker = kMarkerFailed;
 			a.pat_plane[0] = a.off_plane[0] = 0;
 		}
 		return;
 	}
-	if (alive != ~0ull)
-		atomicMin(&s_alive, alive);
+	if (st.alive != ~0ull)
+		atomicMin(&s_alive, st.alive);
 	__syncthreads();
 	if (stamp)
 		stamp[3] = __builtin_amdgcn_s_memrealtime();
 	if (blk == 0 && tid == 0) {   // header and trailer cells
-		const uint32_t all_cells = cell_in;
+		const uint32_t all_cells = st.cell_in;
 		const unsigned long long k = s_alive;
 		const uint32_t last_dev = k != ~0ull ? (uint32_t)k : a.misc[0];
 		const int32_t last_ref = (int32_t)a.dev2ref[last_dev];
@@ -1726,12 +1801,18 @@ int sparse_group_enqueue(const acm_dfa *d, const SieveJob *jobs, uint32_t count,
 	uint32_t blocks = (g.ntiles + kWaves - 1) / kWaves;
 	if (blocks > (uint32_t)d->num_cus)
 		blocks = (uint32_t)d->num_cus;
-	// K2: a wave per kTilesPerChecker tiles, and one workgroup for the serial walks
+	// K2: one workgroup per batch for the serial walks, then a wave per block of tiles
 	const uint32_t cwaves = g.nrows - 1;
-	const uint32_t cblocks = (cwaves + 1 + helpers + 7u) & ~7u;   // (a multiple of 8 per batch: k_sieve_check)
-	uint32_t eblocks = 2;   // a power of two; each works out the whole prefix, more of them only for the copies
-	while (eblocks < 64 && ((size_t)eblocks << 22) < n)   // (a CU issues scattered 4-byte stores one a clock)
+	const uint32_t cblocks = (cwaves + helpers + 7u) & ~7u;   // (a multiple of 8 per batch: k_sieve_check)
+	const uint32_t clead = (count + 7u) & ~7u;                // ... behind the workgroups of the batches' serial walks
+	// K3: workgroups of four waves per batch, a power of two; each works out the whole prefix, more of them only
+	// for the copies (a CU issues scattered 4-byte stores one a clock)
+	static const uint32_t force_eblocks = getenv("ACM_SIEVE_EBLOCKS") ? (uint32_t)atoi(getenv("ACM_SIEVE_EBLOCKS")) : 0u;   // debugging aid: 1..64
+	uint32_t eblocks = 1;
+	while (eblocks < 64 && ((size_t)eblocks << kEmitLogBytes) < n)
 		eblocks *= 2;
+	if (force_eblocks)
+		eblocks = std::min(std::max(force_eblocks, 1u), 64u);
 	const bool long_keys = d->sv_gram_len == 6;
 	if (d->nocase) {   // (no clock stamps: the debugging aid is for the case-sensitive kernels)
 		switch (d->sv_stride) {
@@ -1778,10 +1859,10 @@ int sparse_group_enqueue(const acm_dfa *d, const SieveJob *jobs, uint32_t count,
 	static const char *skip = getenv("ACM_SIEVE_SKIP");   // experiment (results are void): "c" no check kernel, "e" no emit kernel
 	const bool skip_check = skip && strchr(skip, 'c'), skip_emit = skip && strchr(skip, 'e');
 #define ACM_CHECK(W, NC)                                                                                                                        \
-	if (helpers) hipLaunchKernelGGL((k_sieve_check<W, true, kTilesPerChecker, NC>), dim3(cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers); \
+	if (helpers) hipLaunchKernelGGL((k_sieve_check<W, true, kTilesPerChecker, NC>), dim3(clead + cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers); \
 	else if (tpc == kTilesPerCheckerWide)                                                                                                           \
-		hipLaunchKernelGGL((k_sieve_check<W, false, kTilesPerCheckerWide, NC>), dim3(cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers);     \
-	else hipLaunchKernelGGL((k_sieve_check<W, false, kTilesPerChecker, NC>), dim3(cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers)
+		hipLaunchKernelGGL((k_sieve_check<W, false, kTilesPerCheckerWide, NC>), dim3(clead + cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers);     \
+	else hipLaunchKernelGGL((k_sieve_check<W, false, kTilesPerChecker, NC>), dim3(clead + cblocks * count), dim3(kCheckBlock), 0, s, grp, helpers)
 	if (!skip_check && d->nocase)
 	switch (d->sv_stride) {
 	case 8: ACM_CHECK(8, true); break;
