@@ -1611,6 +1611,30 @@ class Matcher:
                 out_capacity, _ptr(at_out), at_capacity, _ptr(seg_start), segments, _ptr(seg_out), _ptr(info), _ptr(ws),
                 nb, st), "acm_extract_async")
 
+    def _packed_prologue(self, delimiter, terminator, before, after, only_matching):
+        """What scan_extract and scan_format check first: (the delimiter's byte, the terminator's byte)."""
+        d = delimiter[0] if isinstance(delimiter, (bytes, bytearray)) else int(delimiter)
+        if only_matching and self.wild:
+            raise ValueError("only_matching needs an automaton without wildcard contexts: a match there ends "
+                             "behind its record's offset")
+        if before < 0 or after < 0:
+            raise ValueError("before and after are >= 0")
+        term = d if terminator is None else (terminator[0] if isinstance(terminator, (bytes, bytearray)) else int(terminator))
+        return d, term
+
+    def _packed_results(self, pl, info, cap, out, at, seg):
+        """What scan_extract and scan_format read back behind the packing pass: (the output's bytes, where every used
+        range's bytes begin, info, seg_out or None); ACM_ERR_CAPACITY for an output of more than cap bytes."""
+        res = info.to_numpy(np.int32, 8, stream=self.stream)
+        m = (int(np.uint32(res[3])) << 32) | int(np.uint32(res[2]))
+        if res[6]:
+            raise AcmError(_lib.ACM_ERR_CAPACITY, pl.where, "the output has %d bytes but the buffer holds %d" % (m, cap))
+        data = out.to_numpy(np.uint8, m, stream=self.stream).tobytes()
+        used = int(res[0])
+        at_cells = at.to_numpy(np.int32, used + 2, stream=self.stream)[1:1 + used].copy()
+        seg_cells = seg.to_numpy(np.int32, pl.nseg, stream=self.stream) if seg is not None else None
+        return data, at_cells, res, seg_cells
+
     def scan_extract(self, text=None, texts=None, delimiter=b"\n", before=0, after=0, invert=False, per_line=False,
                      only_matching=False, glue=None, terminator=None, init_state=0, out_capacity=None):
         """grep's output on the device: the lines that hold a match (invert: that hold none) with before lines in
@@ -1632,13 +1656,7 @@ class Matcher:
         records.  A convenience call, sized for the worst case as scan_lines is; a caller who knows better uses
         the *_async calls with its own buffers.  An output that does not fit is ACM_ERR_CAPACITY, never cut
         silently."""
-        d = delimiter[0] if isinstance(delimiter, (bytes, bytearray)) else int(delimiter)
-        if only_matching and self.wild:
-            raise ValueError("only_matching needs an automaton without wildcard contexts: a match there ends "
-                             "behind its record's offset")
-        if before < 0 or after < 0:
-            raise ValueError("before and after are >= 0")
-        term = d if terminator is None else (terminator[0] if isinstance(terminator, (bytes, bytearray)) else int(terminator))
+        d, term = self._packed_prologue(delimiter, terminator, before, after, only_matching)
         with _Pipeline(self, "Matcher.scan_extract", text, texts) as pl:
             n, info = pl.n, pl.alloc(32)
             if only_matching:
@@ -1665,15 +1683,8 @@ class Matcher:
                 cap = out_capacity if out_capacity is not None else min(n + lcap * (1 + len(g)), 2 ** 31 - 17)
                 begin, end, ranges, incl = beg, nxt, lcap, False
                 grp = (rel, beg, nxt, cnt)
-            out, at, seg = pl.extract(begin, end, ranges, info, cap, g, term, incl)
-            res = info.to_numpy(np.int32, 8, stream=self.stream)
-            m = (int(np.uint32(res[3])) << 32) | int(np.uint32(res[2]))
-            if res[6]:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, pl.where, "the output has %d bytes but the buffer holds %d" % (m, cap))
-            data = out.to_numpy(np.uint8, m, stream=self.stream).tobytes()
-            used = int(res[0])
-            at_cells = at.to_numpy(np.int32, used + 2, stream=self.stream)[1:1 + used].copy()
-            seg_cells = seg.to_numpy(np.int32, pl.nseg, stream=self.stream) if seg is not None else None
+            packed = pl.extract(begin, end, ranges, info, cap, g, term, incl)
+            data, at_cells, res, seg_cells = self._packed_results(pl, info, cap, *packed)
             if grp is None:
                 k = ranges
                 s = begin.to_numpy(np.int32, k + 1, stream=self.stream)[1:].astype(np.int64)
@@ -1745,13 +1756,7 @@ class Matcher:
         them.  out_capacity: by default a bound that always fits: scan_extract's, and for every line the longest
         prefix this text can have (the longest name, the digits of n + 1, a separator each).  An output that does
         not fit is ACM_ERR_CAPACITY, never cut silently."""
-        d = delimiter[0] if isinstance(delimiter, (bytes, bytearray)) else int(delimiter)
-        if only_matching and self.wild:
-            raise ValueError("only_matching needs an automaton without wildcard contexts: a match there ends "
-                             "behind its record's offset")
-        if before < 0 or after < 0:
-            raise ValueError("before and after are >= 0")
-        term = d if terminator is None else (terminator[0] if isinstance(terminator, (bytes, bytearray)) else int(terminator))
+        d, term = self._packed_prologue(delimiter, terminator, before, after, only_matching)
         with _Pipeline(self, "Matcher.scan_format", text, texts) as pl:
             n, info, lcap = pl.n, pl.alloc(32), pl.n + 1
             table = None
@@ -1798,15 +1803,8 @@ class Matcher:
                 begin, end, ranges, incl = beg, nxt, lcap, False
                 planes = (rel, beg, nxt, kind)
                 prefix.update(kind_plane=kind, num_plane=rel)
-            out, at, seg = pl.format(begin, end, ranges, info, cap, g, term, incl, **prefix)
-            res = info.to_numpy(np.int32, 8, stream=self.stream)
-            m = (int(np.uint32(res[3])) << 32) | int(np.uint32(res[2]))
-            if res[6]:
-                raise AcmError(_lib.ACM_ERR_CAPACITY, pl.where, "the output has %d bytes but the buffer holds %d" % (m, cap))
-            data = out.to_numpy(np.uint8, m, stream=self.stream).tobytes()
-            used = int(res[0])
-            at_cells = at.to_numpy(np.int32, used + 2, stream=self.stream)[1:1 + used].copy()
-            seg_cells = seg.to_numpy(np.int32, pl.nseg, stream=self.stream) if seg is not None else None
+            packed = pl.format(begin, end, ranges, info, cap, g, term, incl, **prefix)
+            data, at_cells, res, seg_cells = self._packed_results(pl, info, cap, *packed)
             h = linfo.to_numpy(np.int32, 8, stream=self.stream)
             first = 1 + (int(np.uint32(h[4])) | int(np.uint32(h[5])) << 32)
             k = ranges if only_matching else int(planes[0].to_numpy(np.int32, 1, stream=self.stream)[0])

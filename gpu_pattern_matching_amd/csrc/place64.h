@@ -1,4 +1,4 @@
-// 64-bit placement: what the passes that write a packed byte output (rewrite.hip, extract.hip, format.hip) share on top of the
+// 64-bit placement: what the passes that write a packed byte output (rewrite.hip, and through range_pack.h extract.hip and format.hip) share on top of the
 // record-pass core.  Internal to the library, gfx950 only.  Two launches of 64-bit block sums over the input cells give
 // every used cell its end in the output; the copy kernels find the cells of a tile of OUTPUT by a search on those ends.
 #pragma once
@@ -6,6 +6,9 @@
 #include "record_pass.h"
 
 namespace acm_rp {
+
+constexpr uint32_t kTileBytes = 16384;            // output bytes a copy kernel's workgroup owns
+constexpr size_t kMaxBytes = 0x7FFFFFFFul - 16;   // 2^31 - 17: the longest text and the longest output
 
 // sum over the block of v.  Every thread gets the sum.  red: kWaves cells.
 __device__ __forceinline__ int64_t block_sum64(int64_t v, int64_t *red)

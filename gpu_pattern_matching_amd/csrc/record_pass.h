@@ -1,5 +1,5 @@
 // The record-pass core: what the passes that run behind a scan (segment.hip, tally.hip, lines.hip, sequence.hip,
-// rule.hip, select.hip, rewrite.hip, extract.hip, format.hip, expand in post.hip, and through entry_pass.h word.hip, case.hip, position.hip, wildcard.hip and approx.hip) share.  Internal to the
+// rule.hip, select.hip, rewrite.hip, through range_pack.h extract.hip and format.hip, expand in post.hip, and through entry_pass.h word.hip, case.hip, position.hip, wildcard.hip and approx.hip) share.  Internal to the
 // library, gfx950 only.  DESIGN.md 6f.
 //
 // A pass runs a fixed grid of at most kMaxBlocks blocks of kThreads threads.  Every block owns a

@@ -33,7 +33,6 @@ namespace {
 
 using namespace acm_rp;
 
-constexpr uint32_t kTileBytes = 16384;                        // output bytes a workgroup owns
 constexpr int kPieces = kTileBytes / 16 / kThreads;           // 16-byte pieces per thread: 4
 // the source of a streamed piece: two aligned 16-byte loads and a byte align, or (the other form measured in DESIGN.md
 // 6p, kept buildable with -DACM_REWRITE_UNALIGNED_SOURCE) one unaligned 16-byte load
@@ -406,8 +405,6 @@ Layout layout_of(size_t max_records, uint32_t blocks)
 	l.total = at;
 	return l;
 }
-
-constexpr size_t kMaxBytes = 0x7FFFFFFFul - 16;   // 2^31 - 17
 
 }  // namespace
 

@@ -1173,7 +1173,7 @@ int acm_rewrite_async(const acm_dfa *, const void *d_text, size_t n, long text_o
  * kernel runs on a grid over out_capacity: a workgroup owns 16 KiB of OUTPUT, finds its ranges by a search
  * on the output ends, stages the tile in LDS -- a 16-byte aligned source piece per lane, shifted in
  * registers to its place -- and streams it out in aligned 16-byte stores; a tile inside one range's
- * bytes is copied straight (csrc/extract.hip).  The launch count and the grids depend on max_ranges,
+ * bytes is copied straight (csrc/range_pack.h).  The launch count and the grids depend on max_ranges,
  * segments and out_capacity only -- m lives on the device -- and tiles behind min(m, out_capacity) leave
  * at once.  The workspace query is monotone in both arguments and a multiple of 256.
  * Not provided: extraction continued across calls (a range is used whole or not at all: give whole texts);
@@ -1232,8 +1232,8 @@ int acm_extract_async(const void *d_text, size_t n, long text_origin,
  * kernel runs on a grid over out_capacity: a workgroup owns 16 KiB of OUTPUT, finds its ranges by a search on
  * the output ends and stages the tile in LDS: a thread per range writes glue, prefix and terminator (a name
  * over 32 bytes is copied by the thread's wave), the bytes go as aligned 16-byte source pieces, a piece a
- * lane, and the tile leaves in aligned 16-byte stores (csrc/format.hip).  The launch count and the grids
- * depend on max_ranges, segments and out_capacity only.  Every run gives the same bytes.  The workspace
+ * lane, and the tile leaves in aligned 16-byte stores (csrc/range_pack.h, csrc/format.hip).  The launch count
+ * and the grids depend on max_ranges, segments and out_capacity only.  Every run gives the same bytes.  The workspace
  * query is monotone in both arguments and a multiple of 256.
  * Not provided: prefixes continued across calls (the caller carries the bases); "--" between two texts (glue
  * never joins texts; grep prints one there); padded or aligned numbers (grep -T); lines cut at a text start
