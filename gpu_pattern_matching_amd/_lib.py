@@ -45,6 +45,8 @@ EXTRACT_MAX_GLUE = 16
 FORMAT_NAME, FORMAT_NUMBER, FORMAT_OFFSET = 2, 4, 8
 FORMAT_MAX_NAME = 4096
 LINE_SELECTED, LINE_GROUP_HEAD = 1, 2
+NORM_PERCENT, NORM_SQUEEZE, NORM_STRIP = 1, 2, 4
+NORM_BLOCK = 1024
 SEQ_MAX_PARTS = 32
 GAP_UNBOUNDED = 0x7FFFFFFF
 WILDCARD_MAX_POSITIONS = 4096
@@ -224,6 +226,11 @@ NATIVE_API = {
     "acm_line_context_lines_async": (C.c_int, [_vp, C.c_size_t, _vp, C.c_long, C.c_long, _vp, C.c_size_t, C.c_int, C.c_int,
                                                C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t,
                                                _vp]),
+    "acm_normalize_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "acm_normalize_async": (C.c_int, [_vp, C.c_size_t, C.c_long, C.c_uint, C.c_char_p, C.c_int, _vp, C.c_size_t, _vp, _vp,
+                                      _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "acm_normalize_remap_async": (C.c_int, [_vp, _vp, C.c_size_t, C.c_long, C.c_uint, _vp, _vp, _vp, _vp, C.c_size_t, _vp,
+                                            _vp, _vp, _vp]),
     "acm_scan_set_mode": (C.c_int, [_vp, C.c_int]),
     "acm_scan_set_graphs": (C.c_int, [_vp, C.c_int]),
     "acm_scan_graph_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

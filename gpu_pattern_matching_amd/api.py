@@ -718,6 +718,36 @@ class _Pipeline:
                              workspace=ws)
         return out, at, seg
 
+    def normalize(self, flags, blank_mask=None, blank_byte=0x20, out_capacity=None):
+        """the normalise pass over the pipeline's text, which the normalised text then replaces (with texts, their
+        starts in it replace the starts): every later stage runs on it.  What normalize_remap needs is kept.  The
+        scan's length is a host argument, so the host waits here once and reads the figures; returns them, int32[8]"""
+        cap = self.n if out_capacity is None else out_capacity
+        ws = self.workspace(self.m.lib.acm_normalize_workspace_bytes, self.n, self.nseg)
+        out = self.alloc((cap + 15) // 16 * 16 + 16)
+        keep = self.alloc(max((self.n + 63) // 64 * 8, 16))
+        block = self.alloc(((self.n + _lib.NORM_BLOCK - 1) // _lib.NORM_BLOCK + 1) * 4)
+        seg = self.alloc(self.nseg * 4) if self.nseg else None
+        info = self.alloc(32)
+        self.m.normalize_async(self.d, self.n, flags, out, cap, keep, block, info, blank_mask=blank_mask,
+                               blank_byte=blank_byte, seg_start=self.d_st, segments=self.nseg, seg_out=seg, workspace=ws)
+        res = info.to_numpy(np.int32, 8, stream=self.stream)
+        if res[4]:
+            raise AcmError(_lib.ACM_ERR_CAPACITY, self.where, "the normalised text has %d bytes but the buffer holds %d" % (
+                int(res[0]), cap))
+        self.norm = (self.d, self.n, flags, keep, block)
+        self.d, self.n, self.d_st = out, int(res[0]), seg
+        return res
+
+    def normalize_remap(self, info):
+        """the current planes (pattern, offset in the normalised text) brought back to the text normalize() read: the
+        offset plane in place becomes where every match ends; returns the plane of where it starts"""
+        d, n, flags, keep, block = self.norm
+        start = self.alloc(self.room * 4)
+        self.m.normalize_remap_async(d, n, flags, keep, block, self.off, self.max_records, self.off, info,
+                                     pat_plane=self.pat, start_out=start)
+        return start
+
     def line_context(self, starts, lcap, linfo, cinfo, before, after, invert, ws):
         """the context pass over the current planes' offsets and the device-made starts; returns the planes (rel,
         begin, next, lines) of the groups, lcap + 2 cells each.  ws: (buffer, nbytes)"""
@@ -1438,6 +1468,83 @@ class Matcher:
             at_cells = at.to_numpy(np.int32, used + 2, stream=self.stream)[1:1 + used].copy()
             seg_cells = seg.to_numpy(np.int32, p.nseg, stream=self.stream) if seg is not None else None
             return data, res, at_cells, seg_cells
+
+    @staticmethod
+    def blank_mask(blank_set):
+        """32-byte mask (bit b % 8 of byte b // 8: byte b is blank) of an iterable of byte values or a bytes-like
+        object; None stays None (the default set: tab, LF, VT, FF, CR, space)."""
+        if blank_set is None:
+            return None
+        m = bytearray(32)
+        for b in bytes(blank_set) if isinstance(blank_set, (bytes, bytearray, memoryview)) else blank_set:
+            m[int(b) >> 3] |= 1 << (int(b) & 7)
+        return bytes(m)
+
+    def normalize_async(self, d_text, n, flags, out, out_capacity, keep, block, info, blank_mask=None, blank_byte=0x20,
+                        text_origin=0, seg_start=None, segments=0, seg_out=None, workspace=None, stream=None):
+        """Enqueue the normalise pass (acm_normalize_async): the device text d_text[0, n) with percent triples decoded
+        (NORM_PERCENT) and blank units squeezed to blank_byte (NORM_SQUEEZE) or dropped (NORM_STRIP), into out (16-byte
+        aligned, out_capacity bytes; None with 0: only the figures).  keep: device uint64[ceil(n / 64)], a bit per
+        byte that emits; block: device int32[ceil(n / 1024) + 1], the output in front of every 1024 input bytes: the
+        offset map.  blank_mask: 32 host bytes (Matcher.blank_mask) or None for the default set.  info: device
+        int32[8]: m, units dropped, triples, blank units emitted, 1 if the output was cut, 0s.  seg_start and
+        seg_out, int32[segments] each: the text starts, and where every text begins in the output.  workspace: (ptr,
+        nbytes), or None for a temporary one that lives until the stream has passed it (the call then synchronises)."""
+        st = stream if stream is not None else self.stream
+        with self._workspace(workspace, st, self.lib.acm_normalize_workspace_bytes, n, segments) as (ws, nb):
+            check(self.lib.acm_normalize_async(
+                _ptr(d_text), n, text_origin, flags, blank_mask, blank_byte, _ptr(out), out_capacity, _ptr(keep),
+                _ptr(block), _ptr(seg_start), segments, _ptr(seg_out), _ptr(info), _ptr(ws), nb, st), "acm_normalize_async")
+
+    def normalize_remap_async(self, d_text, n, flags, keep, block, off_plane, max_records, off_out, info, pat_plane=None,
+                              start_out=None, text_origin=0, stream=None):
+        """Enqueue the remap pass (acm_normalize_remap_async): records whose offsets lie in the normalised text become
+        offsets into the text the normalise call read.  d_text, n, flags, text_origin, keep and block are that
+        call's.  off_out (it may be off_plane): where every record's last emitting unit ends; with pat_plane and
+        start_out: where the match starts.  Unmapped cells are -1; info: device int32[8]: records, records with an
+        unmapped cell, 0s."""
+        st = stream if stream is not None else self.stream
+        check(self.lib.acm_normalize_remap_async(
+            self.dfa, _ptr(d_text), n, text_origin, flags, _ptr(keep), _ptr(block), _ptr(pat_plane), _ptr(off_plane),
+            max_records, _ptr(off_out), _ptr(start_out), _ptr(info), st), "acm_normalize_remap_async")
+
+    def scan_normalized(self, text=None, texts=None, percent=False, squeeze=False, strip=False, blank_set=None,
+                        blank_byte=0x20, all_patterns=False, out_capacity=None):
+        """Matches against a normalised view of the input, reported on the input: the normalise pass
+        (acm_normalize_async: percent triples decoded, blanks squeezed to blank_byte or stripped), an ordinary scan of
+        the normalised text, the segment pass over the normalised texts when texts is given (no match spans two
+        texts, normalised or not), the case pass for a mixed automaton or with all_patterns every pattern of every
+        record, then the remap (acm_normalize_remap_async).  text: host bytes; or None with texts: a list of
+        bytes-like objects or a (uint8 array, int32 starts) pair.  blank_set: the blank bytes (None: tab, LF, VT,
+        FF, CR, space).  Returns (patterns, starts, ends, m): per match its pattern and the first and last byte of
+        the input it covers (int32, in the coordinates of the input or of the concatenation), and the normalised
+        length.  The scan's length is a host argument and m lives on the device: the host waits once between
+        normalise and scan to read it.  out_capacity: the room for the normalised text (by default the input's
+        length, which always suffices); a text that does not fit is ACM_ERR_CAPACITY."""
+        flags = (_lib.NORM_PERCENT if percent else 0) | (_lib.NORM_SQUEEZE if squeeze else 0) | (_lib.NORM_STRIP if strip else 0)
+        with _Pipeline(self, "Matcher.scan_normalized", text, texts) as p:
+            m = int(p.normalize(flags, self.blank_mask(blank_set), blank_byte, out_capacity)[0])
+            none = np.zeros(0, dtype=np.int32)
+            if m == 0:
+                return none, none, none, 0
+            info = p.alloc(32)
+            if all_patterns or self.mixed:
+                p.scan()
+                if p.nseg:
+                    p.segment()
+                if all_patterns:
+                    p.every_pattern(8 * p.cap)
+                else:
+                    p.case(p.cap, False)
+            elif p.nseg:
+                p.scan()
+                p.segment(_lib.REPORT_HEAD)
+            else:
+                p.scan(report=_lib.REPORT_HEAD)
+            p.max_records = n = p.count()
+            start = p.normalize_remap(info)
+            ends, pats, _, starts = p.download(n, start)
+            return pats, starts, ends.astype(np.int32), m
 
     def tally_async(self, pat_plane, off_plane, max_records, class_total, report=0, all_patterns=False,
                     accumulate=False, class_of=None, num_classes=None, seg_start=None, segments=0, seg_class=None,

@@ -17,7 +17,7 @@ OBJ = os.path.join(PKG, "_build")
 LIB = os.path.join(PKG, "libacmatch.so")
 CLI = os.path.join(PKG, "acm_grep")          # native CLI (csrc/acm_grep.cpp), host code only
 
-SOURCES = ["automaton.cpp", "compact_tables.cpp", "sieve_image.cpp", "multi.cpp", "dispatch.cpp", "device_dfa.hip", "scan.hip", "lds_walk.hip", "sparse.hip", "post.hip", "segment.hip", "word.hip", "case.hip", "position.hip", "wildcard.hip", "approx.hip", "edit.hip", "sequence.hip", "rule.hip", "select.hip", "rewrite.hip", "extract.hip", "format.hip", "tally.hip", "lines.hip", "runtime.hip", "compat.hip"]
+SOURCES = ["automaton.cpp", "compact_tables.cpp", "sieve_image.cpp", "multi.cpp", "dispatch.cpp", "device_dfa.hip", "scan.hip", "lds_walk.hip", "sparse.hip", "post.hip", "segment.hip", "word.hip", "case.hip", "position.hip", "wildcard.hip", "approx.hip", "edit.hip", "sequence.hip", "rule.hip", "select.hip", "rewrite.hip", "extract.hip", "format.hip", "tally.hip", "lines.hip", "normalize.hip", "runtime.hip", "compat.hip"]
 ARCH = "gfx950"
 
 

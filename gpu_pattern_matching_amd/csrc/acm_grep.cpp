@@ -59,7 +59,7 @@ double now_us()
 	       "    acm_grep -f file -p file -B chunk_size -D devpos\n"
 	       "             -G global_ws -L local_ws [-m max]\n"
 	       "             [-w cpu_threads] [-R max] [-I file] [-P file] [-tvxFMAiSWcno]\n"
-	       "             [-r file -O dir] [-C N[,M] -T dir [-V]] [-k N]\n"
+	       "             [-r file -O dir] [-C N[,M] -T dir [-V]] [-k N] [-z SPEC]\n"
 	       "    acm_grep -h\n\n"
 	       "Options (those of ocl_aho_grep):\n"
 	       "  -f file        input: a file, a directory, or comma-separated files\n"
@@ -203,6 +203,18 @@ double now_us()
 	       "                 the budget are reported only where another piece chose them.  The -v line ends in\n"
 	       "                 ' edits <d> length <l>'.  Composes with and refuses what -k does, and with -c, which counts the\n"
 	       "                 unique records (extension)\n"
+	       "  -z SPEC        match against a normalised view of the input: SPEC is a comma list of 'url' (a %%XX triple counts as\n"
+	       "                 the byte it encodes, decoded once) and at most one of 'ws' (a run of tab, LF, VT, FF, CR and space\n"
+	       "                 counts as one space), 'strip' (those bytes do not count at all) and 'nul' (NUL bytes do not count:\n"
+	       "                 UTF-16LE text of ASCII reads as ASCII).  Every buffer is normalised on the device, each text alone;\n"
+	       "                 the scan and the passes of -W, -I and -A run on the normalised bytes, and every record is mapped\n"
+	       "                 back: offsets and counts are those of the file as it is, a match that ends in a triple ends on the\n"
+	       "                 triple's last digit, one that ends in a squeezed run on the run's first byte.  Needs -S: the\n"
+	       "                 texts are the files (with -t: the lines); a file that a buffer cuts is normalised piece by piece,\n"
+	       "                 and with -W the word test at such a cut sees the next piece's first byte as it is in the file,\n"
+	       "                 not as it would be normalised: use a -G/-B that holds every file whole.\n"
+	       "                 Composes with -x, -i, -I, -A, -W, -c, -v, -w, -D and -R (extension; not with -n, -C, -T, -o, -r,\n"
+	       "                 -O, -H, -N, -b, -k, -e, -P, -Q, -K, -E, -X, -V or -F)\n"
 	       "  -h             this help\n");
 	exit(EXIT_FAILURE);
 }
@@ -262,6 +274,10 @@ struct Config {
 	int edit = 0;            // -e: the patterns of -k are edit patterns, verified by the edit pass in the approx pass's place
 	int approx = 0;          // -k N: the budget; every pattern's records go through the approx pass (all_patterns is set too)
 	int only = 0;            // -o: every pattern of the records goes through the select pass (all_patterns is set too)
+	std::string norm_spec;   // -z
+	int norm = 0;            // -z: every buffer is normalised on the device, scanned normalised, its records mapped back
+	unsigned norm_flags = 0; // ACM_NORM_*
+	int norm_nul = 0;        // -z nul: the blank set is {00}
 	std::vector<int> devs;   // -D 0,1,...: worker i runs on devs[i % devs.size()] (the reference has one -D)
 	int max_results = MAX_RESULTS, pat_limit = -1;
 	long global_ws = -1, local_ws = -1, chunk = -1;
@@ -379,8 +395,17 @@ struct Buffer {   // one of the two staging buffers of a worker
 	     *d_results3_off = nullptr, *d_start_line = nullptr;   // (d_results3_off: the bucket pass's second output, not read)
 	int32_t *h_results3 = nullptr, *h_start_line = nullptr, *h_line_info = nullptr;
 	size_t line_ws_bytes = 0;
-	const void *text = nullptr;  // the scanned stream on the device (d_data, or d_packed)
+	const void *text = nullptr;  // the buffer's stream on the device (d_data, or d_packed)
 	size_t stream_len = 0;
+	// -z only: the normalised stream, the map back (keep words, block cells), where every text of seg_starts begins in
+	// it, the figures and their pinned twin ([0]: its length); the scan and the word and case passes read scan_text
+	void *d_nz_out = nullptr, *d_nz_keep = nullptr, *d_nz_block = nullptr, *d_nz_seg = nullptr, *d_nz_info = nullptr,
+	     *d_nz_rinfo = nullptr, *d_nz_ws = nullptr;
+	int32_t *h_nz_info = nullptr;
+	size_t nz_ws_bytes = 0;
+	const void *scan_text = nullptr;      // what is scanned: text, or with -z the normalised stream
+	size_t scan_len = 0;
+	const int32_t *scan_seg = nullptr;    // the text starts in scan_text: d_seg_start, or with -z d_nz_seg
 	bool packed = true;          // the chunks lie back to back in h_data: no offset remapping
 	int32_t *rec_pat = nullptr, *rec_off = nullptr;   // the scan's (or segment pass's) planes, for finish()
 	void *d_packed = nullptr;
@@ -458,6 +483,17 @@ void buffer_alloc(Buffer &b, const Config &c, void *stream)
 		CK(acm_rt_malloc(&b.d_seg_off, (size + 2) * 4));
 		CK(acm_rt_malloc(&b.d_seg_start, (G + 1) * 4));
 		CK(acm_rt_malloc(&b.d_seg_ws, b.seg_ws_bytes));
+	}
+	if (c.norm) {
+		b.nz_ws_bytes = acm_normalize_workspace_bytes(size, G + 1);
+		CK(acm_rt_malloc(&b.d_nz_out, size + 32));
+		CK(acm_rt_malloc(&b.d_nz_keep, (size / 64 + 2) * 8));
+		CK(acm_rt_malloc(&b.d_nz_block, (size / ACM_NORM_BLOCK + 3) * 4));
+		CK(acm_rt_malloc(&b.d_nz_seg, (G + 1) * 4));
+		CK(acm_rt_malloc(&b.d_nz_info, 32));
+		CK(acm_rt_malloc(&b.d_nz_rinfo, 32));
+		CK(acm_rt_malloc(&b.d_nz_ws, b.nz_ws_bytes));
+		CK(acm_rt_host_alloc((void **)&b.h_nz_info, 64));
 	}
 	if (c.words) {
 		b.word_ws_bytes = acm_word_workspace_bytes(size);
@@ -748,11 +784,32 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 		    (const int32_t *)b.d_starts, chunks, s));
 		b.text = b.d_packed;
 	}
+	if (c.segmented && !b.seg_starts.empty())
+		CK(acm_rt_memcpy_h2d(b.d_seg_start, b.seg_starts.data(), b.seg_starts.size() * 4, s));
+	b.scan_text = b.text;
+	b.scan_len = b.stream_len;
+	b.scan_seg = (const int32_t *)b.d_seg_start;
+	if (c.norm) {
+		// the stream normalised, every text (-S: a file, with -t a line) alone; what follows scans and filters the
+		// normalised stream, and finish() maps the records back.  The scan's length is a host argument: the host waits
+		// here for the figures.  A file that a buffer cuts is normalised piece by piece.
+		static const uint8_t nul_set[32] = { 1 };
+		const size_t ns = b.seg_starts.size();
+		CK(acm_normalize_async(b.text, b.stream_len, 0, c.norm_flags, c.norm_nul ? nul_set : nullptr, ' ', b.d_nz_out,
+		    (size_t)c.global_ws * c.chunk + 16, (uint64_t *)b.d_nz_keep, (int32_t *)b.d_nz_block,
+		    ns ? (const int32_t *)b.d_seg_start : nullptr, ns, ns ? (int32_t *)b.d_nz_seg : nullptr, (int32_t *)b.d_nz_info,
+		    b.d_nz_ws, b.nz_ws_bytes, s));
+		CK(acm_rt_memcpy_d2h(b.h_nz_info, b.d_nz_info, 32, s));
+		CK(acm_rt_stream_sync(s));
+		b.scan_text = b.d_nz_out;
+		b.scan_len = (size_t)b.h_nz_info[0];
+		b.scan_seg = (const int32_t *)b.d_nz_seg;
+	}
 	int32_t *pat = (int32_t *)b.d_pat, *off = (int32_t *)b.d_off;
 	acm_scan_batch sb;
 	memset(&sb, 0, sizeof(sb));
-	sb.d_text = b.text;
-	sb.n = b.stream_len;
+	sb.d_text = b.scan_text;
+	sb.n = b.scan_len;
 	sb.init_state = w.last_state;
 	if (prev) {
 		sb.init_state = 0;
@@ -772,16 +829,14 @@ void submit(Worker &w, Buffer &b, const Buffer *prev)
 	// patterns where the text has their case, the expansion (-A) lists them
 	const bool states = c.segmented || c.words || c.all_patterns || c.cased || c.seq;   // (-P needs -S)
 	sb.report = states ? ACM_REPORT_STATE : ACM_REPORT_HEAD;
-	if (c.segmented && !b.seg_starts.empty())
-		CK(acm_rt_memcpy_h2d(b.d_seg_start, b.seg_starts.data(), b.seg_starts.size() * 4, s));
 	if ((c.pos || c.wild || c.approx) && c.segmented && b.end_known) {   // a start at the stream's end, for the position, wildcard and approx passes alone: the last text is closed
 		b.end_start = (int32_t)b.stream_len;
 		CK(acm_rt_memcpy_h2d((int32_t *)b.d_seg_start + b.seg_starts.size(), &b.end_start, 4, s));
 	}
 	CK(acm_scan_batch_async(w.dfa, &sb));
 	if (c.segmented) {
-		CK(acm_segment_matches_async(w.dfa, pat, off, cap - 2, (const int32_t *)b.d_seg_start, b.seg_starts.size(),
-		    (long)b.stream_len, (c.all_patterns || c.words || c.cased || c.pos || c.seq) ? ACM_REPORT_STATE : ACM_REPORT_HEAD,
+		CK(acm_segment_matches_async(w.dfa, pat, off, cap - 2, b.scan_seg, b.seg_starts.size(),
+		    (long)b.scan_len,(c.all_patterns || c.words || c.cased || c.pos || c.seq) ? ACM_REPORT_STATE : ACM_REPORT_HEAD,
 		    (int32_t *)b.d_seg_pat, (int32_t *)b.d_seg_off, nullptr, cap, nullptr, b.d_seg_ws, b.seg_ws_bytes, s));
 		pat = (int32_t *)b.d_seg_pat;
 		off = (int32_t *)b.d_seg_off;
@@ -808,12 +863,12 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		int32_t *wp = (int32_t *)(every ? b.d_pat_all : b.d_word_pat);
 		int32_t *wo = (int32_t *)(every ? b.d_off_all : b.d_word_off);
 		const size_t wcap = every ? b.all_cap : b.scan_cap;
-		CK(acm_word_matches_async(w.dfa, pat, off, cap - 2, b.text, 0, (long)b.stream_len,
+		CK(acm_word_matches_async(w.dfa, pat, off, cap - 2, b.scan_text, 0, (long)b.scan_len,
 		    w.tail_len ? w.d_tail[w.tail_cur] : nullptr, w.tail_len, next_byte,
-		    c.segmented ? (const int32_t *)b.d_seg_start : nullptr, c.segmented ? b.seg_starts.size() : 0, nullptr,
+		    c.segmented ? b.scan_seg : nullptr, c.segmented ? b.seg_starts.size() : 0, nullptr,
 		    every, wp, wo, wcap, w.d_tail[w.tail_cur ^ 1], b.d_word_ws, b.word_ws_bytes, s));
 		w.tail_cur ^= 1;
-		w.tail_len = std::min((size_t)w.sh->max_pattern_len, w.tail_len + b.stream_len);
+		w.tail_len = std::min((size_t)w.sh->max_pattern_len, w.tail_len + b.scan_len);
 		pat = wp;
 		off = wo;
 		cap = wcap;
@@ -826,11 +881,11 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		const size_t ccap = every ? b.all_cap : b.scan_cap;
 		// the tail of the worker's stream so far is this buffer's before: a pattern that began in the buffer
 		// in front is compared whole (-S: the segment pass has left no entry that reaches into another text)
-		CK(acm_case_matches_async(w.dfa, pat, off, cap - 2, b.text, 0, (long)b.stream_len,
+		CK(acm_case_matches_async(w.dfa, pat, off, cap - 2, b.scan_text, 0, (long)b.scan_len,
 		    w.tail_len ? w.d_tail[w.tail_cur] : nullptr, w.tail_len, every, cp, co, ccap, w.d_tail[w.tail_cur ^ 1],
 		    b.d_case_ws, b.case_ws_bytes, s));
 		w.tail_cur ^= 1;
-		w.tail_len = std::min((size_t)w.sh->max_pattern_len, w.tail_len + b.stream_len);
+		w.tail_len = std::min((size_t)w.sh->max_pattern_len, w.tail_len + b.scan_len);
 		pat = cp;
 		off = co;
 		cap = ccap;
@@ -844,6 +899,10 @@ void finish(Worker &w, Buffer &b, int next_byte)
 		cap = b.all_cap;
 		CK(acm_rt_memcpy_d2h(b.h_all_count, pat, 4, s));
 	}
+	if (c.norm)   // every pass that reads the normalised stream has run: each record back to the last byte of the unit
+		      // that emitted its last byte, in the stream's own coordinates: what is counted, bucketed and printed
+		CK(acm_normalize_remap_async(nullptr, b.text, b.stream_len, 0, c.norm_flags, (const uint64_t *)b.d_nz_keep,
+		    (const int32_t *)b.d_nz_block, nullptr, off, cap - 2, off, nullptr, (int32_t *)b.d_nz_rinfo, s));
 	if (c.approx) {
 		// the mismatches of every piece's whole pattern, each in its own text.  The planes hold every pattern (the
 		// expansion's, or the case pass's); the tail of the worker's stream so far is this buffer's before: a span
@@ -1470,7 +1529,7 @@ int main(int argc, char **argv)
 	Shared sh;
 	Config &c = sh.cfg;
 	int opt;
-	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xor:O:C:VT:HNbk:e")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o, r, O, C, V, T, H, N, b, k, e
+	while ((opt = getopt(argc, argv, "f:m:p:tw:vxB:D:FG:L:R:MhAiSWcnI:P:Q:EK:Xor:O:C:VT:HNbk:ez:")) != -1) {   // ocl_aho_grep.c:411 + A, i, S, W, c, n, I, P, Q, E, K, X, o, r, O, C, V, T, H, N, b, k, e, z
 		switch (opt) {
 		case 'f': c.data_path = optarg; break;
 		case 'm': c.pat_limit = atoi(optarg); break;
@@ -1536,6 +1595,7 @@ int main(int argc, char **argv)
 			break;
 		}
 		case 'e': c.edit = 1; break;
+		case 'z': c.norm_spec = optarg; c.norm = 1; break;
 		default: usage();
 		}
 	}
@@ -1690,6 +1750,47 @@ int main(int argc, char **argv)
 		for (const auto &r : refused)
 			if (r.on) {
 				printf("ERROR: -k cannot be combined with %s: %s\n", r.opt, r.why);
+				err++;
+			}
+	}
+	if (c.norm) {
+		// SPEC: a comma list of url and at most one of ws, strip, nul
+		int blanks = 0;
+		bool bad = c.norm_spec.empty();
+		for (size_t at = 0; at <= c.norm_spec.size() && !bad;) {
+			const size_t comma = std::min(c.norm_spec.find(',', at), c.norm_spec.size());
+			const std::string word = c.norm_spec.substr(at, comma - at);
+			if (word == "url" && !(c.norm_flags & ACM_NORM_PERCENT)) {
+				c.norm_flags |= ACM_NORM_PERCENT;
+			} else if ((word == "ws" || word == "strip" || word == "nul") && !blanks++) {
+				c.norm_flags |= word == "ws" ? ACM_NORM_SQUEEZE : ACM_NORM_STRIP;
+				c.norm_nul = word == "nul";
+			} else {
+				bad = true;
+			}
+			at = comma + 1;
+		}
+		if (bad) {
+			printf("ERROR: -z takes a comma list of 'url' and at most one of 'ws', 'strip' and 'nul', each once: not '%s'\n",
+			    c.norm_spec.c_str());
+			err++;
+		}
+		if (!c.segmented) {   // a blank run and a triple end with their text: the texts must be told apart
+			printf("ERROR: -z needs -S: a file (with -t: a line) is normalised as a text of its own\n");
+			err++;
+		}
+		// the passes that read the text or count in its coordinates are each a follow-up: which coordinates?
+		const struct { bool on; const char *opt; } refused[] = {
+			{ c.lineno != 0, "-n" }, { c.ctx != 0, "-C" }, { !c.ext_dir.empty(), "-T" }, { c.only != 0 && c.repl_path.empty(), "-o" },
+			{ !c.repl_path.empty(), "-r" }, { !c.out_dir.empty(), "-O" }, { c.fmt_name != 0, "-H" }, { c.fmt_num != 0, "-N" },
+			{ c.fmt_off != 0, "-b" }, { c.approx != 0, "-k" }, { c.edit != 0, "-e" }, { !c.pos_path.empty(), "-P" },
+			{ !c.seq_path.empty(), "-Q" }, { c.rules != 0, "-K" }, { c.ext != 0, "-E" }, { c.grp != 0, "-X" }, { c.invert != 0, "-V" },
+			{ c.follow != 0, "-F" },
+		};
+		for (const auto &r : refused)
+			if (r.on) {
+				printf("ERROR: -z cannot be combined with %s: lines, ranges, positions and signatures over a normalised scan are "
+				       "not provided\n", r.opt);
 				err++;
 			}
 	}

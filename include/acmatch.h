@@ -1410,6 +1410,86 @@ int acm_line_context_lines_async(const int32_t *d_line_start, size_t capacity, c
     int32_t *d_rel_out, int32_t *d_begin_out, int32_t *d_next_out, int32_t *d_kind_out,
     size_t out_capacity, int32_t *d_ctx_info, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* Normalised scanning: a stage in front of the scan that makes the text the signatures were written for --
+ * percent triples decoded, blanks squeezed or stripped -- and a pass behind it that brings the records back
+ * to the bytes the caller has.  The scan and every pass behind it run unchanged on the normalised text.
+ * Text: acm_rewrite_async's contract (16-byte aligned, readable up to n rounded up to 16, n <= 2^31 - 17,
+ * d_text[i] the byte at offset text_origin + i, text_origin in int32; bytes behind n never influence
+ * anything).  With d_seg_start the n bytes are cut into texts as the segment pass cuts them (every start
+ * clamped into the text; the bytes in front of the first start are a text of their own); without it they
+ * are one text.
+ * flags: ACM_NORM_PERCENT, together with at most one of ACM_NORM_SQUEEZE and ACM_NORM_STRIP; 0 is legal (the
+ * output is the text).
+ *   Units.   With ACM_NORM_PERCENT offset i is a TRIPLE HEAD iff t[i] == '%', i + 2 lies inside i's own text
+ *            and t[i+1], t[i+2] are both in [0-9A-Fa-f].  A head and its two digits are a unit of length 3
+ *            whose value is the decoded byte; every byte in no triple is a unit of length 1 whose value is
+ *            the byte.  Decoding happens once (%2541 gives %41); a '%' whose digits would lie in the next
+ *            text or behind n stays literal.  Without the flag every byte is a unit.
+ *   Blanks.  A unit is BLANK iff its value is in the blank set: blank_mask, HOST memory of 32 bytes passed by
+ *            value (bit b % 8 of byte b / 8: byte b), NULL for {09, 0a, 0b, 0c, 0d, 20}.  With
+ *            ACM_NORM_SQUEEZE a blank unit is emitted as blank_byte (0..255) iff it is the first unit of its
+ *            text or the unit in front of it in the same text is not blank, else dropped: a run never
+ *            continues across a text start.  With ACM_NORM_STRIP every blank unit is dropped.  With neither
+ *            no unit is blank.  Every other unit is emitted with its value.
+ *   Output.  The emitted bytes in order, m <= n of them.  For output offset o, first(o) = text_origin + the
+ *            offset of the emitting unit's first byte and last(o) = first(o) + the unit's length - 1.  A
+ *            squeezed run's emitter is its first unit only.
+ *   d_out      receives the first min(m, out_capacity) bytes; no byte at or behind that point is written.
+ *              d_out == NULL with out_capacity == 0: the figures only.  16-byte aligned; overlaps neither the
+ *              text nor the other outputs
+ *   d_keep     uint64[ceil(n / 64)], required: bit i % 64 of word i / 64 is set iff byte i emits (it is the
+ *              first byte of a unit that is emitted); bits behind n are 0
+ *   d_block    int32[ceil(n / ACM_NORM_BLOCK) + 1], required: cell j = the output bytes emitted by the input
+ *              in front of byte j * ACM_NORM_BLOCK; the last cell is m.  With d_keep the whole offset map, in
+ *              1/8 + 1/256 of the text
+ *   d_seg_out  with d_seg_start, both or neither: int32[segments]; cell k = the output bytes emitted by the
+ *              input in front of start k (clamped): where text k begins in the output, ready to be the
+ *              segment pass's d_seg_start over the normalised text
+ *   d_info     int32[8], required, written whole: [0] m, [1] units dropped, [2] triples (emitted or not),
+ *              [3] blank units emitted, [4] 1 iff m > out_capacity and d_out is not NULL (never cut
+ *              silently), [5..7] 0
+ * Every run gives the same bytes (no order is decided by atomics).  No read leaves the inputs and no write
+ * leaves the outputs and the workspace.  Stream-ordered, no host sync, no allocation, no host read of device
+ * data; argument errors (acm_rewrite_async's list; unknown flag bits, squeeze with strip, blank_byte outside
+ * 0..255 under squeeze, a NULL d_keep or d_block) return ACM_ERR_ARG before anything is enqueued.
+ * Three launches on a fixed grid: the keep words and per-block counts from one read of the text, the block
+ * sums, and a write kernel that owns 16 KiB of INPUT per tile, ranks the kept bytes, stages them in LDS and
+ * streams them out in aligned 16-byte stores (csrc/normalize.hip).  With segments a zero-fill and a launch
+ * over the starts go in front (a bit per start) and one launch over the starts behind (d_seg_out).  The
+ * workspace query is monotone in both arguments and a multiple of 256.
+ *
+ * acm_normalize_remap_async: one pass over records in the scan's cell layout (the count read from cell 0 of
+ * d_off_plane on the device, clamped to max_records), whose offsets are offsets into the normalised text.
+ * The text, n, text_origin, flags, d_keep and d_block are the ones the normalise call got and wrote.
+ * d_off_out's record is last(off).  With d_pat_plane (pattern indices) and d_start_out, d_start_out's record
+ * is first(s), s where the select pass says the match starts (off - length + 1 for a plain pattern).  An
+ * offset or start outside [0, m) and a cell that is no pattern index give the cell -1, and such records are
+ * counted; whatever the planes hold, nothing is read or written outside.  Cell 0 of each output is the count.
+ * d_off_out may equal d_off_plane (its cell 0 then stays what it is). d_info int32[8]: [0] records looked at, [1] records with an unmapped
+ * cell, rest 0.  A triple is told from a '%' in front of two literal digits by the digits' keep bits (the
+ * remap is not given the text starts).  One case is therefore not exact: under ACM_NORM_STRIP with a blank set
+ * that holds hex digits, a literal '%' whose two digits lie across a text start and are both stripped is taken
+ * for a triple, and last(off) is then 2 too large.  With the default set, and with any set without hex digits,
+ * the remap is exact.
+ * ACM_ERR_ARG: a NULL map, plane, output or d_info, d_start_out without d_pat_plane, d_pat_plane without the
+ * automaton, bad flags, max_records over 2^31 - 2.  A zero-fill of d_info and one launch, a thread a record.
+ *
+ * Not provided: normalisation continued across calls (give whole texts); repeated decoding, '+' as space,
+ * %uXXXX, HTML entities; case folding (the automaton's own nocase does that); lines, extraction, rewriting
+ * and position windows over a normalised scan; a scan that takes its length from the device (m lives on the
+ * device and acm_scan_async's length is a host argument: a caller reads d_info[0] back once in between). */
+enum { ACM_NORM_PERCENT = 1, ACM_NORM_SQUEEZE = 2, ACM_NORM_STRIP = 4 };
+#define ACM_NORM_BLOCK 1024
+size_t acm_normalize_workspace_bytes(size_t max_text, size_t segments);
+int acm_normalize_async(const void *d_text, size_t n, long text_origin, unsigned flags,
+    const uint8_t *blank_mask, int blank_byte, void *d_out, size_t out_capacity,
+    uint64_t *d_keep, int32_t *d_block, const int32_t *d_seg_start, size_t segments, int32_t *d_seg_out,
+    int32_t *d_info, void *d_workspace, size_t workspace_bytes, void *stream);
+int acm_normalize_remap_async(const acm_dfa *, const void *d_text, size_t n, long text_origin,
+    unsigned flags, const uint64_t *d_keep, const int32_t *d_block, const int32_t *d_pat_plane,
+    const int32_t *d_off_plane, size_t max_records, int32_t *d_off_out, int32_t *d_start_out,
+    int32_t *d_info, void *stream);
+
 int acm_scan_batch_async(const acm_dfa *, const acm_scan_batch *);
 
 /* count batches with one call, enqueued in array order: what a worker pool
