@@ -9,7 +9,9 @@ it goes on with the file of the buffer in front.  Written from the rules of the 
     before it; the buffer is packed while no short chunk has another chunk behind it.
 
 layout() needs nothing of the project.  On top of it one function per file-writing mode gives {file name: expected
-bytes}: the models (extract_model, format_model, select_model, rewrite_model) over the records bytes.find gives."""
+bytes}: the models (extract_model, format_model, select_model, rewrite_model) over the records bytes.find gives.
+normalized_hits() gives the -v lines of a run with -S -z: every piece of a file that a buffer holds normalised alone by
+normalize_model, the pieces of a text joined, bytes.find over that."""
 import collections
 import os
 
@@ -164,6 +166,68 @@ def rewrite_expected(files, B, G, workers, pats, repl, segmented=False, nocase=F
         for k, (_, f) in enumerate(b.starts):
             out[os.path.basename(files[f][0])] += data[seg[k]:seg[k + 1] if k + 1 < len(seg) else len(data)]
     return out, dropped, buffers
+
+
+Hit = collections.namedtuple("Hit", "pattern file offset slot spans")
+Hit.__doc__ = """pattern: its index; file: an index into the list given; offset: of the match's last byte in its file (the last
+byte of the unit that emitted the match's last byte); slot: the chunk of its buffer that byte lies in; spans: the
+match began in an earlier piece than it ends in"""
+
+
+def pieces(files, B, G, workers, lines=False):
+    """per worker the pieces a run with -S -z normalises each alone, in stream order: (file, offset in the file, bytes,
+    it begins a text, the index of its buffer, its offset in that buffer's stream).  A buffer's stream is cut at its
+    starts; with lines also behind every newline.  A piece begins a text when it is of another file than the piece in
+    front of it, or with lines when that piece ended a line; else it goes on with the text in front: a file that a
+    buffer cuts, a line that one cuts.  (With lines the layout is still the one of binary mode: it is the layout of a
+    run with -t only where it cuts no line.)"""
+    out = []
+    for bufs in layout(files, B, G, workers):
+        mine, done, last_file, line_open = [], collections.Counter(), None, False
+        for b in bufs:
+            at = [s for s, _ in b.starts] + [len(b.stream)]
+            for k, (s, f) in enumerate(b.starts):
+                raw = b.stream[s:at[k + 1]]
+                parts = raw.split(b"\n") if lines else [raw]         # (only \n ends a line: not bytes.splitlines)
+                for p in [p + b"\n" for p in parts[:-1]] + parts[-1:]:
+                    if not p:
+                        continue
+                    mine.append((f, done[f], p, f != last_file or (lines and not line_open), b.index, s))
+                    done[f] += len(p)
+                    s += len(p)
+                    last_file, line_open = f, not p.endswith(b"\n")
+        out.append(mine)
+    return out
+
+
+def normalized_hits(files, pats, B, G, workers, flags, blanks=None, nocase=False, words=False, lines=False):
+    """-S -z: the sorted Hits of a run.  Every piece (pieces()) is normalised alone by the model; a text for matching is
+    the concatenation of the normalised pieces of one file (with lines: of one line), since the scan goes on from one
+    piece into the next in the state the piece in front left; every pattern is found in it with bytes.find (entries();
+    nocase: one flag, or one per pattern); a hit lies where the model's last[] of the piece that holds its last byte
+    says.  Without -A a run reports one pattern per end: give patterns none of which is a suffix of another."""
+    import normalize_model as nm
+    fold = list(nocase) if isinstance(nocase, (list, tuple)) else [bool(nocase)] * len(pats)
+    hits = []
+    for w, mine in enumerate(pieces(files, B, G, workers, lines)):
+        bufs = layout(files, B, G, workers)[w]
+        texts = []
+        for p in mine:
+            if p[3]:
+                texts.append([])
+            texts[-1].append((p, nm.normalize(p[2], flags, blanks)))
+        for text in texts:
+            out = b"".join(x.out for _, x in text)
+            ends = np.cumsum([x.m for _, x in text])                   # the normalised text in front of the end of every piece
+            for i, pat in enumerate(pats):
+                for e in entries([out], [pat], fold[i], words)[1].tolist():
+                    j = int(np.searchsorted(ends, e, side="right"))
+                    js = int(np.searchsorted(ends, e - len(pat) + 1, side="right"))
+                    (f, at, raw, _, index, s), x = text[j]
+                    last = int(x.last[e - (int(ends[j - 1]) if j else 0)])
+                    sizes = np.cumsum([n for _, n in bufs[index].chunks])
+                    hits.append(Hit(i, f, at + last, int(np.searchsorted(sizes, s + last, side="right")), js < j))
+    return sorted(hits)
 
 
 def numbered_expected(files, workers, pats):

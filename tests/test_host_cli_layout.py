@@ -4,12 +4,15 @@ for the inputs of test_gpu_cli_buffers.py: the model is right for those inputs w
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 import cli_layout as lay
+import normalize_model as nm
 import test_gpu_cli_buffers as cb
 import test_gpu_extract_cli as xc
 import test_gpu_format_cli as fc
+import test_gpu_normalize_cli_buffers as nb
 import test_gpu_rewrite_cli as rc
 import test_gpu_select_cli as sc
 
@@ -191,3 +194,93 @@ def test_set_R_against_grep(tmp_path):
         r = subprocess.run([xc.GREP, "-a", "-o", "-b", "-F", "-f", pats, path], capture_output=True, env=dict(os.environ, LC_ALL="C"), timeout=60)
         assert r.stdout.splitlines() == got.get(path, []), path
         assert bool(t) == (len(got.get(path, [])) > 20)
+
+
+# ------------------------------------------------------------------ normalized_hits (-S -z)
+
+
+def whole_file_hits(named, pats, flags, blanks=None, nocase=False, words=False):
+    """every file normalised whole: (pattern, file, offset of the last byte)"""
+    out = set()
+    for f, (_, t) in enumerate(named):
+        x = nm.normalize(t, flags, blanks)
+        cells, offs = lay.entries([x.out], pats, nocase, words)
+        out |= {(p, f, int(x.last[e])) for p, e in zip(cells.tolist(), offs.tolist())}
+    return out
+
+
+def stream_cut_hits(named, pats, b, g, workers, flags):
+    """the brute force over the worker's stream: it is cut where a buffer or a file begins, every stream[a:b] is
+    normalised alone, the pieces of a file are joined"""
+    out = set()
+    for (mine, stream, bounds), bufs in zip(lay.streams(named, workers), lay.layout(named, b, g, workers)):
+        cuts = sorted({x.base for x in bufs} | set(bounds.tolist()))
+        for k, f in enumerate(mine):
+            edges = [c for c in cuts if bounds[k] <= c <= bounds[k + 1]]
+            norm = [(a, nm.normalize(stream[a:z], flags)) for a, z in zip(edges, edges[1:])]
+            text, at = b"".join(x.out for _, x in norm), np.cumsum([0] + [x.m for _, x in norm])
+            for p, e in zip(*(v.tolist() for v in lay.entries([text], pats))):
+                j = int(np.searchsorted(at, e, side="right")) - 1
+                out.add((p, f, norm[j][0] + int(norm[j][1].last[e - at[j]]) - int(bounds[k])))
+    return out
+
+
+def flat(hits):
+    return {(h.pattern, h.file, h.offset) for h in hits}
+
+
+def test_normalized_hits_of_whole_files():
+    """where no buffer cuts a file the hits are those of every file normalised whole, whatever the layout"""
+    for workers in (1, 2, 3):
+        named = nb.whole_set(workers)
+        for spec in ("url,ws", "strip,url", "nul", "url"):
+            flags, blanks = nb.SPECS[spec]
+            for kw in (dict(), dict(nocase=True), dict(words=True)):
+                want = whole_file_hits(named, nb.EVERY, flags, blanks, **kw)
+                for b, g in ((nb.B, nb.G_WHOLE), (4096, 16), (64, 1 << 12)):
+                    assert not lay.cut_files(named, b, g, workers)
+                    got = lay.normalized_hits(named, nb.EVERY, b, g, workers, flags, blanks, **kw)
+                    assert flat(got) == want and len(got) == len(want) > 10 and not any(h.spans for h in got)
+    # the slot is the chunk of the buffer that holds the byte
+    named = [("a", b"x" * 70 + b"a href"), ("b", b"a%20href")]
+    assert lay.normalized_hits(named, [b"a href"], 64, 16, 1, nm.PERCENT) == [lay.Hit(0, 0, 75, 1, False), lay.Hit(0, 1, 7, 2, False)]
+
+
+def test_normalized_hits_of_cut_files():
+    for workers in (1, 2):
+        named, planted = nb.cut_set(workers)
+        for flags in (nm.PERCENT | nm.SQUEEZE, nm.PERCENT | nm.STRIP, nm.SQUEEZE):
+            for b, g in ((nb.B, nb.G_CUT), (16, 16), (1024, 1)):
+                got = lay.normalized_hits(named, nb.EVERY, b, g, workers, flags)
+                assert flat(got) == stream_cut_hits(named, nb.EVERY, b, g, workers, flags) and len(got) > 1000
+        assert flat(lay.normalized_hits(named, nb.ONE, nb.B, nb.G_CUT, workers, 3)) != whole_file_hits(named, nb.ONE, 3)
+    # by hand: the triple and the run that a cut divides are not joined, the match that it divides is found
+    named = [("f", b".....a%2" + b"0href.a " + b" href.a " + b"href....")]
+    assert [(h.offset, h.spans) for h in lay.normalized_hits(named, [b"a href"], 8, 1, 1, 3)] == [(27, True)]
+    assert sorted(o for _, _, o in whole_file_hits(named, [b"a href"], 3)) == [12, 20, 27]
+
+
+def test_normalized_hits_of_lines():
+    named = [("f", b"a\nhref a \n href%0ab\n\na b"), ("g", b"a href\r\na%20b")]
+    one = lay.normalized_hits(named, [b"a href", b"a b"], 64, 16, 1, 3, lines=True)
+    assert [(h.pattern, h.file, h.offset) for h in one] == [(0, 1, 5), (1, 0, 23), (1, 1, 12)]
+    assert (0, 0, 5) in whole_file_hits(named, [b"a href", b"a b"], 3)
+    # a line that a buffer cuts goes on
+    assert [h[:3] for h in lay.normalized_hits([("f", b"xxxxxxa href\n")], [b"a href"], 8, 1, 1, 3, lines=True)] == [(0, 0, 11)]
+
+
+def test_the_normalized_sets_lie_as_meant():
+    """the conditions test_gpu_normalize_cli_buffers.py states about its inputs, without a device"""
+    for workers in (1, 2, 3):
+        nb.check_whole(nb.whole_set(workers), workers)
+        nb.whole_expected(workers, "url,ws", ["-v"])
+        nb.whole_expected(workers, "strip,url", ["-v", "-i"])
+        nb.whole_expected(workers, "nul", ["-v", "-c", "-A"])
+    nb.check_whole(nb.whole_set(2, True), 2, True)
+    for workers in (1, 2):
+        for every in (False, True):
+            nb.word_expected(workers, every)                               # word borders that exist on one side only
+            nb.cut_expected(workers, every)                                # hits across cuts, and others than whole files give
+        nb.case_expected(workers)                                          # exact dropped, folding kept
+        nb.line_expected(workers, "url,ws", ["-v"])
+        nb.line_expected(workers, "strip,url", ["-v", "-A"])

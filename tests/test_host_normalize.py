@@ -133,3 +133,40 @@ def test_the_local_rule_is_the_serial_walk(flags):
             starts = sorted(set(rng.integers(0, n + 1, rng.integers(0, max(n // 8, 2))).tolist()))
             r = nm.normalize(t, flags, seg_start=starts)
             assert np.array_equal(r.keep, local_keep(t, flags, [s for s in starts if s < n])), (n, k, t, starts)
+
+
+# ------------------------------------------------------------------ the inputs of the GPU tests past one buffer
+
+
+def test_scale_inputs_are_what_they_are_meant_to_be():
+    """what test_gpu_normalize_scale.py states about its inputs, from the model alone: more starts and more output than
+    the largest grid has threads, equal consecutive d_block cells in every text of dropped cells, the starts of the
+    wildcard records on offset 0, at -1, on a triple and on a squeezed run's blank"""
+    import test_gpu_normalize_scale as sc
+    for flags in (PERCENT | SQUEEZE, PERCENT | STRIP):
+        text, starts, x = sc.check_grid_case(flags)
+        assert x.m > 262144 and starts.size == 300000
+        sc.check_wild_case(flags)
+    for name, t, modes, starts, least in sc.dropped_cell_texts():
+        for flags in modes:
+            x = nm.normalize(t.tobytes(), flags)
+            assert sc.equal_cells(x) >= least >= 1, (name, flags)
+            assert any(x.block[s // nm.BLOCK] == x.block[s // nm.BLOCK + 1] for s in starts if s < t.size), name   # a start in a dropped cell
+    period, p = sc.tiled_period()
+    offs = sc.tiled_offsets(p, period.size, sc.REPS)
+    assert offs.max() == sc.REPS * p.m + 1 and 2000 < offs.size < 5000
+    tiled = sc.Tiled(p, period.size, sc.REPS)
+    assert tiled.last[p.m] == period.size + p.last[0] and tiled.first[tiled.m - 1] == (sc.REPS - 1) * period.size + p.first[-1]
+
+
+def test_chain_inputs_are_what_they_are_meant_to_be():
+    """what test_gpu_normalize_chain.py states about its inputs: m % 16 is 1 and 15, more than 1000 matches in every case,
+    one that ends on a triple and one that starts on a squeezed run's blank, parts cut inside a triple and a run, empty
+    parts and parts that strip to nothing, exact patterns dropped where folding ones are kept"""
+    import test_gpu_normalize_chain as ch
+    assert sorted({(s, ph) for s, ph, _ in ch.SHAPES}) == [("one", 1), ("one", 15), ("texts", 1), ("texts", 15)]
+    for shape, phase, flags in ch.SHAPES:
+        for name in ch.CASES:
+            ch.check_expected(name, shape, phase, flags)
+    assert ch.no_suffixes(ch.PLAIN) and ch.no_suffixes(ch.NOCASE) and ch.no_suffixes(ch.MIXED) and not ch.no_suffixes(ch.MIXED_ALL)
+    assert all(len(p) >= 3 for p, _ in ch.PLAIN)
